@@ -8,7 +8,9 @@ rewards/dones uploaded; GAE + advantage normalisation; then epoch x n_minibatch 
 inside the first conv, forward, fused loss, backward, clip + Adam) -- everything agents/ppo.py:225-255 does
 except env.step and logging ("rollout inference + H2D + GAE + epoch passes of minibatch updates").
 
-    python bench.py                      # 1 GPU
+    python bench.py                      # 1 GPU: the headline line only
+    python bench.py --full               # + the fp32 parity-mode sub-record and the CPU baseline
+    python bench.py --dump-outputs DIR   # + what the last timed step computed, as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W     # weak scaling: 256 envs per GPU, global minibatch 8192
 """
@@ -208,13 +210,38 @@ def host_cores():
     return min(n, 16)
 
 
+LOSS_KEYS = ("Loss/pi", "Loss/v", "Loss/entropy", "Loss/x_entropy", "Loss/feature_sparsity", "Loss/total")
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(path, eng, summary):
+    """What the timed path computed in its last step, as a caller of it receives it: the flat parameter vector after the last
+    optimizer step (layout.py order), the last rollout's actions / log-probs / values and its GAE returns / normalised advantages
+    as they lie in the rollout ring, and the update's loss summary (PPO.optimize's finite entries, in LOSS_KEYS order).
+    float32, the losses float64; about 4 MB at hard-500."""
+    from mi355.engine import F_ACT, F_LOGP, F_VALUE, F_RET, F_ADV
+    arrays = {"params": eng.get_params(), "actions": eng.read_field(F_ACT), "log_probs": eng.read_field(F_LOGP),
+              "values": eng.read_field(F_VALUE), "returns": eng.read_field(F_RET), "advantages": eng.read_field(F_ADV),
+              "losses": np.array([summary[k] for k in LOSS_KEYS], np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed PPO iterations")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--param_name", default="hard-500")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline: the fp32 parity-mode sub-record (`fp32`, a child process) and "
+                    "the CPU baseline (`cpu_baseline`); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (parameters, rollout "
+                    "ring fields, losses) as DIR/<name>.npy; the inputs are the same from run to run for the same arguments")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample", type=int, default=32, help="rollout steps (of all E envs) the CPU baseline leg runs")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--precision", default="bf16", choices=["fp32", "bf16"],
@@ -233,12 +260,14 @@ def main():
                     "the default uploads every step's E frames from pinned host memory inside the timed region, as the real loop must")
     ap.add_argument("--engine-only", action="store_true", help="diagnostic: the rollout phase drives mi_rollout_submit / mi_rollout_wait directly with frames "
                     "that already lie in pinned buffers (rounds 1-2's loop) instead of the product's collector PPO._collect on an EnvGroups env")
-    ap.add_argument("--no-fp32-record", action="store_true", help="skip the three extra iterations in the fp32 parity mode (the `fp32` sub-record)")
+    ap.add_argument("--no-fp32-record", action="store_true", help="with --full: skip the three extra iterations in the fp32 parity mode (the `fp32` sub-record)")
     ap.add_argument("--n-actions", type=int, default=9, help="action count A: 9 = the reference's default for Procgen (ActionWrapper merges the 15 key "
                     "combinations by name, helper_local.py:653), 15 = --no-reduce_duplicate_actions")
     ap.add_argument("--rollout-groups", type=int, default=0, help="env groups of the pipelined rollout (0 = auto: 4 when n_envs >= 128 divides, else 2; "
                     "1 = the reference's serial step: upload, forward, read-back one after the other)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -437,10 +466,12 @@ def main():
                "kernel_profile_period": (0 if args.no_kernel_profile else max(1, args.profile_period)),    # kernels[]: the bracketed sample only
                "kernels": sorted(prof, key=lambda r: -r["ms"])[:24],
                "loss_total": summary["Loss/total"]}
-        if world == 1 and args.precision == "bf16" and not args.no_fp32_record and not args.engine_only and args.rank_share == 1:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, eng, summary)
+        if args.full and world == 1 and args.precision == "bf16" and not args.no_fp32_record and not args.engine_only and args.rank_share == 1:
             eng.close()
             out["fp32"] = fp32_record(args)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(hp, E, A, args.cpu_sample, args.cpu_threads or host_cores())
         print(json.dumps(out))
     if world > 1:

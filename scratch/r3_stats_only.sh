@@ -4,7 +4,7 @@ set -o pipefail
 T=${1:-r03_run10}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out
 cd $R
-python bench.py > $O/${T}_bf16_bench.json 2> $O/${T}_bench.err || exit 1
+python bench.py --full > $O/${T}_bf16_bench.json 2> $O/${T}_bench.err || exit 1
 python bench.py --no-cpu-baseline --no-fp32-record > $O/${T}b_bf16_bench.json 2>> $O/${T}_bench.err || exit 2
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r3_prof -o runc -- python3 $R/bench.py --no-cpu-baseline --no-fp32-record --steps 3 --warmup 1 > $O/${T}_bf16_bench_under_rocprof.json 2> $O/r3_prof.err || exit 3
