@@ -32,7 +32,8 @@ typedef struct mi_config {
     int32_t obs_dim;       /* MLP only: observation vector length (IMPALA is fixed 64x64x3 uint8 NHWC) */
     int32_t mlp_depth;     /* MLP only: MLPModel depth (>= 2) */
     int32_t mlp_width;     /* MLP only: MLPModel mid_weight */
-    int32_t out_dim;       /* embedder.output_dim: 256 for IMPALA, latent_size for MLP */
+    int32_t out_dim;       /* embedder.output_dim.  IMPALA: a multiple of 64 in [64, 512] (0 = 256, the reference's default);
+                              MLP: latent_size */
     int32_t max_batch;     /* largest number of samples one mi_minibatch / mi_forward call may carry */
     int32_t device;        /* HIP device ordinal */
     int32_t precision;     /* IMPALA activations / activation gradients in HBM: 0 = fp32 (parity mode), 1 = bf16 storage +

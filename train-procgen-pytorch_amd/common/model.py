@@ -77,14 +77,22 @@ class ImpalaBlock(nn.Module):
         self.res2 = ResidualBlock(out_channels)
 
 
+# embedder widths the HIP kernels are built for (mi_create checks the same set)
+IMPALA_OUTPUT_DIMS = tuple(range(64, 513, 64))
+
+
 class ImpalaModel(_EngineBacked):
     arch = "impala"
 
     def __init__(self, in_channels, output_dim=256, latent_dim=32, **kwargs):
         super().__init__()
-        if in_channels != 3 or output_dim != 256 or latent_dim != 32:
-            raise NotImplementedError("the HIP IMPALA-CNN is built for 3x64x64 frames, latent_dim 32, output_dim 256 "
-                                      "(every procgen param set in hyperparams/procgen/config.yml)")
+        if in_channels != 3:
+            raise NotImplementedError(f"in_channels={in_channels}: the HIP IMPALA-CNN is built for 3x64x64 (RGB) frames")
+        if latent_dim != 32:
+            raise NotImplementedError(f"latent_dim={latent_dim}: the HIP IMPALA-CNN is built for latent_dim 32 (block3's channel count)")
+        if output_dim not in IMPALA_OUTPUT_DIMS:
+            raise NotImplementedError(f"output_dim={output_dim}: the HIP IMPALA embedder supports output_dim in "
+                                      f"{list(IMPALA_OUTPUT_DIMS)} (multiples of 64 from 64 to 512)")
         self.block1 = ImpalaBlock(in_channels, 16)
         self.block2 = ImpalaBlock(16, 32)
         self.block3 = ImpalaBlock(32, latent_dim)

@@ -44,7 +44,7 @@ class CategoricalPolicy(nn.Module):
 
     def param_shapes(self):
         if self.arch == "impala":
-            return layout.impala_param_shapes(self.action_size)
+            return layout.impala_param_shapes(self.action_size, output_dim=self.embedder.output_dim)
         e = self.embedder
         return layout.mlp_param_shapes(self.action_size, e.input_size, e.depth, e.mid_weight, e.output_dim)
 

@@ -226,11 +226,27 @@ void launch_gru_value_bwd(const float* gi, const float* gh, const float* hm, con
 void launch_gru_gates(const float* gi, const float* gh, const float* hm, float* h_out, float* feat_out, int n, int H, hipStream_t st);
 
 // ---------------------------------------------------------------- embedder.fc on the bf16 matrix cores (fc_bf16.hip)
+// IMPALA embedder widths (output_dim): the multiples of 64 in [64, 512] (mi_create).  The bf16 fc kernels and the fc section of
+// repack_all_kernel are templates on the width; this maps a run-time width onto F<D>::run(args...) and returns false for any other.
+template <template <int> class F, typename... Args>
+static inline bool fc_dispatch_width(int D, Args... args) {
+    switch (D) {
+    case 64: F<64>::run(args...); return true;
+    case 128: F<128>::run(args...); return true;
+    case 192: F<192>::run(args...); return true;
+    case 256: F<256>::run(args...); return true;
+    case 320: F<320>::run(args...); return true;
+    case 384: F<384>::run(args...); return true;
+    case 448: F<448>::run(args...); return true;
+    case 512: F<512>::run(args...); return true;
+    default: return false;
+    }
+}
 struct FcNtArgs;
-void launch_fc_fwd_small_bf16(const void* X, const unsigned short* Wp, const float* bias, float* feat, int n, hipStream_t st);
+void launch_fc_fwd_small_bf16(const void* X, const unsigned short* Wp, const float* bias, float* feat, int n, int D, hipStream_t st);
 void launch_fc_pack(const float* w, unsigned short* wp, unsigned short* wt, int N, int K, hipStream_t st);
-void launch_fc_fwd_bf16(const void* x_bf16, const unsigned short* wp, const float* bias, float* y, int n, hipStream_t st);
-void launch_fc_dgrad_bf16(const float* dy, const unsigned short* wt, const void* mask_bf16, void* dx_bf16, int n, hipStream_t st);
+void launch_fc_fwd_bf16(const void* x_bf16, const unsigned short* wp, const float* bias, float* y, int n, int D, hipStream_t st);
+void launch_fc_dgrad_bf16(const float* dy, const unsigned short* wt, const void* mask_bf16, void* dx_bf16, int n, int D, hipStream_t st);
 void launch_fc_tn(const float* A, const unsigned short* B, float* gW, float* ws, size_t ws_floats, int M, int N, int K, hipStream_t st);
 
 // blocks 2 + 3 of a rollout-sized batch (n <= 256) in one launch (rollout_bf16.hip): bank / bias = their ten convs in network order
@@ -266,4 +282,4 @@ void launch_heads_fwd(const float* feat, const float* Wh, const float* bh, float
 void launch_pull_bytes(const void* host_src /* pinned, device-visible */, void* dst, size_t bytes /* multiple of 16 */, hipStream_t st);
 void launch_pull_i32(const int32_t* host_src /* pinned, device-visible */, int32_t* dst, int n, hipStream_t st);
 void launch_repack_all(const float* params, unsigned short* banks, const BankDesc* d_desc, int n_desc, const float* c1_w, unsigned short* c1_bank /* or null */,
-                       const float* fc_w, unsigned short* fc_wp, unsigned short* fc_wt, hipStream_t st);      // the three re-packing launches of an IMPALA bf16 context in one
+                       const float* fc_w, unsigned short* fc_wp, unsigned short* fc_wt, int H /* output_dim */, hipStream_t st);      // the three re-packing launches of an IMPALA bf16 context in one

@@ -1273,7 +1273,8 @@ void launch_pack_conv1_bank(const float* w, unsigned short* bank, hipStream_t st
 int conv1_bank_elems() { return 16 * C1_WS; }
 // Every bf16 image of the parameters in ONE launch after an optimizer step (three launches before): blocks [0, 8 n_desc) the conv filter
 // banks (pack_banks_kernel's element loop, 8 blocks per bank), the next few block1.conv's bank, the rest embedder.fc's two packed
-// images ([256][2048] for the forward, [2048][256] for the data gradient; fc_bf16.hip).
+// images ([D][2048] for the forward, [2048][D] for the data gradient; fc_bf16.hip), D = output_dim.
+template <int D>
 __global__ void repack_all_kernel(const float* __restrict__ params, unsigned short* __restrict__ banks, const BankDesc* __restrict__ desc, int n_desc,
                                   const float* __restrict__ c1_w, unsigned short* __restrict__ c1_bank,
                                   const float* __restrict__ fc_w, unsigned short* __restrict__ fc_wp, unsigned short* __restrict__ fc_wt) {
@@ -1301,17 +1302,24 @@ __global__ void repack_all_kernel(const float* __restrict__ params, unsigned sho
         return;
     }
     b -= C1B;
-    const int e = b * 256 + threadIdx.x;                   // embedder.fc: N = 256 rows of K = 2048
-    if (e < 256 * 2048) {
+    const int e = b * 256 + threadIdx.x;                   // embedder.fc: N = D rows of K = 2048
+    if (e < D * 2048) {
         const unsigned short h = f2bf(fc_w[e]);
         fc_wp[e] = h;                                      // [n][k]
-        fc_wt[(long long)(e % 2048) * 256 + e / 2048] = h; // [k][n]
+        fc_wt[(long long)(e % 2048) * D + e / 2048] = h;   // [k][n]
     }
 }
+template <int D> struct RepackAll {
+    static void run(const float* params, unsigned short* banks, const BankDesc* d_desc, int n_desc, const float* c1_w, unsigned short* c1_bank,
+                    const float* fc_w, unsigned short* fc_wp, unsigned short* fc_wt, hipStream_t st) {
+        const int blocks = 8 * n_desc + (16 * C1_WS + 255) / 256 + D * 2048 / 256;
+        hipLaunchKernelGGL(repack_all_kernel<D>, dim3(blocks), dim3(256), 0, st, params, banks, d_desc, n_desc, c1_w, c1_bank, fc_w, fc_wp, fc_wt);
+    }
+};
 void launch_repack_all(const float* params, unsigned short* banks, const BankDesc* d_desc, int n_desc, const float* c1_w, unsigned short* c1_bank,
-                       const float* fc_w, unsigned short* fc_wp, unsigned short* fc_wt, hipStream_t st) {
-    const int blocks = 8 * n_desc + (16 * C1_WS + 255) / 256 + 256 * 2048 / 256;
-    hipLaunchKernelGGL(repack_all_kernel, dim3(blocks), dim3(256), 0, st, params, banks, d_desc, n_desc, c1_w, c1_bank, fc_w, fc_wp, fc_wt);
+                       const float* fc_w, unsigned short* fc_wp, unsigned short* fc_wt, int H, hipStream_t st) {
+    if (!fc_dispatch_width<RepackAll>(H, params, banks, d_desc, n_desc, c1_w, c1_bank, fc_w, fc_wp, fc_wt, st))
+        mi_launch_fail("repack_all: no fc image kernel for this output_dim");
 }
 __global__ __launch_bounds__(256, 4) void conv1_pool_fwd_bf16_kernel(ConvArgs a, const unsigned short* lut16, unsigned short* p_out, uint8_t* p_arg) {      // 4 waves per SIMD: <= 128 registers (140 cost a workgroup per CU)
     __shared__ __attribute__((aligned(16))) unsigned short s_in[C1P::NPIX * 4];

@@ -122,7 +122,7 @@ struct mi_ctx {
     // network
     std::vector<ConvLayer> convs;
     Block blk[3];
-    Linear fc;            // impala fc 2048->256
+    Linear fc;            // impala fc 2048->H (output_dim)
     std::vector<Linear> mlp;
     std::vector<float*> mlp_act;   // X0 (input), h1..hL
     int64_t wh_off, bh_off;        // heads: (A+1) x H weights, (A+1) bias (device order)
@@ -142,7 +142,7 @@ struct mi_ctx {
     float* d_u; float* d_lp;
     unsigned short* banks; BankDesc* d_bank_desc; int n_banks;   // bf16 mode: pre-packed conv filter banks
     unsigned short* c1_bank;                                   // bf16 mode: block1.conv forward bank (conv1 kernels' LDS layout)
-    unsigned short *fc_wp, *fc_wt;            // bf16 mode: packed fc.weight images ([256][2048] and [2048][256])
+    unsigned short *fc_wp, *fc_wt;            // bf16 mode: packed fc.weight images ([H][2048] and [2048][H])
     bool fc_packed_valid;
     float *d_pack, *h_pack, *h_rd, *d_rd;     // packed rollout read-back {act,logp,value} x E ; packed {rew,done} upload
     unsigned *d_done_ctr, *h_flag, roll_ticket;   // rollout step: workgroup counter, host-visible completion ticket (heads_sample_kernel)
@@ -315,13 +315,16 @@ int mi_create(const mi_config* cfg, mi_ctx** out) {
     ARG(cfg->n_steps >= 1 && cfg->n_envs >= 1 && cfg->max_batch >= 1, "n_steps/n_envs/max_batch");
     ARG(cfg->precision == 0 || cfg->precision == 1, "precision must be 0 (fp32) or 1 (bf16 activations)");
     if (cfg->arch == MI_ARCH_MLP) ARG(cfg->obs_dim >= 1 && cfg->mlp_depth >= 2 && cfg->mlp_width >= 1 && cfg->out_dim >= 1, "mlp dims");
+    if (cfg->arch == MI_ARCH_IMPALA)          // out_dim 0: unset by a C caller, the reference's default 256
+        ARG(cfg->out_dim == 0 || (cfg->out_dim >= 64 && cfg->out_dim <= 512 && cfg->out_dim % 64 == 0),
+            "impala out_dim (output_dim) must be a multiple of 64 in [64, 512]");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(-3, "no HIP device: the MI355X library has no CPU fallback");
     HIPC(hipSetDevice(cfg->device));
     mi_ctx* c = new mi_ctx();
     c->cfg = *cfg;
     c->T = cfg->n_steps; c->E = cfg->n_envs; c->A = cfg->n_actions;
-    c->H = (cfg->arch == MI_ARCH_IMPALA) ? 256 : cfg->out_dim;
+    c->H = (cfg->arch == MI_ARCH_IMPALA && cfg->out_dim == 0) ? 256 : cfg->out_dim;
     c->NB = cfg->max_batch < cfg->n_envs ? cfg->n_envs : cfg->max_batch;
     c->bf = (cfg->arch == MI_ARCH_IMPALA) && cfg->precision == 1;
     c->es = c->bf ? 2.0 : 4.0;
@@ -432,7 +435,7 @@ int mi_create(const mi_config* cfg, mi_ctx** out) {
     for (int g = 0; g < mi_ctx::MAX_GROUPS; ++g) { c->gw[g] = nullptr; c->gs[g] = nullptr; c->ev_fork[g] = c->ev_join[g] = nullptr; c->g_forked[g] = c->g_busy[g] = c->g_last[g] = c->g_dirty[g] = false; c->g_ticket[g] = 0; }
     c->multirank = 0; c->pending_n = -1; c->sal_dc = nullptr; c->sal_dx = nullptr; c->sal_src = nullptr;
     c->fc_wp = c->fc_wt = nullptr; c->fc_packed_valid = false;
-    if (c->bf) { HIPC(dalloc(&c->fc_wp, (size_t)256 * 2048)); HIPC(dalloc(&c->fc_wt, (size_t)256 * 2048)); }
+    if (c->bf) { HIPC(dalloc(&c->fc_wp, (size_t)c->H * 2048)); HIPC(dalloc(&c->fc_wt, (size_t)c->H * 2048)); }
     c->banks = nullptr; c->d_bank_desc = nullptr; c->n_banks = 0; c->c1_bank = nullptr;
     if (c->bf && c->cfg.arch == MI_ARCH_IMPALA) HIPC(dalloc(&c->c1_bank, (size_t)conv1_bank_elems()));
     for (auto& L : c->convs) { L.bank_f = -1; L.bank_d = -1; }
@@ -814,7 +817,7 @@ static void net_gru(mi_ctx* c, int n, int soff = 0) {
 static void fc_refresh(mi_ctx* c) {
     if (c->bf && !c->fc_packed_valid) {
         launch_repack_all(c->params, c->banks, c->d_bank_desc, c->n_banks, c->convs.empty() ? nullptr : c->params + c->convs[0].w_off,
-                          c->convs.empty() ? nullptr : c->c1_bank, c->params + c->fc.w_off, c->fc_wp, c->fc_wt, CUR(c));
+                          c->convs.empty() ? nullptr : c->c1_bank, c->params + c->fc.w_off, c->fc_wp, c->fc_wt, c->H, CUR(c));
         c->fc_packed_valid = true;
     }
 }
@@ -885,10 +888,11 @@ static void net_forward(mi_ctx* c, const InputSrc& src, int n, bool recurrent = 
             prev = k.P2;
         }
         const float* last_p2 = prev;
-        if (c->bf) {                            // bf16 matrix cores on the packed [256][2048] weight image (fc_bf16.hip)
-            ProfScope ps(c, PC_GEMM, n, 2.0 * n * 2048 + 2.0 * 2048 * 256 + 4.0 * n * 256, 2.0 * n * 2048 * 256);
-            if (n >= 1024) launch_fc_fwd_bf16(last_p2, c->fc_wp, c->params + c->fc.b_off, feat, n, CUR(c));
-            else launch_fc_fwd_small_bf16(last_p2, c->fc_wp, c->params + c->fc.b_off, feat, n, CUR(c));   // rollout-sized: latency-bound
+        if (c->bf) {                            // bf16 matrix cores on the packed [H][2048] weight image (fc_bf16.hip)
+            const double H = c->H;
+            ProfScope ps(c, PC_GEMM, n, 2.0 * n * 2048 + 2.0 * 2048 * H + 4.0 * n * H, 2.0 * n * 2048 * H);
+            if (n >= 1024) launch_fc_fwd_bf16(last_p2, c->fc_wp, c->params + c->fc.b_off, feat, n, c->H, CUR(c));
+            else launch_fc_fwd_small_bf16(last_p2, c->fc_wp, c->params + c->fc.b_off, feat, n, c->H, CUR(c));   // rollout-sized: latency-bound
         } else
             linear_fwd(c, last_p2, 1, c->params + c->fc.w_off, c->params + c->fc.b_off, feat, n, 2048, c->H, 1, c->bf);
     } else {
@@ -956,17 +960,18 @@ static void net_backward(mi_ctx* c, const InputSrc& src, int n) {
         launch_heads_bwd_reduce(c->gemm_ws, c->grads + c->wh_off, c->grads + c->bh_off, n, c->H, c->A + 1, ss);      // (before fc_tn reuses the slabs)
         launch_fs_metric_seg(c->blk[2].P2, c->bf, j.st, 2048, c->fs_scratch, c->fs_parts, ss);
         launch_loss_finalize_seg(j.a, j.st, j.mode, j.ring, c->fs_parts, 2048, j.fsr, j.log, ss);
-        launch_fc_tn(c->dfeat, (const unsigned short*)c->blk[2].P2, c->grads + c->fc.w_off, c->gemm_ws, (size_t)8 << 20, 256, 2048, n, ss);
-        launch_colsum_acc(c->dfeat, n, 256, 256, c->grads + c->fc.b_off, c->col_ws, ss);
+        launch_fc_tn(c->dfeat, (const unsigned short*)c->blk[2].P2, c->grads + c->fc.w_off, c->gemm_ws, (size_t)8 << 20, c->H, 2048, n, ss);
+        launch_colsum_acc(c->dfeat, n, c->H, c->H, c->grads + c->fc.b_off, c->col_ws, ss);
         tl_stream = nullptr;
         hipEventRecord(c->ev_side_join, ss);
         c->side.armed = false;
         side_forked = true;
     } else if (fc16) {
         fc_refresh(c);
-        { ProfScope ps(c, PC_GEMM, n, 2.0 * n * 2048 + 4.0 * n * 256 + 4.0 * 2048 * 256, 2.0 * n * 2048 * 256);
-          launch_fc_tn(c->dfeat, (const unsigned short*)c->blk[2].P2, c->grads + c->fc.w_off, c->gemm_ws, (size_t)8 << 20, 256, 2048, n, CUR(c)); }
-        launch_colsum_acc(c->dfeat, n, 256, 256, c->grads + c->fc.b_off, c->col_ws, CUR(c));
+        { const double H = c->H;
+          ProfScope ps(c, PC_GEMM, n, 2.0 * n * 2048 + 4.0 * n * H + 4.0 * 2048 * H, 2.0 * n * 2048 * H);
+          launch_fc_tn(c->dfeat, (const unsigned short*)c->blk[2].P2, c->grads + c->fc.w_off, c->gemm_ws, (size_t)8 << 20, c->H, 2048, n, CUR(c)); }
+        launch_colsum_acc(c->dfeat, n, c->H, c->H, c->grads + c->fc.b_off, c->col_ws, CUR(c));
     } else
         linear_wgrad(c, c->dfeat, c->blk[2].P2, 1, c->grads + c->fc.w_off, c->grads + c->fc.b_off, n, 2048, c->H, c->bf);
     issue_grad_allreduce(c, c->fc.w_off, c->n_params - c->fc.w_off, false);       // region A: fc + heads gradients are final
@@ -974,8 +979,9 @@ static void net_backward(mi_ctx* c, const InputSrc& src, int n) {
     float* Ga = c->GP[1];
     float* Gb = c->GP[2];
     if (fc16) {
-        ProfScope ps(c, PC_GEMM, n, 4.0 * n * 256 + 2.0 * 2048 * 256 + 2.0 * 2.0 * n * 2048, 2.0 * n * 2048 * 256);
-        launch_fc_dgrad_bf16(c->dfeat, c->fc_wt, c->blk[2].P2, Gout, n, CUR(c));
+        const double H = c->H;
+        ProfScope ps(c, PC_GEMM, n, 4.0 * n * H + 2.0 * 2048 * H + 2.0 * 2.0 * n * 2048, 2.0 * n * 2048 * H);
+        launch_fc_dgrad_bf16(c->dfeat, c->fc_wt, c->blk[2].P2, Gout, n, c->H, CUR(c));
     } else
         linear_dgrad(c, c->dfeat, c->params + c->fc.w_off, c->blk[2].P2, Gout, n, 2048, c->H, c->bf);
     if (c->fs_grad_coef != 0.f) {    // + fs_coef * d(feature sparsity) / d(block3 output): one element per column (launch_fs_grad, misc.hip)

@@ -1,7 +1,8 @@
-// embedder.fc (2048 -> 256, common/model.py:176,199-200) on the bf16 matrix cores for the bf16 mode: forward,
+// embedder.fc (2048 -> D, common/model.py:176,199-200) on the bf16 matrix cores for the bf16 mode: forward,
 // data gradient and weight gradient.  The activations (block3 output, bf16 NHWC = the flattened 2048 features) are
-// read as stored; the fp32 gradient of the 256 features is rounded to bf16 while staged; fc.weight is kept as two
-// packed bf16 images ([256][2048] for forward, [2048][256] for dgrad) refreshed after every optimizer step.
+// read as stored; the fp32 gradient of the D features is rounded to bf16 while staged; fc.weight is kept as two
+// packed bf16 images ([D][2048] for forward, [2048][D] for dgrad) refreshed after every optimizer step.  D = output_dim,
+// a multiple of 64 in [64, 512] (mi_create); the dedicated kernels are templates on D, instantiated for every such width.
 //   NT kernel : C[M][N] = A[M][K] * Bp[N][K]^T         (forward: +bias, ReLU, fp32 out; dgrad: ReLU mask, bf16 out)
 //   TN kernel : gW[M][N] += A[K][M]^T * relu(B[K][N])   (weight gradient; both operands K(=batch)-major in memory ->
 //               ds_read_b64_tr_b16 fragments; split over the batch, slabs summed in fixed order)
@@ -151,7 +152,7 @@ static void launch_fc_nt_t(const FcNtArgs& g, hipStream_t st) {
     std::call_once(attr, [] { hipFuncSetAttribute((const void*)fc_nt_kernel<A_F32, TM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); });
     hipLaunchKernelGGL((fc_nt_kernel<A_F32, TM>), dim3((g.N + 63) / 64, (g.M + TM - 1) / TM), dim3(256), LDS, st, g);
 }
-void launch_fc_nt(const FcNtArgs& g, hipStream_t st) {          // K % 128 == 0 (2048 forward, 256 data gradient)
+void launch_fc_nt(const FcNtArgs& g, hipStream_t st) {          // K % 128 == 0 (2048 forward, D data gradient: D = 256 only in use)
     if (g.M <= 0) return;
     const int tn = (g.N + 63) / 64;
     const bool small_grid = (long long)tn * ((g.M + 127) / 128) < 512;         // fewer than 2 workgroups per CU with 128-row tiles
@@ -279,19 +280,20 @@ void launch_fc_tn(const float* A, const unsigned short* B, float* gW, float* ws,
 }
 
 // ------------------------------------------------------------------------------------------ forward, dedicated kernel
-// y[n][256] = relu(relu(x)[n][2048] x W^T + b).  K = 2048 is the long dimension: 16 steps of 128.  A workgroup owns 64 rows x 64 columns
+// y[n][D] = relu(relu(x)[n][2048] x W^T + b).  K = 2048 is the long dimension: 16 steps of 128.  A workgroup owns 64 rows x 64 columns
 // (wave w: rows 16w .. 16w+15); the x operand never touches LDS -- every lane loads its own MFMA fragments (16 bytes of one row) straight
 // from global memory one step ahead, into one of two register sets -- and the 64 x 128 slice of the packed weight goes through a
 // double-buffered LDS tile (one barrier per step).  512 workgroups at n = 8192: two or more per CU overlap each other's round trips
 // (the tiled NT kernel: one round trip per step and nothing to overlap it, 33 us).  n % 64 == 0; other sizes take the NT kernel.
 constexpr int FF_BK = 128, FF_LD = FF_BK + 16;
 constexpr size_t FF_LDS = (size_t)2 * 64 * FF_LD * 2;
+template <int D>
 __global__ __launch_bounds__(256) void fc_fwd_bf16_kernel(const unsigned short* __restrict__ x, const unsigned short* __restrict__ wp,
                                                           const float* __restrict__ bias, float* __restrict__ y, int nrb) {
     typedef unsigned ff_u32x4 __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) unsigned short ff_smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, kq = lane >> 4;
-    int cb, rbk; fc_block_map(4, nrb, cb, rbk);
+    int cb, rbk; fc_block_map(D / 64, nrb, cb, rbk);
     const int m0 = rbk * 64 + wave * 16, n0 = cb * 64;
     const unsigned short* xrow = x + (long long)(m0 + i) * 2048 + kq * 8;
     struct XF { ff_u32x4 f[4]; };                           // the lane's x fragments of one K step (4 MFMA k-steps of 32)
@@ -332,38 +334,53 @@ __global__ __launch_bounds__(256) void fc_fwd_bf16_kernel(const unsigned short* 
         const f32x4 bb = *(const f32x4*)(bias + n);
         f32x4 v = acc[b] + bb;
         v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-        *(f32x4*)(y + (long long)(m0 + i) * 256 + n) = v;
+        *(f32x4*)(y + (long long)(m0 + i) * D + n) = v;
     }
 }
-// embedder.fc: y[n][256] = relu(relu(x)[n][2048] * W^T + b)
-void launch_fc_fwd_bf16(const void* x_bf16, const unsigned short* wp, const float* bias, float* y, int n, hipStream_t st) {
-    if (n > 0 && n % 64 == 0 && bias) {
-        static std::once_flag attr;          // (launchers run on up to 4 group worker threads)
-        std::call_once(attr, [] { hipFuncSetAttribute((const void*)fc_fwd_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FF_LDS); });
-        hipLaunchKernelGGL(fc_fwd_bf16_kernel, dim3(4 * (n / 64)), dim3(256), FF_LDS, st, (const unsigned short*)x_bf16, wp, bias, y, n / 64);
-        return;
-    }
+template <int D>
+static void launch_fc_fwd_bf16_t(const void* x_bf16, const unsigned short* wp, const float* bias, float* y, int n, hipStream_t st) {
+    static std::once_flag attr;          // (launchers run on up to 4 group worker threads)
+    std::call_once(attr, [] { hipFuncSetAttribute((const void*)fc_fwd_bf16_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FF_LDS); });
+    hipLaunchKernelGGL(fc_fwd_bf16_kernel<D>, dim3(D / 64 * (n / 64)), dim3(256), FF_LDS, st, (const unsigned short*)x_bf16, wp, bias, y, n / 64);
+}
+template <int D> struct FcFwd { static void run(const void* x, const unsigned short* wp, const float* b, float* y, int n, hipStream_t st) { launch_fc_fwd_bf16_t<D>(x, wp, b, y, n, st); } };
+// embedder.fc: y[n][D] = relu(relu(x)[n][2048] * W^T + b)
+void launch_fc_fwd_bf16(const void* x_bf16, const unsigned short* wp, const float* bias, float* y, int n, int D, hipStream_t st) {
+    if (n > 0 && n % 64 == 0 && bias && fc_dispatch_width<FcFwd>(D, x_bf16, wp, bias, y, n, st)) return;
     FcNtArgs g{};
-    g.A = x_bf16; g.Bp = wp; g.C = y; g.M = n; g.N = 256; g.K = 2048; g.bias = bias; g.mask = nullptr;
+    g.A = x_bf16; g.Bp = wp; g.C = y; g.M = n; g.N = D; g.K = 2048; g.bias = bias; g.mask = nullptr;
     g.a_f32 = 0; g.relu_a = 1; g.relu_out = 1; g.c_bf16 = 0;
     launch_fc_nt(g, st);
 }
 // ------------------------------------------------------------------------------------------ data gradient, dedicated kernel
-// dx[n][2048] (bf16) = (dy[n][256] x W) * (x > 0), W as the packed image wt [2048][256].  K = 256 is short and N = 2048 long, so the
+// dx[n][2048] (bf16) = (dy[n][D] x W) * (x > 0), W as the packed image wt [2048][D].  K = D is short and N = 2048 long, so the
 // tile-per-workgroup NT kernel re-read the fp32 dy rows once per 64-column tile (32 x 8 MB through L2: it ran at L2 bandwidth,
 // 37.8 us per 8192 rows).  Here a workgroup (4 waves x 32 rows = 128 rows) keeps its dy rows in REGISTERS as MFMA fragments for the
 // whole K (2 row tiles x 8 K steps, rounded to bf16 once) and walks 256 columns in 4 steps of 64: per step the 64 x 256 slice of wt
 // goes through a double-buffered LDS tile (one barrier per step), the mask words of the NEXT step are already in flight, and the lane
 // layout (wt rows as the MFMA A operand) leaves 4 consecutive columns of one row per lane: 8-byte mask loads and stores.
-// n % 128 == 0 (the training minibatch sizes); other sizes take the NT kernel.
-constexpr int FD_LD = 256 + 16;                           // LDS row stride of the wt slice (bf16 elements)
-constexpr size_t FD_LDS = (size_t)2 * 64 * FD_LD * 2;
+// D = 256: n % 128 == 0 (the training minibatch sizes); other sizes take the NT kernel.  Other widths: any n (rows past n are clamped
+// on load and not stored; the NT kernel needs K % 128 == 0, which D = 64, 192, 320, 448 are not).  For D > 256 each 64-column step
+// walks K in NKC = 2 chunks of KC = D / 2 through the same double buffer (one barrier per chunk): the LDS slice stays at most
+// 64 x (256 + 16) elements = 68 KB, as at D = 256.  dy stays whole in registers (D / 8 VGPRs per row tile): 248 VGPRs at D = 384
+// (two workgroups per CU, as at D = 256: 232), 304 at D = 512 (one workgroup per CU, 4 waves).
+template <int D> struct FdShape {
+    static constexpr int NKC = D > 256 ? 2 : 1, KC = D / NKC;  // K chunks per column step; chunk length
+    static constexpr int LD = KC + 16;                       // LDS row stride of the wt slice (bf16 elements)
+    static constexpr size_t LDS = (size_t)2 * 64 * LD * 2;
+};
 constexpr int FD_STEPS = 4;                              // 64-column steps per workgroup: 2048 / (64 * 4) = 8 column ranges x n / 128 row blocks = 2 workgroups per CU at n = 8192
 #ifdef FC_TIMING
 __device__ unsigned long long g_fc_timing[8];
 #endif
+// nr: D = 256: the number of 128-row blocks (n % 128 == 0); other D: n, the number of rows.
+template <int D>
 __global__ __launch_bounds__(256) void fc_dgrad_bf16_kernel(const float* __restrict__ dy, const unsigned short* __restrict__ wt,
-                                                            const unsigned short* __restrict__ mask, unsigned short* __restrict__ dx, int nrb) {
+                                                            const unsigned short* __restrict__ mask, unsigned short* __restrict__ dx, int nr) {
+    constexpr bool GUARD = D != 256;
+    constexpr int KS = D / 32, NKC = FdShape<D>::NKC, KC = FdShape<D>::KC, FD_LD = FdShape<D>::LD, CHK = KC / 8, EB = 64 * CHK / 256;
+    const int nrb = GUARD ? (nr + 127) / 128 : nr;
+    auto rowc = [&](int r) { return GUARD ? (r < nr ? r : nr - 1) : r; };        // clamped load row
     extern __shared__ __attribute__((aligned(16))) unsigned short fd_smem[];
 #ifdef FC_TIMING
     long long tacc_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast_ = clock64();
@@ -375,66 +392,75 @@ __global__ __launch_bounds__(256) void fc_dgrad_bf16_kernel(const float* __restr
     int cb, rbk; fc_block_map(2048 / (64 * FD_STEPS), nrb, cb, rbk);
     const int m0 = rbk * 128 + wave * 32, n0 = cb * (64 * FD_STEPS);
     // dy fragments: row tile a (16 rows), K step ks: lane (i, kq) holds dy[m0 + 16a + i][32 ks + 8 kq .. +7]
-    bf16x8 av[2][8];
+    bf16x8 av[2][KS];
 #pragma unroll
-    for (int a = 0; a < 2; ++a) {                          // (one row tile at a time: 64 staging registers, not 128)
-        uint4 raw[8][2];
+    for (int a = 0; a < 2; ++a) {                          // (one row tile, 8 K steps at a time: 64 staging registers, not 128)
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-            const uint4* p = (const uint4*)(dy + (long long)(m0 + a * 16 + i) * 256 + ks * 32 + kq * 8);
-            raw[ks][0] = p[0]; raw[ks][1] = p[1];
-        }
+        for (int k8 = 0; k8 < KS; k8 += 8) {
+            uint4 raw[8][2];
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-            const uint4 lo = raw[ks][0], hi = raw[ks][1];
-            av[a][ks] = __builtin_bit_cast(bf16x8, (uint4){fc_pack2(__uint_as_float(lo.x), __uint_as_float(lo.y)), fc_pack2(__uint_as_float(lo.z), __uint_as_float(lo.w)),
-                                                           fc_pack2(__uint_as_float(hi.x), __uint_as_float(hi.y)), fc_pack2(__uint_as_float(hi.z), __uint_as_float(hi.w))});
+            for (int ks = 0; ks < 8; ++ks) {
+                if (k8 + ks >= KS) break;
+                const uint4* p = (const uint4*)(dy + (long long)rowc(m0 + a * 16 + i) * D + (k8 + ks) * 32 + kq * 8);
+                raw[ks][0] = p[0]; raw[ks][1] = p[1];
+            }
+#pragma unroll
+            for (int ks = 0; ks < 8; ++ks) {
+                if (k8 + ks >= KS) break;
+                const uint4 lo = raw[ks][0], hi = raw[ks][1];
+                av[a][k8 + ks] = __builtin_bit_cast(bf16x8, (uint4){fc_pack2(__uint_as_float(lo.x), __uint_as_float(lo.y)), fc_pack2(__uint_as_float(lo.z), __uint_as_float(lo.w)),
+                                                                    fc_pack2(__uint_as_float(hi.x), __uint_as_float(hi.y)), fc_pack2(__uint_as_float(hi.z), __uint_as_float(hi.w))});
+            }
         }
         asm volatile("" ::: "memory");
     }
     // (ext-vector type: a straight global -> register -> LDS copy of the HIP uint4 STRUCT compiles to memcpy through a private array,
     //  which lands in scratch memory)
     typedef unsigned fd_u32x4 __attribute__((ext_vector_type(4)));
-    fd_u32x4 rb[8];                                         // staging: 64 rows x 32 chunks of the next wt slice
-    auto fetch_b = [&](int st) {
+    fd_u32x4 rb[EB];                                        // staging: 64 rows x CHK chunks of the next wt slice
+    auto fetch_b = [&](int s) {                             // substep s: column step s / NKC, K chunk s % NKC
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { const int l = tid + e * 256; rb[e] = *(const fd_u32x4*)(wt + (long long)(n0 + st * 64 + (l >> 5)) * 256 + (l & 31) * 8); }
+        for (int e = 0; e < EB; ++e) { const int l = tid + e * 256; rb[e] = *(const fd_u32x4*)(wt + (long long)(n0 + s / NKC * 64 + l / CHK) * D + s % NKC * KC + l % CHK * 8); }
     };
     uint2 mk[2][4];                                         // mask words of the step in progress (fetched behind the previous step's epilogue)
     auto fetch_mask = [&](int st) {
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
-            for (int b = 0; b < 4; ++b) mk[a][b] = *(const uint2*)(mask + (long long)(m0 + a * 16 + i) * 2048 + n0 + st * 64 + b * 16 + kq * 4);
+            for (int b = 0; b < 4; ++b) mk[a][b] = *(const uint2*)(mask + (long long)rowc(m0 + a * 16 + i) * 2048 + n0 + st * 64 + b * 16 + kq * 4);
     };
     FDCK(0);                                                // dy fragments loaded and rounded
     fetch_b(0); fetch_mask(0);
+    f32x4 acc[2][4];
 #pragma unroll 2
-    for (int st = 0; st < FD_STEPS; ++st) {
-        unsigned short* Bs = fd_smem + (st & 1) * 64 * FD_LD;
+    for (int s = 0; s < FD_STEPS * NKC; ++s) {             // substep s: column step st, K chunk kc; LDS buffer s & 1
+        const int st = s / NKC, kc = s % NKC;
+        unsigned short* Bs = fd_smem + (s & 1) * 64 * FD_LD;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { const int l = tid + e * 256; *(fd_u32x4*)(Bs + (l >> 5) * FD_LD + (l & 31) * 8) = rb[e]; }
+        for (int e = 0; e < EB; ++e) { const int l = tid + e * 256; *(fd_u32x4*)(Bs + l / CHK * FD_LD + l % CHK * 8) = rb[e]; }
         FDCK(1);                                            // wait for the staged slice + LDS stores
         __syncthreads();
         FDCK(2);                                    // (also: every wave is done with the other buffer, written next step)
         const int nx = st + 1 < FD_STEPS ? st + 1 : st;            // unconditional (the last slice / mask is simply fetched again)
-        fetch_b(nx);
-        f32x4 acc[2][4];
+        fetch_b(s + 1 < FD_STEPS * NKC ? s + 1 : s);
+        if (kc == 0) {
 #pragma unroll
-        for (int a = 0; a < 2; ++a)
+            for (int a = 0; a < 2; ++a)
 #pragma unroll
-            for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
+        for (int ks = 0; ks < KC / 32; ++ks) {
             bf16x8 bv[4];
 #pragma unroll
             for (int b = 0; b < 4; ++b) bv[b] = *(const bf16x8*)(Bs + (b * 16 + i) * FD_LD + ks * 32 + kq * 8);
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
-                for (int b = 0; b < 4; ++b) acc[a][b] = MFMA_BF16(bv[b], av[a][ks], acc[a][b]);
+                for (int b = 0; b < 4; ++b) acc[a][b] = MFMA_BF16(bv[b], av[a][kc * (KC / 32) + ks], acc[a][b]);
         }
         FDCK(3);                                            // next slice requested + MFMAs
+        if (kc != NKC - 1) continue;                        // (the column step's last K chunk: epilogue)
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -444,6 +470,7 @@ __global__ __launch_bounds__(256) void fc_dgrad_bf16_kernel(const float* __restr
                 float v[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = ((h[r] & 0x8000u) || h[r] == 0) ? 0.f : acc[a][b][r];      // mask > 0 (bf16 bits: not negative, not zero)
+                if (GUARD && m0 + a * 16 + i >= nr) continue;
                 *(uint2*)(dx + (long long)(m0 + a * 16 + i) * 2048 + n0 + st * 64 + b * 16 + kq * 4) = (uint2){fc_pack2(v[0], v[1]), fc_pack2(v[2], v[3])};
             }
         fetch_mask(nx);
@@ -453,25 +480,31 @@ __global__ __launch_bounds__(256) void fc_dgrad_bf16_kernel(const float* __restr
     if (threadIdx.x == 0) for (int q = 0; q < 8; ++q) atomicAdd(&g_fc_timing[q], (unsigned long long)tacc_[q]);
 #endif
 }
-// dx[n][2048] (bf16) = (dy[n][256] * W) * (x > 0)
-void launch_fc_dgrad_bf16(const float* dy, const unsigned short* wt, const void* mask_bf16, void* dx_bf16, int n, hipStream_t st) {
-    if (n > 0 && n % 128 == 0 && mask_bf16) {
+template <int D> struct FcDgrad {
+    static void run(const float* dy, const unsigned short* wt, const void* mask_bf16, void* dx_bf16, int n, hipStream_t st) {
+        constexpr size_t LDS = FdShape<D>::LDS;
         static std::once_flag attr;          // (launchers run on up to 4 group worker threads)
-        std::call_once(attr, [] { hipFuncSetAttribute((const void*)fc_dgrad_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FD_LDS); });
-        hipLaunchKernelGGL(fc_dgrad_bf16_kernel, dim3(2048 / (64 * FD_STEPS) * (n / 128)), dim3(256), FD_LDS, st, dy, wt, (const unsigned short*)mask_bf16, (unsigned short*)dx_bf16, n / 128);
-        return;
+        std::call_once(attr, [] { hipFuncSetAttribute((const void*)fc_dgrad_bf16_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); });
+        const int nrb = (n + 127) / 128;
+        hipLaunchKernelGGL(fc_dgrad_bf16_kernel<D>, dim3(2048 / (64 * FD_STEPS) * nrb), dim3(256), LDS, st, dy, wt, (const unsigned short*)mask_bf16, (unsigned short*)dx_bf16,
+                           D == 256 ? nrb : n);
     }
+};
+// dx[n][2048] (bf16) = (dy[n][D] * W) * (x > 0)
+void launch_fc_dgrad_bf16(const float* dy, const unsigned short* wt, const void* mask_bf16, void* dx_bf16, int n, int D, hipStream_t st) {
+    if (n > 0 && mask_bf16 && (D != 256 || n % 128 == 0) && fc_dispatch_width<FcDgrad>(D, dy, wt, mask_bf16, dx_bf16, n, st)) return;
     FcNtArgs g{};
-    g.A = dy; g.Bp = wt; g.C = dx_bf16; g.M = n; g.N = 2048; g.K = 256; g.bias = nullptr; g.mask = (const unsigned short*)mask_bf16;
+    g.A = dy; g.Bp = wt; g.C = dx_bf16; g.M = n; g.N = 2048; g.K = D; g.bias = nullptr; g.mask = (const unsigned short*)mask_bf16;
     g.a_f32 = 1; g.relu_a = 0; g.relu_out = 0; g.c_bf16 = 1;
     launch_fc_nt(g, st);
 }
 
 // ------------------------------------------------------------------------------------------ small-batch forward (rollout)
-// n = E (256) rows: latency-bound, so the work is spread over (n/16) x (256/16) workgroups.  A workgroup owns a 16 x 16
+// n = E (256) rows: latency-bound, so the work is spread over (n/16) x (D/16) workgroups.  A workgroup owns a 16 x 16
 // output tile; its 4 waves split K = 2048 (16 MFMA steps each), every lane loads exactly its own operand fragments
 // straight from global memory / L2 (all 32 loads in flight before the first MFMA), the 4 partial tiles are summed through
 // LDS in fixed order, + bias, ReLU.
+template <int D>
 __global__ __launch_bounds__(256) void fc_small_bf16_kernel(const unsigned short* __restrict__ X, const unsigned short* __restrict__ Wp,
                                                             const float* __restrict__ bias, float* __restrict__ feat, int n) {
     __shared__ float red[4][256];
@@ -497,10 +530,14 @@ __global__ __launch_bounds__(256) void fc_small_bf16_kernel(const unsigned short
     const int row = tid >> 4, col = tid & 15;
     if (e0 + row < n) {
         const float v = ((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid])) + bias[o0 + col];
-        feat[(long long)(e0 + row) * 256 + o0 + col] = v > 0.f ? v : 0.f;
+        feat[(long long)(e0 + row) * D + o0 + col] = v > 0.f ? v : 0.f;
     }
 }
-void launch_fc_fwd_small_bf16(const void* X, const unsigned short* Wp, const float* bias, float* feat, int n, hipStream_t st) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(fc_small_bf16_kernel, dim3(16, (n + 15) / 16), dim3(256), 0, st, (const unsigned short*)X, Wp, bias, feat, n);
+template <int D> struct FcSmall {
+    static void run(const void* X, const unsigned short* Wp, const float* bias, float* feat, int n, hipStream_t st) {
+        hipLaunchKernelGGL(fc_small_bf16_kernel<D>, dim3(D / 16, (n + 15) / 16), dim3(256), 0, st, (const unsigned short*)X, Wp, bias, feat, n);
+    }
+};
+void launch_fc_fwd_small_bf16(const void* X, const unsigned short* Wp, const float* bias, float* feat, int n, int D, hipStream_t st) {
+    if (n > 0 && !fc_dispatch_width<FcSmall>(D, X, Wp, bias, feat, n, st)) mi_launch_fail("fc_small_bf16: no kernel for this output_dim");
 }

@@ -1182,6 +1182,9 @@ void launch_philox_debug(const uint32_t* in6, int n, uint32_t* out4, float* u_ou
 // product and then one ACTION of the normalisation: the exp / log terms are computed one per lane, every sum is still
 // taken in action order 0..A-1 (each lane re-adds the terms from LDS), so the numbers are those of the sequential
 // log_softmax_twice + CDF walk of sample_kernel.
+// WIDE (H > 256: IMPALA output_dim up to 512, any MLP latent_size): features and head rows are staged in K chunks of 256 through the
+// same LDS rows, each dot product carried across the chunks in the same order of operations as the single-chunk loop.
+template <bool WIDE>
 __global__ __launch_bounds__(256) void heads_sample_kernel(const float* __restrict__ feat, const float* __restrict__ Wh,
                                                            const float* __restrict__ bh, int n, int H, int A, const float* u,
                                                            unsigned long long seed, unsigned long long ctr, int32_t* act,
@@ -1195,6 +1198,43 @@ __global__ __launch_bounds__(256) void heads_sample_kernel(const float* __restri
     const int el = tid >> 4, o = tid & 15, e = e0 + el;
     float rwd = 0.f, dn = 0.f;
     if (rd && o == 0 && e < n) { rwd = rd[e]; dn = rd[n + e]; }          // (host-visible staging) issued first: latency hidden by the dots
+    if constexpr (WIDE) {
+        float acc0 = 0.f, acc1 = 0.f;                     // outputs o and (o == 0 only, A + 1 == 17) 16
+        for (int c0 = 0; c0 < H; c0 += 256) {
+            const int HC = H - c0 < 256 ? H - c0 : 256;
+            __syncthreads();                              // (every thread is done with the previous chunk)
+            if ((H & 3) == 0) {
+                const int H4 = HC >> 2;
+                for (int k = tid; k < 16 * H4; k += 256) {
+                    const int r = k / H4, kk = (k % H4) * 4;
+                    *(f32x4*)(s_f + r * 260 + kk) = (e0 + r < n) ? *(const f32x4*)(feat + (long long)(e0 + r) * H + c0 + kk) : (f32x4){0.f, 0.f, 0.f, 0.f};
+                }
+                for (int k = tid; k < (A + 1) * H4; k += 256) {
+                    const int r = k / H4, kk = (k % H4) * 4;
+                    *(f32x4*)(s_w + r * 260 + kk) = *(const f32x4*)(Wh + (long long)r * H + c0 + kk);
+                }
+            } else {
+                for (int k = tid; k < 16 * HC; k += 256) { const int r = k / HC, kk = k % HC; s_f[r * 260 + kk] = (e0 + r < n) ? feat[(long long)(e0 + r) * H + c0 + kk] : 0.f; }
+                for (int k = tid; k < (A + 1) * HC; k += 256) { const int r = k / HC, kk = k % HC; s_w[r * 260 + kk] = Wh[(long long)r * H + c0 + kk]; }
+            }
+            __syncthreads();
+            auto dot = [&](int oo, float acc) {
+                const float* w = s_w + oo * 260;
+                const float* f = s_f + el * 260;
+                int k = 0;
+                for (; k + 4 <= HC; k += 4) {
+                    const f32x4 fv = *(const f32x4*)(f + k), ww = *(const f32x4*)(w + k);
+                    acc += fv.x * ww.x + fv.y * ww.y + fv.z * ww.z + fv.w * ww.w;
+                }
+                for (; k < HC; ++k) acc += f[k] * w[k];
+                return acc;
+            };
+            if (o <= A) acc0 = dot(o, acc0);
+            if (o + 16 <= A) acc1 = dot(o + 16, acc1);
+        }
+        if (o <= A) s_z[el * 17 + o] = acc0 + bh[o];
+        if (o + 16 <= A) s_z[el * 17 + o + 16] = acc1 + bh[o + 16];
+    } else {
     if (H == 256) {
         // the IMPALA width: all 9 loads of a thread are issued before the first LDS store (the general loop below divides by a
         // run-time H and waits for every load before the next: 9 memory latencies in a row, half of this kernel's time)
@@ -1246,6 +1286,7 @@ __global__ __launch_bounds__(256) void heads_sample_kernel(const float* __restri
         }
         for (; k < H; ++k) acc += f[k] * w[k];
         s_z[el * 17 + oo] = acc + bh[oo];
+    }
     }
     __syncthreads();
     // The 16 lanes of an env sit in one wave (lane = 16*(el & 3) + o).  A lane publishes its term in the env's 64-byte LDS row and
@@ -1340,8 +1381,12 @@ void launch_heads_sample(const float* feat, const float* Wh, const float* bh, in
                          float* hout, const float* rd, float* rew_dst, float* done_dst, hipStream_t st,
                          unsigned* done_ctr, unsigned* host_flag, unsigned ticket) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(heads_sample_kernel, dim3((n + 15) / 16), dim3(256), 0, st, feat, Wh, bh, n, H, A, u, seed, ctr, act, logp, value, pack, hout,
-                       rd, rew_dst, done_dst, done_ctr, host_flag, ticket);
+    if (H > 256)
+        hipLaunchKernelGGL(heads_sample_kernel<true>, dim3((n + 15) / 16), dim3(256), 0, st, feat, Wh, bh, n, H, A, u, seed, ctr, act, logp, value, pack, hout,
+                           rd, rew_dst, done_dst, done_ctr, host_flag, ticket);
+    else
+        hipLaunchKernelGGL(heads_sample_kernel<false>, dim3((n + 15) / 16), dim3(256), 0, st, feat, Wh, bh, n, H, A, u, seed, ctr, act, logp, value, pack, hout,
+                           rd, rew_dst, done_dst, done_ctr, host_flag, ticket);
 }
 void launch_sample(const float* hout, int n, int A, const float* u, unsigned long long seed, unsigned long long ctr,
                    int32_t* act, float* logp, float* value, hipStream_t st) {

@@ -92,7 +92,7 @@ class Engine:
                       precision={"fp32": 0, "bf16": 1}[precision], stream=stream)
         self.precision = precision
         self.T, self.E, self.A, self.max_batch = n_steps, n_envs, n_actions, max(max_batch, n_envs)
-        self.H = 256 if self.arch == ARCH_IMPALA else out_dim
+        self.H = (out_dim or 256) if self.arch == ARCH_IMPALA else out_dim
         self.obs_dim = obs_dim
         self._ctx = C.c_void_p()
         self._chk(self.lib.mi_create(C.byref(cfg), C.byref(self._ctx)))

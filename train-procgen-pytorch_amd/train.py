@@ -196,9 +196,7 @@ def initialize_model(device, env, hp):
     obs_shape = env.observation_space.shape
     arch = hp.get('architecture', 'impala')
     if arch == 'impala':
-        if hp.get("output_dim", 256) != 256:
-            raise NotImplementedError("output_dim != 256: the IMPALA kernels are built for the reference's 2048 -> 256 embedder")
-        model = ImpalaModel(in_channels=obs_shape[0], output_dim=256)
+        model = ImpalaModel(in_channels=obs_shape[0], output_dim=hp.get("output_dim", 256))
     elif arch == 'mlpmodel':
         model = MLPModel(obs_shape[0], hp.get("depth", 4), hp.get("mid_weight", 64), hp.get("latent_size", 256))
     else:
