@@ -228,7 +228,12 @@ int mi_op_conv3x3(mi_ctx* ctx, int32_t mode /*0 fwd,1 dgrad,2 wgrad; a block's f
 /* bf16 precision only: the fused residual-block kernels.  mode 0 forward (x, w1, b1, w2, b2 -> out_a = conv1 output,
  * out_y = block output); mode 1 data gradients (x = dy, a_fwd, x_fwd, w1, w2 -> out_a = d conv1-output, out_y = d block-input);
  * mode 3: res1 + res2 forward in one launch with the same (w1, b1, w2, b2) for both blocks (out_a = second conv1 output);
- * mode 2 (16 channels @32x32, 32 channels @16x16) the whole backward in one launch: out_y = d block-input, out_a[0 .. 2*(9*ch*ch+ch)) = {dW1, db1, dW2, db2}.
+ * mode 2 (16 channels @32x32, 32 channels @16x16) the whole backward in one launch: out_y = d block-input, out_a[0 .. 2*(9*ch*ch+ch)) = {dW1, db1, dW2, db2};
+ * mode 4: res1 + res2 forward in one launch with four distinct convs, as the training forward runs them: w1 = [res1.conv1; res1.conv2],
+ * b1 = [res1.conv1.bias; res1.conv2.bias], w2 / b2 the same for res2; out_a = [A1; A2] (each block's conv1 output), out_y = [P1; P2]
+ * (each block's output), 2 x n x hw x hw x ch floats each.
+ * Every mode poisons its outputs before the launch (a skipped element reads back as NaN) and fails with -4 when a kernel writes
+ * past the end of an output tensor or into a weight-gradient slab row past its grid.  mi_op_conv3x3 and mi_op_maxpool do the same.
  * Replaces ResidualBlock.forward and its autograd (common/model.py:141-146). */
 int mi_op_resblock(mi_ctx* ctx, int32_t mode, int32_t ch, int32_t hw, int32_t n, const float* x, const float* w1, const float* b1,
                    const float* w2, const float* b2, const float* a_fwd, const float* x_fwd, float* out_a, float* out_y);

@@ -12,13 +12,10 @@ import torch
 import torch.nn.functional as F
 
 from conftest import load_npz, npz_json, npz_params
+from update_inputs import UPDATE_N, batches, check_per_image, check_wgrad, frames_to_nchw, hard_dy, hard_frames, hard_images, r16, wgrad64
 
 pytestmark = pytest.mark.gpu
 SHAPES = [(3, 16, 64), (16, 16, 32), (16, 32, 32), (32, 32, 16), (32, 32, 8)]
-
-
-def r16(t):
-    return t.bfloat16().float()
 
 
 def nhwc(t):
@@ -38,15 +35,26 @@ def eng():
 
 
 def _inputs(cin, cout, hw, n, seed):
+    """Update-sized n (>= 1024) get the hard images of update_inputs.py."""
     g = torch.Generator().manual_seed(seed)
     w = torch.randn(cout, cin, 3, 3, generator=g) * 0.2
     b = torch.randn(cout, generator=g)
     if cin == 3:
         x_u8 = torch.randint(0, 256, (n, hw, hw, 3), generator=g, dtype=torch.uint8).numpy()
+        if n >= 1024:
+            x_u8 = hard_frames(x_u8)
         # block1.conv in bf16 mode stages the frame as bf16(k/255) (uint8 -> bf16 table)
-        return w, b, x_u8, r16(torch.from_numpy((x_u8.transpose(0, 3, 1, 2) / 255.0).astype(np.float32)))
+        return w, b, x_u8, r16(frames_to_nchw(x_u8))
     x = r16(torch.randn(n, cin, hw, hw, generator=g))
+    if n >= 1024:
+        x = hard_images(x)
     return w, b, nhwc(x), x
+
+
+def _dy(shape, seed):
+    """An output gradient of bf16 values; at update-sized n one image's is zero."""
+    dy = r16(torch.randn(shape, generator=torch.Generator().manual_seed(seed)))
+    return hard_dy(dy) if shape[0] >= 1024 else dy
 
 
 @pytest.mark.parametrize("cin,cout,hw", SHAPES)
@@ -88,56 +96,65 @@ def test_conv_wgrad_bf16_inputs(eng, cin, cout, hw, n):
     assert relerr(gb, dout.sum(dim=(0, 2, 3)).numpy()) < 1e-4
 
 
-@pytest.mark.parametrize("n", [1, 5, 37])
+@pytest.mark.parametrize("n", [1, 5, 37] + UPDATE_N)
 def test_block1_conv_pool_fused_bf16(eng, n):
     """block1.conv + MaxPool2d(3,2,1) in one launch (the conv output lives in LDS only), and the weight gradient taken
     straight from the POOLED gradient + arg-max bytes (pool backward fused into the operand staging).  The unfused
-    kernels are the oracle for the forward (bit-identical: same conv arithmetic, same tie rule); torch autograd on the
-    bf16-rounded conv output for the gradient."""
+    kernels are the oracle for the forward (bit-identical: same conv arithmetic, same tie rule), torch per image as well;
+    torch autograd on the bf16-rounded conv output for the gradient, summed in float64."""
     w, b, x_u8, x = _inputs(3, 16, 64, n, 11)
     conv = eng.op_conv3x3(0, 3, 16, 64, w.numpy(), inp=x_u8, bias=b.numpy())              # unfused conv (bf16 values)
     pooled = eng.op_conv3x3(3, 3, 16, 64, w.numpy(), inp=x_u8, bias=b.numpy())
     assert np.array_equal(pooled, eng.op_maxpool(0, conv))
+    ref_p = F.max_pool2d(r16(F.conv2d(x, r16(w), b, padding=1)), kernel_size=3, stride=2, padding=1)
+    check_per_image(pooled, nhwc(ref_p), f"block1.conv+pool n={n} pooled map", 1e-2)
+    del ref_p
     c = torch.from_numpy(conv).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    del conv
     y = F.max_pool2d(c, kernel_size=3, stride=2, padding=1)
     assert np.array_equal(pooled, nhwc(y.detach()))
-    dy = r16(torch.randn(y.shape, generator=torch.Generator().manual_seed(12)))
+    dy = _dy(y.shape, 12)
     y.backward(dy)
     dc = c.grad            # one-hot form (conv1_wgrad_onehot_bf16_kernel): the pooled gradients multiply the frame pixels directly, the <= 4
-    ref_w = torch.nn.grad.conv2d_weight(x, w.shape, dc, padding=1)      # contributions of a conv pixel are never summed into a bf16 first
+    ref_w, ref_b = wgrad64(x, dc)                                       # contributions of a conv pixel are never summed into a bf16 first
     gw, gb = eng.op_conv3x3(4, 3, 16, 64, w.numpy(), inp=x_u8, bias=b.numpy(), dout=nhwc(dy))
-    assert relerr(gw, ref_w.numpy()) < 2e-5
-    assert relerr(gb, dc.sum(dim=(0, 2, 3)).numpy()) < 2e-5
+    check_wgrad(gw, gb, ref_w, ref_b, f"block1.conv n={n} from the pooled gradient", 2e-5)
 
 
 @pytest.mark.parametrize("cin,cout,hw", [(16, 32, 32), (32, 32, 16)])
-@pytest.mark.parametrize("n", [1, 5, 12])
+@pytest.mark.parametrize("n", [1, 5, 12] + UPDATE_N)
 def test_block_conv_pool_fused_bf16(eng, cin, cout, hw, n):
     """block2.conv / block3.conv + MaxPool2d(3,2,1) in one launch, and both gradients of the conv taken from the POOLED
     gradient + arg-max bytes (max-pool backward fused into the operand staging of the weight- and data-gradient
-    kernels).  Forward oracle: the unfused kernels (bit-identical: same conv arithmetic, same tie rule).  Backward
-    oracle: torch autograd through max_pool2d on the kernel's own bf16 conv output."""
+    kernels).  Forward oracle: the unfused kernels (bit-identical: same conv arithmetic, same tie rule), torch per image
+    as well.  Backward oracle: torch autograd through max_pool2d on the kernel's own bf16 conv output; weight gradients
+    summed in float64.  n >= 1024: the rolling-rows forward (conv_pool_fwd_roll) and several items per workgroup."""
     w, b, x_dev, x = _inputs(cin, cout, hw, n, 21)
     conv = eng.op_conv3x3(0, cin, cout, hw, w.numpy(), inp=x_dev, bias=b.numpy())
     pooled = eng.op_conv3x3(3, cin, cout, hw, w.numpy(), inp=x_dev, bias=b.numpy())
     assert np.array_equal(pooled, eng.op_maxpool(0, conv))
+    ref_p = F.max_pool2d(r16(F.conv2d(x, r16(w), b, padding=1)), kernel_size=3, stride=2, padding=1)
+    check_per_image(pooled, nhwc(ref_p), f"conv+pool ({cin},{cout},{hw}) n={n} pooled map", 1e-2)
+    del ref_p
     c = torch.from_numpy(conv).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    del conv
     y = F.max_pool2d(c, kernel_size=3, stride=2, padding=1)
     assert np.array_equal(pooled, nhwc(y.detach()))
-    dy = r16(torch.randn(y.shape, generator=torch.Generator().manual_seed(22)))
+    dy = _dy(y.shape, 22)
     y.backward(dy)
     dc = r16(c.grad)                                                    # the staging rounds the gathered sum to bf16
-    ref_w = torch.nn.grad.conv2d_weight(x, w.shape, dc, padding=1)
+    del c, y
+    ref_w, ref_b = wgrad64(x, dc)
     gw, gb = eng.op_conv3x3(4, cin, cout, hw, w.numpy(), inp=x_dev, bias=b.numpy(), dout=nhwc(dy))
-    assert relerr(gw, ref_w.numpy()) < 1e-4
-    assert relerr(gb, dc.sum(dim=(0, 2, 3)).numpy()) < 1e-4
+    check_wgrad(gw, gb, ref_w, ref_b, f"conv ({cin},{cout},{hw}) n={n} from the pooled gradient", 1e-4)
     ref_x = torch.nn.grad.conv2d_input(x.shape, r16(w), dc, padding=1)
     gx = eng.op_conv3x3(5, cin, cout, hw, w.numpy(), inp=x_dev, bias=b.numpy(), dout=nhwc(dy))
     assert relerr(gx, nhwc(ref_x)) < 1e-2
+    check_per_image(gx, nhwc(ref_x), f"conv ({cin},{cout},{hw}) n={n} data gradient from the pooled gradient", 1e-2)
     # block2.conv and block3.conv: both gradients from ONE launch (one max-pool backward gather; block2_conv_bwd_bf16_kernel,
     # block3_conv_bwd_bf16_kernel); the data gradient is bit-identical to the generic kernel's
     gw2, gb2 = eng.op_conv3x3(6, cin, cout, hw, w.numpy(), inp=x_dev, bias=b.numpy(), dout=nhwc(dy))
-    assert relerr(gw2, ref_w.numpy()) < 1e-4 and relerr(gb2, dc.sum(dim=(0, 2, 3)).numpy()) < 1e-4
+    check_wgrad(gw2, gb2, ref_w, ref_b, f"conv ({cin},{cout},{hw}) n={n} fused data + weight gradient launch", 1e-4)
     assert np.array_equal(eng.op_conv3x3(7, cin, cout, hw, w.numpy(), inp=x_dev, bias=b.numpy(), dout=nhwc(dy)), gx)
 
 
@@ -207,30 +224,110 @@ def test_residual_pair_role_pipelined_kernel_equals_the_lds_bank_kernel(eng):
     assert np.array_equal(pa, np.concatenate([h[0] for h in halves])) and np.array_equal(py, np.concatenate([h[1] for h in halves]))
 
 
-@pytest.mark.parametrize("ch,hw", [(16, 32), (32, 16), (32, 8)])
-@pytest.mark.parametrize("n", [1, 7])
-def test_residual_block_whole_backward_bf16(eng, ch, hw, n):
-    """Residual block (16 channels @32x32, 32 channels @16x16): data gradients and both weight / bias gradients in ONE
-    launch (the gradient of conv1's output only exists in LDS).  torch reference with the kernel's rounding points:
-    filters bf16 for the data path, d(conv1 output) rounded to bf16 before conv1's transposed conv and weight gradient
-    consume it."""
+def _whole_backward_inputs(ch, hw, n):
     g = torch.Generator().manual_seed(77)
     w1, w2 = torch.randn(ch, ch, 3, 3, generator=g) * 0.15, torch.randn(ch, ch, 3, 3, generator=g) * 0.15
     x = r16(torch.randn(n, ch, hw, hw, generator=g))
+    if n >= 1024:
+        x = hard_images(x)
     a = r16(F.conv2d(F.relu(x), r16(w1), torch.randn(ch, generator=g), padding=1))
     dy = r16(torch.randn(n, ch, hw, hw, generator=g))
+    if n >= 1024:
+        dy = hard_dy(dy)
+    return w1, w2, x, a, dy
+
+
+@pytest.mark.parametrize("ch,hw", [(16, 32), (32, 16), (32, 8)])
+@pytest.mark.parametrize("n", [1, 6] + UPDATE_N)
+def test_residual_pair_with_distinct_weights(eng, ch, hw, n):
+    """The pair launch as net_forward runs it in training mode (op_resblock mode 4): four distinct convs and biases, all four outputs
+    A1, P1, A2, P2 stored.  Per image against torch at the kernel's rounding points (filters, A1, P1 and A2 in bf16).  n <= 6: bit for
+    bit two single-block launches (mode 0).  n >= 1024 (pair32r at 32@16; at 32@8 RB_32_8S with 4 images per workgroup at n = 1024,
+    the 4-image RB_32_8P above): every image equal, bit for bit, to the same images in launches of <= 12 -- a kernel that fed res2
+    from res1's filter banks, or counted a phantom slot, fails both."""
+    g = torch.Generator().manual_seed(500 + ch + hw)
+    W = [torch.randn(ch, ch, 3, 3, generator=g) * 0.1 for _ in range(4)]
+    Bs = [torch.randn(ch, generator=g) * 0.5 for _ in range(4)]
+    x = r16(torch.randn(n, ch, hw, hw, generator=g))
+    if n >= 1024:
+        x = hard_images(x)
+    w1, w2 = torch.stack(W[:2]).numpy(), torch.stack(W[2:]).numpy()
+    b1, b2 = torch.cat(Bs[:2]).numpy(), torch.cat(Bs[2:]).numpy()
+    xh = nhwc(x)
+    oa, oy = eng.op_resblock(4, xh, w1, w2, b1=b1, b2=b2)
+    a1 = r16(F.conv2d(F.relu(x), r16(W[0]), Bs[0], padding=1))
+    p1 = r16(F.conv2d(F.relu(a1), r16(W[1]), Bs[1], padding=1) + x)
+    a2 = r16(F.conv2d(F.relu(p1), r16(W[2]), Bs[2], padding=1))
+    p2 = F.conv2d(F.relu(a2), r16(W[3]), Bs[3], padding=1) + p1
+    for name, out, ref in (("A1", oa[0], a1), ("P1", oy[0], p1), ("A2", oa[1], a2), ("P2", oy[1], p2)):
+        check_per_image(out, nhwc(ref), f"residual pair {ch}@{hw} n={n} {name}", 1e-2)
+    del a1, p1, a2, p2
+    if n < 1024:
+        ra1, ry1 = eng.op_resblock(0, xh, W[0].numpy(), W[1].numpy(), b1=Bs[0].numpy(), b2=Bs[1].numpy())
+        ra2, ry2 = eng.op_resblock(0, ry1, W[2].numpy(), W[3].numpy(), b1=Bs[2].numpy(), b2=Bs[3].numpy())
+        for out, ref in ((oa[0], ra1), (oy[0], ry1), (oa[1], ra2), (oy[1], ry2)):
+            assert np.array_equal(out, ref)
+        return
+    for k0, k1 in batches(n):
+        sa, sy = eng.op_resblock(4, xh[k0:k1], w1, w2, b1=b1, b2=b2)
+        assert np.array_equal(sa, oa[:, k0:k1]) and np.array_equal(sy, oy[:, k0:k1]), (k0, k1)
+
+
+def _batch_invariance_case(eng, op, shape, n):
+    """(launch(lo, hi) -> the outputs of images lo .. hi, as a list of arrays with the image axis first)"""
+    if op == "whole_bwd":
+        ch, hw = shape
+        w1, w2, x, a, dy = _whole_backward_inputs(ch, hw, n)
+        dy, a, x = nhwc(dy), nhwc(a), nhwc(x)
+        return lambda lo, hi: [eng.op_resblock(2, dy[lo:hi], w1.numpy(), w2.numpy(), a_fwd=a[lo:hi], x_fwd=x[lo:hi])[1]]
+    cin, cout, hw = shape
+    w, b, x_dev, _ = _inputs(cin, cout, hw, n, 41)
+    if op == "conv_pool":
+        return lambda lo, hi: [eng.op_conv3x3(3, cin, cout, hw, w.numpy(), inp=x_dev[lo:hi], bias=b.numpy())]
+    dy = nhwc(_dy((n, cout, hw // 2, hw // 2), 42))
+    return lambda lo, hi: [eng.op_conv3x3(m, cin, cout, hw, w.numpy(), inp=x_dev[lo:hi], bias=b.numpy(), dout=dy[lo:hi]) for m in (5, 7)]
+
+
+@pytest.mark.parametrize("op,shape", [("conv_pool", (3, 16, 64)), ("conv_pool", (16, 32, 32)), ("conv_pool", (32, 32, 16)),
+                                      ("pool_dgrad", (16, 32, 32)), ("pool_dgrad", (32, 32, 16)),
+                                      ("whole_bwd", (16, 32)), ("whole_bwd", (32, 16)), ("whole_bwd", (32, 8))])
+@pytest.mark.parametrize("n", UPDATE_N)
+def test_update_sized_launch_equals_launches_of_12(eng, op, shape, n):
+    """Batch invariance of the update phase's persistent kernels: every image of the activation and data-gradient outputs of one
+    n-image launch equals, bit for bit, the same image launched in batches of <= 12 (where every workgroup runs one item and the
+    torch pins above hold).  conv_pool: the fused conv + max pool forward (rolling rows at n >= 1024); pool_dgrad: the data gradient
+    from the pooled gradient, alone (mode 5) and from the fused data + weight gradient launch (mode 7); whole_bwd: the residual
+    block's whole backward (full16d, full32s, full32q).  Weight gradients are exempt: their summation order follows the grid."""
+    launch = _batch_invariance_case(eng, op, shape, n)
+    whole = launch(0, n)
+    for t in whole:
+        assert np.isfinite(t).all() and np.abs(t).max() > 0
+    for lo, hi in batches(n):
+        for k, t in enumerate(launch(lo, hi)):
+            assert np.array_equal(t, whole[k][lo:hi]), (op, shape, n, lo, hi, k)
+
+
+@pytest.mark.parametrize("ch,hw", [(16, 32), (32, 16), (32, 8)])
+@pytest.mark.parametrize("n", [1, 7] + UPDATE_N)
+def test_residual_block_whole_backward_bf16(eng, ch, hw, n):
+    """Residual block (16 channels @32x32, 32 channels @16x16 and @8x8): data gradients and both weight / bias gradients in ONE
+    launch (the gradient of conv1's output only exists in LDS).  torch reference with the kernel's rounding points:
+    filters bf16 for the data path, d(conv1 output) rounded to bf16 before conv1's transposed conv and weight gradient
+    consume it; weight gradients summed in float64.  n >= 1024: full16d runs 16 half-image items per workgroup at n = 2051,
+    full32s 8 images, full32q 2 four-image items, the last with one phantom slot."""
+    w1, w2, x, a, dy = _whole_backward_inputs(ch, hw, n)
     da = r16(torch.nn.grad.conv2d_input(a.shape, r16(w2), dy, padding=1) * (a > 0))
     dx = torch.nn.grad.conv2d_input(x.shape, r16(w1), da, padding=1) * (x > 0) + dy
-    dw2 = torch.nn.grad.conv2d_weight(F.relu(a), w2.shape, dy, padding=1)
-    dw1 = torch.nn.grad.conv2d_weight(F.relu(x), w1.shape, da, padding=1)
+    dw2, db2 = wgrad64(F.relu(a), dy)
+    dw1, db1 = wgrad64(F.relu(x), da)
     flat, gx = eng.op_resblock(2, nhwc(dy), w1.numpy(), w2.numpy(), a_fwd=nhwc(a), x_fwd=nhwc(x))
     flat = flat.ravel()
     wl = ch * ch * 9
     assert relerr(gx, nhwc(dx)) < 1e-2
-    assert relerr(flat[:wl].reshape(ch, ch, 3, 3), dw1.numpy()) < 1e-4
-    assert relerr(flat[wl:wl + ch], da.sum(dim=(0, 2, 3)).numpy()) < 1e-4
-    assert relerr(flat[wl + ch:2 * wl + ch].reshape(ch, ch, 3, 3), dw2.numpy()) < 1e-4
-    assert relerr(flat[2 * wl + ch:2 * wl + 2 * ch], dy.sum(dim=(0, 2, 3)).numpy()) < 1e-4
+    check_per_image(gx, nhwc(dx), f"residual block {ch}@{hw} n={n} whole backward: data gradient", 1e-2)
+    check_wgrad(flat[:wl].reshape(ch, ch, 3, 3), flat[wl:wl + ch], dw1, db1, f"residual block {ch}@{hw} n={n} whole backward: conv1", 1e-4)
+    check_wgrad(flat[wl + ch:2 * wl + ch].reshape(ch, ch, 3, 3), flat[2 * wl + ch:2 * wl + 2 * ch], dw2, db2,
+                f"residual block {ch}@{hw} n={n} whole backward: conv2", 1e-4)
 
 
 @pytest.mark.parametrize("hw,c", [(64, 16), (32, 32), (16, 32)])

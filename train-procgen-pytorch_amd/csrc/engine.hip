@@ -1829,9 +1829,74 @@ static std::vector<uint16_t> host_to_bf16(const float* x, size_t n) {
 static void host_from_bf16(const uint16_t* h, float* x, size_t n) {
     for (size_t k = 0; k < n; ++k) { const uint32_t u = ((uint32_t)h[k]) << 16; memcpy(x + k, &u, 4); }
 }
+// Device memory of one op-level call.  Every buffer is freed on every return path.  Outputs the kernels write are poisoned with
+// 0xFF bytes (NaN in bf16 and fp32), so an element a kernel skips reads back as NaN; the targets the slab reduction adds into keep
+// a zero fill.  A canary band follows each output (and covers the weight-gradient slab rows past a launch's grid); check() compares
+// the bands after the launch and names the tensor a kernel wrote past.  The bands sit after the tensors only: bases keep hipMalloc's
+// alignment.  The production launch path never goes through here.
+struct OpMem {
+    static constexpr size_t GUARD = 64 * 1024;
+    static constexpr int CANARY = 0xA5;
+    struct Band { std::string name; unsigned char* p; size_t bytes; bool rezero; };
+    const char* hook; hipStream_t st;
+    std::vector<void*> owned;
+    std::vector<Band> bands;
+    OpMem(const char* h, hipStream_t s) : hook(h), st(s) {}
+    ~OpMem() { for (void* p : owned) hipFree(p); }
+    OpMem(const OpMem&) = delete;
+    OpMem& operator=(const OpMem&) = delete;
+    template <typename T>
+    hipError_t alloc(T** p, size_t bytes) {          // an input: the +256 bytes cover the kernels' vector over-reads
+        void* q = nullptr;
+        hipError_t e = hipMalloc(&q, bytes + 256);
+        if (e != hipSuccess) return e;
+        owned.push_back(q); *p = (T*)q;
+        return hipMemsetAsync(q, 0, bytes + 256, st);
+    }
+    template <typename T>
+    hipError_t out(T** p, size_t bytes, const char* name, int fill = 0xFF) {
+        void* q = nullptr;
+        hipError_t e = hipMalloc(&q, bytes + GUARD);
+        if (e != hipSuccess) return e;
+        owned.push_back(q); *p = (T*)q;
+        if ((e = hipMemsetAsync(q, fill, bytes, st)) != hipSuccess) return e;
+        return band((unsigned char*)q + bytes, GUARD, name, false);
+    }
+    // the rows [grid, 1024) of a weight-gradient slab region; zero-filled again after the check
+    hipError_t slab_rows(float* slabs, int grid, int row_len, const char* name) {
+        const size_t lo = (size_t)grid * row_len, hi = (size_t)1024 * row_len;
+        return grid < 1024 ? band((unsigned char*)(slabs + lo), (hi - lo) * 4, name, true) : hipSuccess;
+    }
+    hipError_t band(unsigned char* p, size_t bytes, const std::string& name, bool rezero) {
+        bands.push_back(Band{name, p, bytes, rezero});
+        return hipMemsetAsync(p, CANARY, bytes, st);
+    }
+    int check() {           // after the stream synchronisation
+        std::vector<unsigned char> h;
+        std::string bad;
+        for (const Band& b : bands) {
+            h.resize(b.bytes);
+            HIPC(hipMemcpy(h.data(), b.p, b.bytes, hipMemcpyDeviceToHost));
+            static const std::vector<unsigned char> want(1 << 20, (unsigned char)CANARY);
+            for (size_t o = 0; o < b.bytes && bad.empty(); o += want.size()) {
+                const size_t k = std::min(want.size(), b.bytes - o);
+                if (memcmp(h.data() + o, want.data(), k) == 0) continue;
+                size_t i = o;
+                while (h[i] == (unsigned char)CANARY) ++i;
+                bad = std::string(hook) + ": a kernel wrote past the end of " + b.name + " (guard byte " + std::to_string(i) + ")";
+            }
+            if (b.rezero) HIPC(hipMemsetAsync(b.p, 0, b.bytes, st));
+        }
+        bands.clear();
+        HIPC(hipStreamSynchronize(st));
+        return bad.empty() ? 0 : fail(-4, bad);
+    }
+};
+
 // upload an activation tensor in the context's storage type
-static int upload_act(mi_ctx* c, const float* host, size_t n, void** dev) {
-    HIPC(hipMalloc(dev, n * 4 + 256));
+static int upload_act(mi_ctx* c, OpMem& m, const float* host, size_t n, void** dev) {
+    HIPC(m.alloc(dev, n * 4));
+    HIPC(hipStreamSynchronize(c->stream));          // (the fill runs on the context's stream, the copy on the null stream)
     if (c->bf) { auto h = host_to_bf16(host, n); HIPC(hipMemcpy(*dev, h.data(), n * 2, hipMemcpyHostToDevice)); }
     else HIPC(hipMemcpy(*dev, host, n * 4, hipMemcpyHostToDevice));
     return 0;
@@ -1839,6 +1904,12 @@ static int upload_act(mi_ctx* c, const float* host, size_t n, void** dev) {
 static int download_act(mi_ctx* c, const void* dev, float* host, size_t n) {
     if (c->bf) { std::vector<uint16_t> h(n); HIPC(hipMemcpy(h.data(), dev, n * 2, hipMemcpyDeviceToHost)); host_from_bf16(h.data(), host, n); }
     else HIPC(hipMemcpy(host, dev, n * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+static int upload(OpMem& m, const void* host, size_t bytes, void** dev) {
+    HIPC(m.alloc(dev, bytes));
+    HIPC(hipStreamSynchronize(m.st));
+    HIPC(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -1849,87 +1920,95 @@ int mi_op_conv3x3(mi_ctx* c, int32_t mode, int32_t cin, int32_t cout, int32_t hw
     ConvShape s;
     if (shape_of(cin, cout, hw, &s)) return -1;
     ARG((s == CS_3_16_64) == (in_is_u8 != 0) || mode == 1, "block1.conv takes uint8 frames");
-    const size_t px = (size_t)n * hw * hw;
+    const std::string hook = "mi_op_conv3x3 mode " + std::to_string(mode);
+    OpMem m(hook.c_str(), c->stream);
+    const size_t px = (size_t)n * hw * hw, es = c->bf ? 2 : 4;
     TensorDesc td{"w", 0, 0, (int64_t)cout * cin * 9, K_CONVW, cout, cin};
     std::vector<float> wdev(td.n);
     to_device_layout(td, w_ref, wdev.data());
     float *dw = nullptr, *db = nullptr;
     void *din = nullptr, *dres = nullptr, *dmask = nullptr, *ddout = nullptr, *dout_buf = nullptr;
-    HIPC(dalloc(&dw, td.n)); HIPC(hipMemcpy(dw, wdev.data(), td.n * 4, hipMemcpyHostToDevice));
-    if (bias) { HIPC(dalloc(&db, cout)); HIPC(hipMemcpy(db, bias, cout * 4, hipMemcpyHostToDevice)); }
+    if (int r = upload(m, wdev.data(), td.n * 4, (void**)&dw)) return r;
+    if (bias) { if (int r = upload(m, bias, cout * 4, (void**)&db)) return r; }
     const int out_ch = (mode == 1) ? cin : cout;
     if (mode != 1) {
-        if (in_is_u8) { HIPC(hipMalloc(&din, px * 3 + 256)); HIPC(hipMemcpy(din, in, px * 3, hipMemcpyHostToDevice)); }
-        else if (int r = upload_act(c, (const float*)in, px * cin, &din)) return r;
+        if (in_is_u8) { if (int r = upload(m, in, px * 3, &din)) return r; }
+        else if (int r = upload_act(c, m, (const float*)in, px * cin, &din)) return r;
     }
+    // the weight gradient: slabs [grid][td.n + cout] summed into g (the reduction adds: zero fill)
+    auto wgrad_out = [&](float** g, int grid) -> int {
+        HIPC(m.out(g, (td.n + cout) * 4, "the weight / bias gradient", 0));
+        HIPC(m.slab_rows(c->slabs, grid, (int)td.n + cout, "the weight-gradient slab rows past the grid"));
+        return 0;
+    };
+    auto read_wgrad = [&](const float* g) -> int {
+        std::vector<float> hg(td.n + cout);
+        HIPC(hipMemcpy(hg.data(), g, hg.size() * 4, hipMemcpyDeviceToHost));
+        to_ref_layout(td, hg.data(), out);
+        if (dbias_out) memcpy(dbias_out, hg.data() + td.n, cout * 4);
+        return 0;
+    };
     if (mode >= 3) {        // a block's first conv fused with the block's max pool (bf16): 3 = forward -> pooled map,
                             // 4 = weight gradient, 5 = data gradient -- both from the POOLED gradient + the forward's arg-max bytes
         ARG(c->bf && (s == CS_3_16_64 || s == CS_16_32_32 || s == CS_32_32_16), "fused conv+pool modes: block1/2/3.conv in bf16 precision only");
         ARG(mode <= 7 && !(mode >= 5 && s == CS_3_16_64) && in, "mode");
+        ARG(mode == 3 || mode == 5 || c->slabs, "modes 4 / 6: weight gradients need an IMPALA context");
+        ARG(mode < 6 || conv_bwd_fused_grid(s, n) > 0, "modes 6 / 7: block2.conv / block3.conv");
+        ARG(mode == 3 || dout, "dout");
         const size_t pp = (size_t)n * (hw / 2) * (hw / 2) * cout;
         void *dp = nullptr, *dgi = nullptr; uint8_t* di = nullptr; unsigned short* dbank = nullptr; BankDesc* ddesc = nullptr;
-        HIPC(hipMalloc(&dp, pp * 2 + 256)); HIPC(dalloc(&di, pp));
+        HIPC(m.out(&dp, pp * 2, "the pooled map")); HIPC(m.out(&di, pp, "the arg-max bytes", 0));
         ConvArgs a{};
         a.in = din; a.w = dw; a.bias = db; a.n = n; a.bf16 = 1; a.lut16 = c->lut16;
         if (s == CS_3_16_64) launch_conv1_pool_fwd_bf16(a, c->lut16, dp, di, c->stream);
         else {
             const long long bf_len = (long long)cout * bank_ws(cin), bd_len = (long long)cin * bank_ws(cout);
             BankDesc d[2] = {{0, 0, cout, cin, cout, cin, 0, bank_ws(cin), cin == 32 ? 9 : 5}, {0, bf_len, cin, cout, cout, cin, 1, bank_ws(cout), cout == 32 ? 9 : 5}};
-            HIPC(dalloc(&dbank, (size_t)(bf_len + bd_len))); HIPC(hipMalloc((void**)&ddesc, sizeof d)); HIPC(hipMemcpy(ddesc, d, sizeof d, hipMemcpyHostToDevice));
+            HIPC(m.alloc(&dbank, (size_t)(bf_len + bd_len) * 2));
+            if (int r = upload(m, d, sizeof d, (void**)&ddesc)) return r;
             launch_pack_banks(dw, dbank, ddesc, 2, c->stream);
             a.wbank = dbank;
             ARG(launch_conv_pool_fwd_bf16(s, a, dp, di, c->stream), "no fused kernel");
         }
         HIPC(hipGetLastError()); NETCHK(c);
         HIPC(hipStreamSynchronize(c->stream));
-        if (mode == 3) { if (int r = download_act(c, dp, out, pp)) return r; }
-        else if (mode == 4) {
-            ARG(dout && c->slabs, "dout");
-            if (int r = upload_act(c, dout, pp, &ddout)) return r;
+        if (mode == 3) {
+            if (int r = m.check()) return r;
+            return download_act(c, dp, out, pp);
+        }
+        if (int r = upload_act(c, m, dout, pp, &ddout)) return r;
+        if (mode == 4) {
             float* g = nullptr;
-            HIPC(dalloc(&g, td.n + cout));
+            const int grid = wgrad_grid_for(s, n, 1);
+            if (int r = wgrad_out(&g, grid)) return r;
             WgradArgs wa{};
             wa.in = din; wa.dout = ddout; wa.partial = c->slabs; wa.n = n; wa.bf16 = 1; wa.lut16 = c->lut16; wa.pool_arg = di;
-            const int grid = wgrad_grid_for(s, n, 1);
             launch_conv_wgrad(s, wa, c->stream);
             launch_reduce_slabs(c->slabs, grid, (int)td.n + cout, g, (int)td.n, g + td.n, cout, c->stream);
             HIPC(hipGetLastError()); NETCHK(c);
             HIPC(hipStreamSynchronize(c->stream));
-            std::vector<float> hg(td.n + cout);
-            HIPC(hipMemcpy(hg.data(), g, hg.size() * 4, hipMemcpyDeviceToHost));
-            to_ref_layout(td, hg.data(), out);
-            if (dbias_out) memcpy(dbias_out, hg.data() + td.n, cout * 4);
-            hipFree(g);
-        } else {            // 5: data gradient; 6 / 7: the fused data + weight gradient launch (block2.conv), returning dW (+ db) / dx
-            ARG(dout, "dout");
-            ARG(mode == 5 || (conv_bwd_fused_grid(s, n) > 0 && c->slabs), "modes 6 / 7: block2.conv in an IMPALA context");
-            if (int r = upload_act(c, dout, pp, &ddout)) return r;
-            HIPC(hipMalloc(&dgi, px * cin * 2 + 256));
-            ConvArgs g{};
-            g.in = ddout; g.pool_arg = di; g.w = dw; g.out = dgi; g.n = n; g.bf16 = 1; g.wbank = dbank + (long long)cout * bank_ws(cin);
-            float* gw = nullptr;
-            if (mode >= 6) { g.wg_in = din; g.wg_partial = c->slabs; HIPC(dalloc(&gw, td.n + cout)); }
-            launch_conv_dgrad(s, g, c->stream);
-            if (mode >= 6) launch_reduce_slabs(c->slabs, conv_bwd_fused_grid(s, n), (int)td.n + cout, gw, (int)td.n, gw + td.n, cout, c->stream);
-            HIPC(hipGetLastError()); NETCHK(c);
-            HIPC(hipStreamSynchronize(c->stream));
-            if (mode == 6) {
-                std::vector<float> hg(td.n + cout);
-                HIPC(hipMemcpy(hg.data(), gw, hg.size() * 4, hipMemcpyDeviceToHost));
-                to_ref_layout(td, hg.data(), out);
-                if (dbias_out) memcpy(dbias_out, hg.data() + td.n, cout * 4);
-            } else if (int r = download_act(c, dgi, out, px * cin)) return r;
-            if (gw) hipFree(gw);
+            if (int r = m.check()) return r;
+            return read_wgrad(g);
         }
-        void* fr[] = {dw, db, din, ddout, dp, di, dbank, ddesc, dgi};
-        for (void* p : fr) if (p) hipFree(p);
-        return 0;
+        // 5: data gradient; 6 / 7: the fused data + weight gradient launch (block2.conv, block3.conv), returning dW (+ db) / dx
+        HIPC(m.out(&dgi, px * cin * 2, "the data gradient"));
+        ConvArgs g{};
+        g.in = ddout; g.pool_arg = di; g.w = dw; g.out = dgi; g.n = n; g.bf16 = 1; g.wbank = dbank + (long long)cout * bank_ws(cin);
+        float* gw = nullptr;
+        const int fgrid = mode >= 6 ? conv_bwd_fused_grid(s, n) : 0;
+        if (mode >= 6) { g.wg_in = din; g.wg_partial = c->slabs; if (int r = wgrad_out(&gw, fgrid)) return r; }
+        launch_conv_dgrad(s, g, c->stream);
+        if (mode >= 6) launch_reduce_slabs(c->slabs, fgrid, (int)td.n + cout, gw, (int)td.n, gw + td.n, cout, c->stream);
+        HIPC(hipGetLastError()); NETCHK(c);
+        HIPC(hipStreamSynchronize(c->stream));
+        if (int r = m.check()) return r;
+        return mode == 6 ? read_wgrad(gw) : download_act(c, dgi, out, px * cin);
     }
-    if (mode >= 1) { ARG(dout, "dout"); if (int r = upload_act(c, dout, px * cout, &ddout)) return r; }
-    if (res) { if (int r = upload_act(c, res, px * out_ch, &dres)) return r; }
-    if (mask) { if (int r = upload_act(c, mask, px * out_ch, &dmask)) return r; }
+    if (mode >= 1) { ARG(dout, "dout"); if (int r = upload_act(c, m, dout, px * cout, &ddout)) return r; }
+    if (res) { if (int r = upload_act(c, m, res, px * out_ch, &dres)) return r; }
+    if (mask) { if (int r = upload_act(c, m, mask, px * out_ch, &dmask)) return r; }
     if (mode <= 1) {
-        HIPC(hipMalloc(&dout_buf, px * out_ch * 4 + 256));
+        HIPC(m.out(&dout_buf, px * out_ch * es, mode == 0 ? "the conv output" : "the data gradient"));
         ConvArgs a{};
         a.in = (mode == 0) ? din : ddout; a.idx = nullptr; a.in_base = 0; a.w = dw; a.bias = (mode == 0) ? db : nullptr;
         a.res = dres; a.mask = dmask; a.out = dout_buf; a.lut = c->lut; a.n = n; a.relu_in = (mode == 0) ? relu_in : 0; a.bf16 = c->bf;
@@ -1937,98 +2016,115 @@ int mi_op_conv3x3(mi_ctx* c, int32_t mode, int32_t cin, int32_t cout, int32_t hw
         if (mode == 0) launch_conv_fwd(s, a, c->stream); else launch_conv_dgrad(s, a, c->stream);
         HIPC(hipGetLastError()); NETCHK(c);
         HIPC(hipStreamSynchronize(c->stream));
-        if (int r = download_act(c, dout_buf, out, px * out_ch)) return r;
-    } else {
-        ARG(c->slabs, "wgrad needs an IMPALA context");
-        float* g = nullptr;
-        HIPC(dalloc(&g, td.n + cout));
-        WgradArgs a{};
-        a.in = din; a.idx = nullptr; a.in_base = 0; a.dout = ddout; a.partial = c->slabs; a.lut = c->lut; a.n = n; a.relu_in = relu_in; a.bf16 = c->bf;
-        a.lut16 = c->bf ? c->lut16 : nullptr;
-        const int grid = wgrad_grid_for(s, n, c->bf);
-        launch_conv_wgrad(s, a, c->stream);
-        launch_reduce_slabs(c->slabs, grid, (int)td.n + cout, g, (int)td.n, g + td.n, cout, c->stream);
-        HIPC(hipGetLastError()); NETCHK(c);
-        HIPC(hipStreamSynchronize(c->stream));
-        std::vector<float> hg(td.n + cout);
-        HIPC(hipMemcpy(hg.data(), g, hg.size() * 4, hipMemcpyDeviceToHost));
-        to_ref_layout(td, hg.data(), out);
-        if (dbias_out) memcpy(dbias_out, hg.data() + td.n, cout * 4);
-        hipFree(g);
+        if (int r = m.check()) return r;
+        return download_act(c, dout_buf, out, px * out_ch);
     }
-    void* fr[] = {dw, db, din, dres, dmask, ddout, dout_buf};
-    for (void* p : fr) if (p) hipFree(p);
-    return 0;
+    ARG(c->slabs, "wgrad needs an IMPALA context");
+    float* g = nullptr;
+    const int grid = wgrad_grid_for(s, n, c->bf);
+    if (int r = wgrad_out(&g, grid)) return r;
+    WgradArgs a{};
+    a.in = din; a.idx = nullptr; a.in_base = 0; a.dout = ddout; a.partial = c->slabs; a.lut = c->lut; a.n = n; a.relu_in = relu_in; a.bf16 = c->bf;
+    a.lut16 = c->bf ? c->lut16 : nullptr;
+    launch_conv_wgrad(s, a, c->stream);
+    launch_reduce_slabs(c->slabs, grid, (int)td.n + cout, g, (int)td.n, g + td.n, cout, c->stream);
+    HIPC(hipGetLastError()); NETCHK(c);
+    HIPC(hipStreamSynchronize(c->stream));
+    if (int r = m.check()) return r;
+    return read_wgrad(g);
 }
 
 // Fused residual block of the bf16 mode, op level.  mode 0: (x, w1, b1, w2, b2) -> a = conv1(relu(x)) + b1, y = conv2(relu(a)) + b2 + x.
 // mode 1: (dy = x, a_fwd, x_fwd, w1, w2) -> out_a = d a = convT2(dy) * (a_fwd > 0), out_y = d x = convT1(d a) * (x_fwd > 0) + dy.
+// mode 4: res1 + res2 in one launch as net_forward runs them in training mode: w1 / b1 = res1's (conv1; conv2), w2 / b2 = res2's,
+// out_a = (A1; A2), out_y = (P1; P2).
 int mi_op_resblock(mi_ctx* c, int32_t mode, int32_t ch, int32_t hw, int32_t n, const float* x, const float* w1_ref, const float* b1,
                    const float* w2_ref, const float* b2, const float* a_fwd, const float* x_fwd, float* out_a, float* out_y) {
     ARG(c && x && w1_ref && w2_ref && out_a && out_y && n >= 1, "null"); JOIN(c);
     ARG(c->bf, "the fused residual-block kernels exist in bf16 precision only");
-    ARG((mode == 0 || mode == 3) ? (b1 && b2) : (a_fwd && x_fwd), "modes 0 / 3 need the biases, modes 1 / 2 the forward tensors");
+    ARG(mode >= 0 && mode <= 4, "mode");
+    ARG((mode == 0 || mode >= 3) ? (b1 && b2) : (a_fwd && x_fwd), "modes 0 / 3 / 4 need the biases, modes 1 / 2 the forward tensors");
     ConvShape s;
     if (shape_of(ch, ch, hw, &s)) return -1;
+    const std::string hook = "mi_op_resblock mode " + std::to_string(mode);
+    OpMem m(hook.c_str(), c->stream);
     const size_t X = (size_t)n * hw * hw * ch, wl = (size_t)ch * ch * 9;
+    const int nc = mode == 4 ? 4 : 2;           // convs: (w1, w2), or mode 4's (res1.conv1, res1.conv2, res2.conv1, res2.conv2)
+    const float* wsrc[4] = {w1_ref, w2_ref, nullptr, nullptr};
+    const float* bsrc[4] = {b1, b2, nullptr, nullptr};
+    if (mode == 4) { wsrc[1] = w1_ref + wl; wsrc[2] = w2_ref; wsrc[3] = w2_ref + wl; bsrc[1] = b1 + ch; bsrc[2] = b2; bsrc[3] = b2 + ch; }
     TensorDesc td{"w", 0, 0, (int64_t)wl, K_CONVW, ch, ch};
-    std::vector<float> wdev(2 * wl + 2 * ch, 0.f);
-    to_device_layout(td, w1_ref, wdev.data()); to_device_layout(td, w2_ref, wdev.data() + wl);
-    if (b1) memcpy(wdev.data() + 2 * wl, b1, ch * 4);
-    if (b2) memcpy(wdev.data() + 2 * wl + ch, b2, ch * 4);
+    std::vector<float> wdev((size_t)nc * (wl + ch), 0.f);
+    for (int k = 0; k < nc; ++k) {
+        to_device_layout(td, wsrc[k], wdev.data() + k * wl);
+        if (bsrc[k]) memcpy(wdev.data() + nc * wl + k * ch, bsrc[k], ch * 4);
+    }
     float* dparams = nullptr; unsigned short* dbanks = nullptr; BankDesc* ddesc = nullptr;
-    void *dx = nullptr, *da = nullptr, *dxf = nullptr, *doa = nullptr, *doy = nullptr;
-    HIPC(dalloc(&dparams, wdev.size())); HIPC(hipMemcpy(dparams, wdev.data(), wdev.size() * 4, hipMemcpyHostToDevice));
+    void *dx = nullptr, *da = nullptr, *dxf = nullptr;
+    if (int r = upload(m, wdev.data(), wdev.size() * 4, (void**)&dparams)) return r;
+    const float* bias = dparams + nc * wl;
     const int ws = bank_ws(ch), nk = ch == 32 ? 9 : 5;
     const long long bl = (long long)ch * ws;
-    // bank 0 feeds the kernel's first conv, bank 1 its second: forward (w1, w2) as stored; backward (w2^T, w1^T)
+    // bank k feeds the kernel's k-th conv: forward the convs as stored; backward (w2^T, w1^T)
     const bool tr = (mode == 1 || mode == 2);
-    BankDesc d[2] = {{tr ? (long long)wl : 0, 0, ch, ch, ch, ch, tr ? 1 : 0, ws, nk}, {tr ? 0 : (long long)wl, bl, ch, ch, ch, ch, tr ? 1 : 0, ws, nk}};
-    HIPC(dalloc(&dbanks, (size_t)2 * bl)); HIPC(hipMalloc((void**)&ddesc, sizeof d)); HIPC(hipMemcpy(ddesc, d, sizeof d, hipMemcpyHostToDevice));
-    launch_pack_banks(dparams, dbanks, ddesc, 2, c->stream);
-    if (int r = upload_act(c, x, X, &dx)) return r;
-    HIPC(hipMalloc(&doa, X * 2 + 256)); HIPC(hipMalloc(&doy, X * 2 + 256));
+    BankDesc d[4];
+    for (int k = 0; k < nc; ++k) d[k] = BankDesc{tr ? (k == 0 ? (long long)wl : 0) : (long long)(k * wl), k * bl, ch, ch, ch, ch, tr ? 1 : 0, ws, nk};
+    HIPC(m.alloc(&dbanks, (size_t)nc * bl * 2));
+    if (int r = upload(m, d, sizeof(BankDesc) * nc, (void**)&ddesc)) return r;
+    launch_pack_banks(dparams, dbanks, ddesc, nc, c->stream);
+    if (int r = upload_act(c, m, x, X, &dx)) return r;
     if (mode == 2) {        // whole backward of a 16-channel block: out_y = dx, out_a[0 .. 2*(9*ch*ch + ch)) = {dW1, db1, dW2, db2} (reference layout)
         ARG((s == CS_16_16_32 || s == CS_32_32_16 || s == CS_32_32_8) && c->slabs, "the whole-backward kernels exist for the 16-channel @32x32 and 32-channel @16x16 blocks (IMPALA context)");
-        if (int r = upload_act(c, a_fwd, X, &da)) return r;
-        if (int r = upload_act(c, x_fwd, X, &dxf)) return r;
+        if (int r = upload_act(c, m, a_fwd, X, &da)) return r;
+        if (int r = upload_act(c, m, x_fwd, X, &dxf)) return r;
         const int grid = s == CS_16_16_32 ? resblock_bwd_full_grid(n) : resblock_bwd_full32_grid(s, n), slab = (int)wl + ch;
-        float* g = nullptr;
-        HIPC(dalloc(&g, (size_t)2 * slab));
+        void* doy = nullptr; float* g = nullptr;
+        HIPC(m.out(&doy, X * 2, "the data gradient"));
+        HIPC(m.out(&g, (size_t)2 * slab * 4, "the weight / bias gradients", 0));
         float* sl2 = c->slabs; float* sl1 = c->slabs + (size_t)1024 * slab;
+        HIPC(m.slab_rows(sl2, grid, slab, "conv2's weight-gradient slab rows past the grid"));
+        HIPC(m.slab_rows(sl1, grid, slab, "conv1's weight-gradient slab rows past the grid"));
         if (s == CS_16_16_32) launch_resblock_bwd_full_bf16(dx, da, dxf, doy, nullptr, n, dbanks, dbanks + bl, sl2, sl1, c->stream);
         else launch_resblock_bwd_full32_bf16(s, dx, da, dxf, doy, nullptr, n, dbanks, dbanks + bl, sl2, sl1, c->stream);
         launch_reduce_slabs(sl1, grid, slab, g, (int)wl, g + wl, ch, c->stream);
         launch_reduce_slabs(sl2, grid, slab, g + slab, (int)wl, g + slab + wl, ch, c->stream);
         HIPC(hipGetLastError()); NETCHK(c);
         HIPC(hipStreamSynchronize(c->stream));
+        if (int r = m.check()) return r;
         std::vector<float> hg(2 * slab);
         HIPC(hipMemcpy(hg.data(), g, hg.size() * 4, hipMemcpyDeviceToHost));
         to_ref_layout(td, hg.data(), out_a); memcpy(out_a + wl, hg.data() + wl, ch * 4);
         to_ref_layout(td, hg.data() + slab, out_a + slab); memcpy(out_a + slab + wl, hg.data() + slab + wl, ch * 4);
-        if (int r = download_act(c, doy, out_y, X)) return r;
-        void* fr2[] = {dparams, dbanks, ddesc, dx, da, dxf, doa, doy, g};
-        for (void* q : fr2) if (q) hipFree(q);
-        return 0;
+        return download_act(c, doy, out_y, X);
     }
-    if (mode == 3) {        // res1 + res2 in one launch, both with (w1, b1, w2, b2): out_a = second conv1 output, out_y = second block output
-        const float* bb[4] = {dparams + 2 * wl, dparams + 2 * wl + ch, dparams + 2 * wl, dparams + 2 * wl + ch};
+    void* o[4] = {};        // mode 4: A1, P1, A2, P2; otherwise out_a, out_y
+    static const char* oname[4] = {"A1 (res1.conv1 output)", "P1 (res1 output)", "A2 (res2.conv1 output)", "P2 (block output)"};
+    for (int k = 0; k < (mode == 4 ? 4 : 2); ++k) HIPC(m.out(&o[k], X * 2, mode == 4 ? oname[k] : (k ? "out_y" : "out_a")));
+    if (mode == 4) {
+        const float* bb[4] = {bias, bias + ch, bias + 2 * ch, bias + 3 * ch};
+        const unsigned short* bk[4] = {dbanks, dbanks + bl, dbanks + 2 * bl, dbanks + 3 * bl};
+        launch_resblock_pair_bf16(s, dx, bb, o[0], o[1], o[2], o[3], n, bk, c->stream);
+    } else if (mode == 3) {        // res1 + res2 in one launch, both with (w1, b1, w2, b2): out_a = second conv1 output, out_y = second block output
+        const float* bb[4] = {bias, bias + ch, bias, bias + ch};
         const unsigned short* bk[4] = {dbanks, dbanks + bl, dbanks, dbanks + bl};
-        launch_resblock_pair_bf16(s, dx, bb, nullptr, nullptr, doa, doy, n, bk, c->stream);
+        launch_resblock_pair_bf16(s, dx, bb, nullptr, nullptr, o[0], o[1], n, bk, c->stream);
     } else if (mode == 0) {
-        launch_resblock_bf16(s, dx, dparams + 2 * wl, dparams + 2 * wl + ch, doa, doy, n, dbanks, dbanks + bl, c->stream);
+        launch_resblock_bf16(s, dx, bias, bias + ch, o[0], o[1], n, dbanks, dbanks + bl, c->stream);
     } else {
-        if (int r = upload_act(c, a_fwd, X, &da)) return r;
-        if (int r = upload_act(c, x_fwd, X, &dxf)) return r;
-        launch_resblock_bwd_bf16(s, dx, da, dxf, doa, doy, n, dbanks, dbanks + bl, c->stream);
+        if (int r = upload_act(c, m, a_fwd, X, &da)) return r;
+        if (int r = upload_act(c, m, x_fwd, X, &dxf)) return r;
+        launch_resblock_bwd_bf16(s, dx, da, dxf, o[0], o[1], n, dbanks, dbanks + bl, c->stream);
     }
     HIPC(hipGetLastError()); NETCHK(c);
     HIPC(hipStreamSynchronize(c->stream));
-    if (int r = download_act(c, doa, out_a, X)) return r;
-    if (int r = download_act(c, doy, out_y, X)) return r;
-    void* fr[] = {dparams, dbanks, ddesc, dx, da, dxf, doa, doy};
-    for (void* q : fr) if (q) hipFree(q);
-    return 0;
+    if (int r = m.check()) return r;
+    if (mode == 4) {
+        for (int k = 0; k < 4; ++k)
+            if (int r = download_act(c, o[k], (k & 1 ? out_y : out_a) + (k >> 1) * X, X)) return r;
+        return 0;
+    }
+    if (int r = download_act(c, o[0], out_a, X)) return r;
+    return download_act(c, o[1], out_y, X);
 }
 
 // bit 0: run rollout-sized bf16 inference passes on the separate block-2 / block-3 kernels instead of the fused launch (parity A/B)
@@ -2117,23 +2213,22 @@ int mi_debug_read(mi_ctx* c, int32_t which, int32_t n, float* out) {
 int mi_op_maxpool(mi_ctx* c, int32_t mode, int32_t n, int32_t hw, int32_t ch, const float* in, const float* dout, float* out) {
     ARG(c && in && out, "null"); JOIN(c); ARG(n >= 1, "n");
     ARG((hw == 64 && ch == 16) || (hw == 32 && ch == 32) || (hw == 16 && ch == 32), "max pool shapes of the IMPALA blocks only: (64,16), (32,32), (16,32)");
-    const size_t X = (size_t)n * hw * hw * ch, p = X / 4;
+    ARG(mode == 0 || dout, "dout");
+    OpMem m(mode == 0 ? "mi_op_maxpool mode 0" : "mi_op_maxpool mode 1", c->stream);
+    const size_t X = (size_t)n * hw * hw * ch, p = X / 4, es = c->bf ? 2 : 4;
     void *din = nullptr, *dp = nullptr, *dd = nullptr, *dg = nullptr; uint8_t* di = nullptr;
-    if (int r = upload_act(c, in, X, &din)) return r;
-    HIPC(hipMalloc(&dp, p * 4 + 256)); HIPC(dalloc(&di, p));
+    if (int r = upload_act(c, m, in, X, &din)) return r;
+    HIPC(m.out(&dp, p * es, "the pooled map")); HIPC(m.out(&di, p, "the arg-max bytes", 0));
     if (c->bf) launch_maxpool_fwd_bf16(din, dp, di, n, hw, ch, c->stream); else launch_maxpool_fwd((const float*)din, (float*)dp, di, n, hw, ch, c->stream);
-    if (mode == 0) { HIPC(hipStreamSynchronize(c->stream)); if (int r = download_act(c, dp, out, p)) return r; }
-    else {
-        ARG(dout, "dout");
-        if (int r = upload_act(c, dout, p, &dd)) return r;
-        HIPC(hipMalloc(&dg, X * 4 + 256));
+    if (mode != 0) {
+        if (int r = upload_act(c, m, dout, p, &dd)) return r;
+        HIPC(m.out(&dg, X * es, "the data gradient"));
         if (c->bf) launch_maxpool_bwd_bf16(dd, di, dg, n, hw, ch, c->stream); else launch_maxpool_bwd((const float*)dd, di, (float*)dg, n, hw, ch, c->stream);
-        HIPC(hipStreamSynchronize(c->stream));
-        if (int r = download_act(c, dg, out, X)) return r;
     }
     HIPC(hipGetLastError()); NETCHK(c);
-    hipFree(din); hipFree(dp); hipFree(di); if (dd) hipFree(dd); if (dg) hipFree(dg);
-    return 0;
+    HIPC(hipStreamSynchronize(c->stream));
+    if (int r = m.check()) return r;
+    return mode == 0 ? download_act(c, dp, out, p) : download_act(c, dg, out, X);
 }
 
 int mi_op_gemm(mi_ctx* c, int32_t M, int32_t N, int32_t K, const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk,

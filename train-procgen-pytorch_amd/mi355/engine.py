@@ -464,14 +464,23 @@ class Engine:
 
     def op_resblock(self, mode, x, w1, w2, b1=None, b2=None, a_fwd=None, x_fwd=None):
         """bf16 precision: fused residual block.  mode 0 -> (conv1 output, block output); mode 1 (x = dy) -> (d conv1-output, d block-input);
-        mode 2 (16 channels @32x32, x = dy) -> (flat {dW1, db1, dW2, db2} in the head of the first array, d block-input)."""
+        mode 2 (16 channels @32x32, x = dy) -> (flat {dW1, db1, dW2, db2} in the head of the first array, d block-input);
+        mode 3: res1 + res2 in one launch, both blocks with (w1, b1, w2, b2) -> (res2's conv1 output, block output);
+        mode 4: res1 + res2 in one launch with distinct weights: w1 / b1 = res1's (conv1, conv2) stacked ([2, ch, ch, 3, 3] / [2, ch]),
+        w2 / b2 = res2's -> ([A1, A2], [P1, P2]), each [2, n, hw, hw, ch] (res conv1 outputs, res block outputs)."""
         x = _f32(x)
         n, hw, _, ch = x.shape
         w1, w2 = _f32(w1), _f32(w2)
         b1, b2, a_fwd, x_fwd = (None if a is None else _f32(a) for a in (b1, b2, a_fwd, x_fwd))
-        oa, oy = np.empty(max(x.size, 2 * (9 * ch * ch + ch)), np.float32), np.empty_like(x)      # mode 2 packs the weight gradients into oa
+        if mode == 4:
+            assert w1.size == w2.size == 2 * 9 * ch * ch and b1.size == b2.size == 2 * ch, "mode 4 takes each block's two convs stacked"
+            oa, oy = np.empty((2,) + x.shape, np.float32), np.empty((2,) + x.shape, np.float32)
+        else:
+            oa, oy = np.empty(max(x.size, 2 * (9 * ch * ch + ch)), np.float32), np.empty_like(x)      # mode 2 packs the weight gradients into oa
         self._chk(self.lib.mi_op_resblock(self._ctx, C.c_int32(mode), C.c_int32(ch), C.c_int32(hw), C.c_int32(n), _fp(x), _fp(w1), _fp(b1),
                                           _fp(w2), _fp(b2), _fp(a_fwd), _fp(x_fwd), _fp(oa), _fp(oy)))
+        if mode == 4:
+            return oa, oy
         return (oa if mode == 2 else oa[:x.size].reshape(x.shape)), oy
 
     def op_maxpool(self, mode, x, dout=None):
