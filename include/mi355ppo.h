@@ -142,6 +142,20 @@ int mi_commit_staged(mi_ctx* ctx, int32_t t);
 int mi_set_gru(mi_ctx* ctx, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh);
 int mi_rec_state(mi_ctx* ctx, const float* hidden /* E x H or NULL */, const float* done /* E or NULL */);
 int mi_get_hidden(mi_ctx* ctx, float* hidden /* E x H */);
+/* ---- recurrent policies on the pipelined rollout (mi_rollout_groups / submit / wait; the reference's serial loop is agents/ppo.py:225-236
+ *      with hidden_state / done carried from step to step, common/model.py:212-225 for the cell).  With a GRU set every group step runs
+ *      the cell on its own rows as ONE fused launch: h' = GRU(x, h (1 - done)), where h is the step's input state and done is the group's
+ *      done of step t-1 (handed over with the submit), at t == 0 that of mi_rec_begin.  The heads sample on h'.  A row's numbers do
+ *      not depend on the number of groups (no split-K: G = 2 and G = 4 give bit-identical rollouts); against the serial mi_rollout_step
+ *      they differ by the GEMMs' summation order only.
+ *      mi_rec_begin(hidden, done) starts such a rollout: hidden (E x H; NULL = the device's current state) and done (E; NULL = zeros)
+ *      are the carried-in state and flags of its step 0, uploaded in stream order on the main stream with no host wait (the groups' first
+ *      submits order themselves behind it).  Required before the groups' step 0 of every recurrent rollout.  The first call allocates the
+ *      context's hidden ring: (T + 1) x E x H floats, slot t = the input state of step t before masking (what Storage.store records as
+ *      hidden_state, common/storage.py:39-54).  mi_get_hidden_ring(t0, t1, out) copies slots [t0, t1) into out ((t1 - t0) x E x H);
+ *      mi_get_hidden reads h' of the last step (the bootstrap step's state that the serial loop carries into the next iteration). */
+int mi_rec_begin(mi_ctx* ctx, const float* hidden /* E x H or NULL */, const float* done /* E or NULL */);
+int mi_get_hidden_ring(mi_ctx* ctx, int32_t t0, int32_t t1, float* out /* (t1 - t0) x E x H */);
 /* policy(obs, hx, masks) for a recurrent policy on E observations: consumes / advances the state like a policy step */
 int mi_forward_rec(mi_ctx* ctx, const void* obs, float* logp_all, float* value, float* hidden_out);
 
@@ -250,6 +264,11 @@ int mi_debug_read(mi_ctx* ctx, int32_t which, int32_t n, float* out);
  * n x {c0,c1,c2,c3,k0,k1} in; out4 = n x 4 output words of the ten-round bijection (checked against the Random123 known-answer
  * vectors), u_out = n uniforms exactly as the sample kernels draw them for seed = k0 | k1 << 32, counter = c0 | c1 << 32. */
 int mi_debug_philox(mi_ctx* ctx, const uint32_t* ctr_key6, int32_t n, uint32_t* out4, float* u_out);
+/* test hook: the pipelined rollout's fused GRU step on caller data -- n rows, width H (a multiple of 64 in [64, 512], independent of the
+ * context's), x / h: n x H, done: n, weights in nn.GRU's layout (common/model.py:212-225); h_out = h' = GRU(x, h (1 - done)), h_copy (may
+ * be NULL) = the kernel's second copy of h' (the hidden ring's next slot in the rollout) */
+int mi_debug_gru_step(mi_ctx* ctx, int32_t n, int32_t H, const float* x, const float* h, const float* done, const float* w_ih,
+                      const float* w_hh, const float* b_ih, const float* b_hh, float* h_out, float* h_copy);
 /* measurement hook: wall-clock microseconds per policy step of slot t (the step's launches + a stream wait, `iters` times), issued
  * eagerly (mode 0) or as one replay of a hipGraph captured from the same launches (mode 1) */
 int mi_debug_step_latency(mi_ctx* ctx, int32_t t, int32_t iters, int32_t mode, float* us_out);

@@ -306,9 +306,15 @@ class PPO(BaseAgent):
         engine -- in ONE host loop: every (lane, group) is an independent chain.  One lane is the pipelined collector of PPO.train; two
         lanes are the training and the validation rollout of an iteration (agents/ppo.py:225-252 runs them one after the other on the same
         policy; neither depends on the other): both are latency chains that leave the GPU mostly idle, so interleaved they take little
-        longer than one alone."""
+        longer than one alone.
+
+        A recurrent policy's lanes start from their carried-in hidden_state / done (mi_rec_begin: step 0 masks with that done), the GRU cell
+        runs inside every group step on the device, and after the rollout the storage's hidden states come from the engine's hidden ring
+        in one download: _hidden[t] = the input state of step t (what _collect's store records), _hidden[T] = the state after the
+        bootstrap step's cell, which is also the returned hidden state (the serial loop carries that one into the next iteration)."""
         from common.env.vec_envs import StepInfo
         T, arch = self.n_steps, self.policy.arch
+        rec = self.policy.is_recurrent()
         want_dtype = self._obs_dtype(arch)
 
         class Lane:
@@ -332,6 +338,8 @@ class PPO(BaseAgent):
             # the validation lane draws from its own Philox stream (the reference's two rollouts share torch's generator, not its numbers)
             L.seed = self.seed * 1000003 + self._iter + (k << 40)
             L.wait, L.submit, L.ready = engine.rollout_wait_into, engine.rollout_submit, engine.dma_ready
+            if rec:
+                engine.rec_begin(hidden_state, done)
             Ls.append(L)
         for t in range(T + 1):
             for g in range(max(L.G for L in Ls)):
@@ -362,12 +370,20 @@ class PPO(BaseAgent):
         for L in Ls:
             for g in range(L.G):
                 L.wait(g, L.pa + 8 * L.sls[g].start, L.pl + 4 * L.sls[g].start, L.pv + 4 * L.sls[g].start)
+            if rec:
+                if getattr(L.storage, "_hidden_pinned_by", None) is not L.engine:
+                    # the ring download (67 MB at T = E = H = 256) lands in engine-owned page-locked memory, as Storage's reward / done
+                    # mirrors do; every slot is rewritten below
+                    L.storage._hidden = L.engine.pinned(L.storage._hidden.shape, np.float32)
+                    L.storage._hidden_pinned_by = L.engine
+                L.engine.get_hidden_ring(0, T, L.storage._hidden[:T])
+                L.hidden = L.engine.get_hidden()
             L.storage._hidden[T] = L.hidden                  # store_last: value[T] and the frames are already in the device ring
             out.append((np.concatenate(L.obs_g), L.hidden, L.dn.copy()))
         return out
 
     def _can_pipeline(self, env):
-        return len(getattr(env, "env_groups", ())) > 1 and not self.policy.is_recurrent() and self.n_envs % len(env.env_groups) == 0
+        return len(getattr(env, "env_groups", ())) > 1 and self.n_envs % len(env.env_groups) == 0
 
     def train(self, num_timesteps):
         self.total_timesteps = num_timesteps

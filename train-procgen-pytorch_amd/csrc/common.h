@@ -224,6 +224,9 @@ void launch_conv1_input_grad(const void* dC, int bf16, const float* W, float* dX
 void launch_mask_rows(const float* h, const float* done, float* out, int n, int H, hipStream_t st);   // out = h * (1 - done[row])
 void launch_gru_value_bwd(const float* gi, const float* gh, const float* hm, const float* wv, float* dgates, int n, int H, hipStream_t st);
 void launch_gru_gates(const float* gi, const float* gh, const float* hm, float* h_out, float* feat_out, int n, int H, hipStream_t st);
+// h' = GRU(x, h_in * (1 - done)) for n rows in one launch -> h_out (and h_copy unless null); h_in aliases none of x / h_out / h_copy
+void launch_gru_step(const float* x, const float* h_in, const float* done, const float* w_ih, const float* w_hh, const float* b_ih,
+                     const float* b_hh, float* h_out, float* h_copy, int n, int H, hipStream_t st);
 
 // ---------------------------------------------------------------- embedder.fc on the bf16 matrix cores (fc_bf16.hip)
 // IMPALA embedder widths (output_dim): the multiples of 64 in [64, 512] (mi_create).  The bf16 fc kernels and the fc section of

@@ -182,6 +182,10 @@ struct mi_ctx {
     ncclComm_t comm, comm_grad; int comm_world, comm_rank; hipStream_t comm_stream; hipEvent_t ev_ar_ready, ev_ar_done;   // comm: main-stream collectives; comm_grad: the side stream's
     bool ar_armed, ar_issued, ar_inflight; double* adv_all;
     std::string net_err; std::mutex net_err_mu;   // set by the (void) network program on an unsupported launch (any thread); every entry point reports it as -4
+    // recurrent policies on the pipelined rollout (mi_rec_begin, group_issue): hidden ring [T+1][E][H] -- slot t = the input hidden state of step t (slot 0 from
+    // mi_rec_begin, slot t+1 written by step t's fused cell); pinned staging of mi_rec_begin's upload {hidden [E][H], done [E]} and the event
+    // that frees it; g_rec_ok[g]: mi_rec_begin has run since group g last started a rollout (t == 0)
+    float *h_ring, *h_rec_stage; hipEvent_t ev_rec; bool g_rec_ok[MAX_GROUPS];
 };
 
 // ------------------------------------------------------------------------------------------ layout tables
@@ -456,6 +460,7 @@ int mi_create(const mi_config* cfg, mi_ctx** out) {
     }
     c->gru_x = c->gru_dg = nullptr; c->sal_keep_x = c->bwd_from_dfeat = false;
     c->gru_on = false; c->gru_wih = c->gru_whh = c->gru_bih = c->gru_bhh = c->h_state = c->h_masked = c->gru_gi = c->gru_gh = c->d_done = nullptr;
+    c->h_ring = c->h_rec_stage = nullptr; c->ev_rec = nullptr; for (bool& b : c->g_rec_ok) b = false;
     HIPC(hipDeviceSynchronize());
     *out = c;
     return 0;
@@ -490,6 +495,7 @@ int mi_destroy(mi_ctx* c) {
     if (c->banks) hipFree(c->banks); if (c->d_bank_desc) hipFree(c->d_bank_desc); if (c->c1_bank) hipFree(c->c1_bank);
     hipFree(c->stats_ring); hipFree(c->fs_ring); hipFree(c->fs_parts); if (c->d_slab_desc) hipFree(c->d_slab_desc); if (c->sal_dc) hipFree(c->sal_dc); if (c->sal_dx) hipFree(c->sal_dx); hipFree(c->d_pack); hipFree(c->d_rd); hipHostFree(c->h_pack); hipHostFree(c->h_rd); hipFree(c->d_done_ctr); if (c->side_stream) hipStreamDestroy(c->side_stream); hipEventDestroy(c->ev_side_fork); hipEventDestroy(c->ev_side_join); hipHostFree(c->h_flag);
     { float* gr[] = {c->gru_wih, c->gru_whh, c->gru_bih, c->gru_bhh, c->h_state, c->h_masked, c->gru_gi, c->gru_gh, c->d_done, c->gru_x, c->gru_dg}; for (float* q : gr) if (q) hipFree(q); }
+    if (c->h_ring) hipFree(c->h_ring); if (c->h_rec_stage) hipHostFree(c->h_rec_stage); if (c->ev_rec) hipEventDestroy(c->ev_rec);
     hipFree(c->act); hipFree(c->adv_stats); hipFree(c->d_idx); hipFree(c->sumsq);
     if (c->fs_colmax) hipFree(c->fs_colmax); if (c->fs_arg) hipFree(c->fs_arg);
     if (c->fs_keys) hipFree(c->fs_keys); if (c->fs_keys_local) hipFree(c->fs_keys_local); if (c->d_gpos) hipFree(c->d_gpos); if (c->h_gpos) hipHostFree(c->h_gpos);
@@ -1231,9 +1237,20 @@ static int group_issue(mi_ctx* c, int g, const GroupJob& j) {
     const float* du = nullptr;
     if (j.u) { HIPC(hipMemcpyAsync(c->d_u + e0, j.u, (size_t)ng * 4, hipMemcpyHostToDevice, st)); du = c->d_u + e0; }
     InputSrc src{c->frames ? (const void*)c->frames : (const void*)c->obsf, nullptr, (long long)j.t * E + e0};
-    net_forward(c, src, ng, true, false, false, e0);
+    net_forward(c, src, ng, false, false, false, e0);
+    const float* hin = c->feat + (size_t)e0 * c->H;          // what the heads read: the embedder output, or h' of a GRU context
+    if (c->gru_on) {
+        // the GRU cell as ONE launch (misc.hip gru_step_kernel): input state from hidden-ring slot t (mi_rec_begin's upload at t == 0, else
+        // step t-1's output), masked by the group's done (mi_rec_begin's at t == 0, else the copy above); h' -> h_state rows, and slot t+1
+        // unless this is the bootstrap step.  The heads read h' from h_state (the cell cannot overwrite feat, which its other workgroups read).
+        const size_t H = c->H;
+        float* slot = c->h_ring + ((size_t)j.t * E + e0) * H;
+        launch_gru_step(c->feat + (size_t)e0 * H, slot, c->d_done + e0, c->gru_wih, c->gru_whh, c->gru_bih, c->gru_bhh, c->h_state + (size_t)e0 * H,
+                        j.last ? nullptr : slot + (size_t)E * H, ng, c->H, st);
+        hin = c->h_state + (size_t)e0 * H;
+    }
     const size_t o = (size_t)j.t * E + e0;
-    launch_heads_sample(c->feat + (size_t)e0 * c->H, c->params + c->wh_off, c->params + c->bh_off, ng, c->H, c->A, du, j.seed, (unsigned long long)j.t * E + e0,
+    launch_heads_sample(hin, c->params + c->wh_off, c->params + c->bh_off, ng, c->H, c->A, du, j.seed, (unsigned long long)j.t * E + e0,
                         j.last ? nullptr : c->act + o, j.last ? nullptr : c->logp + o, c->value + o, c->h_pack + 3 * e0, nullptr,
                         j.have_rd ? h_rd : nullptr, j.have_rd ? c->rew + o - E : nullptr, j.have_rd ? c->done + o - E : nullptr, st,
                         c->d_done_ctr + 1 + g, c->h_flag + 1 + g, j.ticket);
@@ -1292,6 +1309,10 @@ int mi_rollout_submit(mi_ctx* c, int32_t t, int32_t g, const void* frames, size_
     const int E = c->E, ng = E / c->n_groups, e0 = g * ng;
     ARG(!frames || bytes == (size_t)ng * c->obs_bytes_per_env, "frames byte count != (E / groups) * bytes_per_env");
     if (rew_prev || done_prev) ARG(rew_prev && done_prev && t >= 1, "rew_prev/done_prev come together and belong to step t-1");
+    if (c->gru_on) {
+        ARG(c->h_ring && (t > 0 || c->g_rec_ok[g]), "recurrent rollout: call mi_rec_begin before the groups' first step (t == 0) of every rollout");
+        if (t == 0) c->g_rec_ok[g] = false;
+    }
     GroupWorker* w = c->gw[g];
     worker_drain(w);
     if (!c->g_forked[g]) {               // first step since the main stream last worked: parameters / packed banks must be in place
@@ -1474,6 +1495,38 @@ int mi_rec_state(mi_ctx* c, const float* hidden, const float* done) {
     if (hidden) HIPC(hipMemcpyAsync(c->h_state, hidden, E * H * 4, hipMemcpyHostToDevice, c->stream));
     if (done) HIPC(hipMemcpyAsync(c->d_done, done, E * 4, hipMemcpyHostToDevice, c->stream));
     else HIPC(hipMemsetAsync(c->d_done, 0, E * 4, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return 0;
+}
+int mi_rec_begin(mi_ctx* c, const float* hidden, const float* done) {
+    ARG(c, "null"); JOIN(c); ARG(c->gru_on, "no GRU set: call mi_set_gru first");
+    const size_t H = c->H, E = c->E;
+    if (!c->h_ring) {                                     // only contexts that run grouped recurrent rollouts pay for the ring (67 MB at T = E = H = 256)
+        HIPC(dalloc(&c->h_ring, (size_t)(c->T + 1) * E * H));
+        HIPC(hipHostMalloc((void**)&c->h_rec_stage, (E * H + E) * 4, hipHostMallocDefault));
+        HIPC(hipEventCreateWithFlags(&c->ev_rec, hipEventDisableTiming));
+    } else
+        HIPC(hipEventSynchronize(c->ev_rec));             // the previous call's upload has left the staging buffer (long since, normally)
+    if (hidden) {
+        memcpy(c->h_rec_stage, hidden, E * H * 4);
+        HIPC(hipMemcpyAsync(c->h_ring, c->h_rec_stage, E * H * 4, hipMemcpyHostToDevice, c->stream));
+        HIPC(hipMemcpyAsync(c->h_state, c->h_ring, E * H * 4, hipMemcpyDeviceToDevice, c->stream));
+    } else
+        HIPC(hipMemcpyAsync(c->h_ring, c->h_state, E * H * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (done) {
+        memcpy(c->h_rec_stage + E * H, done, E * 4);
+        HIPC(hipMemcpyAsync(c->d_done, c->h_rec_stage + E * H, E * 4, hipMemcpyHostToDevice, c->stream));
+    } else
+        HIPC(hipMemsetAsync(c->d_done, 0, E * 4, c->stream));
+    HIPC(hipEventRecord(c->ev_rec, c->stream));
+    for (bool& b : c->g_rec_ok) b = true;
+    return 0;
+}
+int mi_get_hidden_ring(mi_ctx* c, int32_t t0, int32_t t1, float* out) {
+    ARG(c && out, "null"); JOIN(c); ARG(c->h_ring, "no hidden ring: mi_rec_begin has not run");
+    ARG(t0 >= 0 && t0 < t1 && t1 <= c->T + 1, "need 0 <= t0 < t1 <= T + 1");
+    const size_t slot = (size_t)c->E * c->H;
+    HIPC(hipMemcpyAsync(out, c->h_ring + (size_t)t0 * slot, (size_t)(t1 - t0) * slot * 4, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -2144,6 +2197,29 @@ int mi_debug_philox(mi_ctx* c, const uint32_t* ctr_key6, int32_t n, uint32_t* ou
     HIPC(hipMemcpy(u_out, du, (size_t)n * 4, hipMemcpyDeviceToHost));
     hipFree(din); hipFree(dout); hipFree(du);
     return 0;
+}
+
+// The fused GRU step of the pipelined rollout (misc.hip gru_step_kernel) on caller data, for tests: n rows, width H (any multiple of 64 up
+// to 512, independent of the context's), weights in nn.GRU's layout.  h_out = h' (and h_copy = the kernel's second copy of it, if not null).
+int mi_debug_gru_step(mi_ctx* c, int32_t n, int32_t H, const float* x, const float* h, const float* done, const float* w_ih, const float* w_hh,
+                      const float* b_ih, const float* b_hh, float* h_out, float* h_copy) {
+    ARG(c && x && h && done && w_ih && w_hh && b_ih && b_hh && h_out, "null"); JOIN(c);
+    ARG(n >= 1 && n <= 65536 && H >= 64 && H <= 512 && H % 64 == 0, "n in [1, 65536], H a multiple of 64 in [64, 512]");
+    const size_t nh = (size_t)n * H, w = (size_t)3 * H * H;
+    std::vector<float*> d(9, nullptr);
+    const size_t sz[9] = {nh, nh, (size_t)n, w, w, (size_t)3 * H, (size_t)3 * H, nh, nh};
+    const float* src[7] = {x, h, done, w_ih, w_hh, b_ih, b_hh};
+    int rc = 0;
+    for (int i = 0; i < 9 && !rc; ++i) if (hipMalloc((void**)&d[i], sz[i] * 4) != hipSuccess) rc = fail(-2, "hipMalloc failed");
+    for (int i = 0; i < 7 && !rc; ++i) if (hipMemcpy(d[i], src[i], sz[i] * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(-2, "upload failed");
+    if (!rc) {
+        launch_gru_step(d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], n, H, c->stream);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(-4, "gru_step_kernel failed");
+    }
+    if (!rc && hipMemcpy(h_out, d[7], nh * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(-2, "download failed");
+    if (!rc && h_copy && hipMemcpy(h_copy, d[8], nh * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(-2, "download failed");
+    for (float* p : d) if (p) hipFree(p);
+    return rc;
 }
 
 // Measurement hook ("hipGraph"): wall-clock microseconds per policy step of slot t -- the step's launches (conv stack,

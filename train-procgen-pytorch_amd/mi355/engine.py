@@ -39,9 +39,9 @@ def lib_path():
 
 EXPORTS = ("mi_last_error mi_create mi_destroy mi_sync mi_host_alloc mi_host_free mi_host_register mi_host_unregister mi_param_count mi_set_params "
            "mi_get_params mi_copy_params mi_get_grads mi_set_adam_state mi_get_adam_state mi_put_obs mi_get_obs mi_put_step "
-           "mi_put_policy_outputs mi_read_field mi_write_field mi_policy_step mi_rollout_step mi_rollout_groups mi_rollout_submit mi_rollout_wait mi_predict_staged mi_value_saliency mi_commit_staged mi_set_gru mi_rec_state mi_get_hidden mi_forward_rec mi_forward mi_compute_estimates "
+           "mi_put_policy_outputs mi_read_field mi_write_field mi_policy_step mi_rollout_step mi_rollout_groups mi_rollout_submit mi_rollout_wait mi_predict_staged mi_value_saliency mi_commit_staged mi_set_gru mi_rec_state mi_get_hidden mi_rec_begin mi_get_hidden_ring mi_forward_rec mi_forward mi_compute_estimates "
            "mi_adv_stats mi_adv_apply mi_minibatch mi_minibatch_multi mi_optimizer_step mi_loss_log_read mi_device_ptr "
-           "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_step_latency").split()
+           "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_gru_step mi_debug_step_latency").split()
 
 
 def load_library():
@@ -329,6 +329,23 @@ class Engine:
         self._chk(self.lib.mi_get_hidden(self._ctx, _fp(out)))
         return out
 
+    def rec_begin(self, hidden=None, done=None):
+        """Carried-in hidden state (E, H) / done flags (E,) of a pipelined recurrent rollout's step 0 (mi_rec_begin: stream-ordered, no host
+        wait; None = the device's current state / zeros).  Call before the groups' first rollout_submit of every rollout."""
+        hidden = None if hidden is None else _f32(hidden).reshape(self.E, self.H)
+        done = None if done is None else _f32(done).reshape(self.E)
+        self._chk(self.lib.mi_rec_begin(self._ctx, _fp(hidden), _fp(done)))
+
+    def get_hidden_ring(self, t0, t1, out=None):
+        """Slots [t0, t1) of the hidden ring, (t1 - t0, E, H) float32: slot t = the input hidden state of step t of the last pipelined
+        recurrent rollout.  out: a C-contiguous float32 array of that shape to fill (page-locked: Engine.dma_ready)."""
+        if out is None:
+            out = np.empty((t1 - t0, self.E, self.H), np.float32)
+        elif out.dtype != np.float32 or not out.flags.c_contiguous or out.size != (t1 - t0) * self.E * self.H:
+            raise EngineError("get_hidden_ring needs a C-contiguous float32 array of (t1 - t0) * E * H elements")
+        self._chk(self.lib.mi_get_hidden_ring(self._ctx, C.c_int32(t0), C.c_int32(t1), _fp(out)))
+        return out
+
     def forward_rec(self, obs):
         want = np.uint8 if self.arch == ARCH_IMPALA else np.float32
         obs = np.ascontiguousarray(obs, dtype=want)
@@ -526,6 +543,17 @@ class Engine:
         out, u = np.empty((a.shape[0], 4), np.uint32), np.empty(a.shape[0], np.float32)
         self._chk(self.lib.mi_debug_philox(self._ctx, _fp(a), C.c_int32(a.shape[0]), _fp(out), _fp(u)))
         return out, u
+
+    def debug_gru_step(self, x, h, done, w_ih, w_hh, b_ih, b_hh, with_copy=False):
+        """The pipelined rollout's fused GRU step on caller data (mi_debug_gru_step): x, h (n, H), done (n,), nn.GRU-layout weights ->
+        h' (n, H), or (h', the kernel's second copy of h') with with_copy."""
+        x, h = _f32(x), _f32(h)
+        n, H = x.shape
+        a = [_f32(v) for v in (done, w_ih, w_hh, b_ih, b_hh)]
+        out = np.empty((n, H), np.float32)
+        cp = np.empty((n, H), np.float32) if with_copy else None
+        self._chk(self.lib.mi_debug_gru_step(self._ctx, C.c_int32(n), C.c_int32(H), _fp(x), _fp(h), *[_fp(v) for v in a], _fp(out), _fp(cp)))
+        return (out, cp) if with_copy else out
 
     def debug_step_latency(self, t, iters=200, graph=False):
         """microseconds per policy step of slot t (launches + stream wait), eager or as a replayed hipGraph of the same launches"""

@@ -112,7 +112,7 @@ def add_training_args(p):
     p.add_argument('--precision', type=str, default=None, choices=['fp32', 'bf16'],
                    help="IMPALA activation storage / matrix-core type: fp32 = parity mode (default), bf16 = BASELINE config 3 (what bench.py measures)")
     p.add_argument('--rollout_groups', type=int, default=0,
-                   help="env groups of the pipelined rollout (one group's frame upload + forward beside the host's env.step of another); 0 = auto (from 128 envs per rank: 4, or 2 + 2 when a validation env runs beside the training env; else 2); 1 = the reference's serial step")
+                   help="env groups of the pipelined rollout (one group's frame upload + forward beside the host's env.step of another); 0 = auto (from 128 envs per rank: 4, or 2 + 2 when a validation env runs beside the training env; else 2; a recurrent policy: 1); 1 = the reference's serial step; a recurrent policy is pipelined only with an explicit G >= 2")
     p.add_argument('--x_entropy_coef', type=float, default=None)
     return p
 
@@ -170,19 +170,23 @@ def _one_env(env_name, n_envs, seed, A, args, hp, is_valid, ret_rms=None, num_th
 
 def make_env(env_name, n_envs, seed, A, args, hp, is_valid=False):
     """get_env_constructor(env_name)(args, hp, is_valid) (common/env/env_constructor.py:13-31) for the envs of the PPO path.  With
-    --rollout_groups G > 1 (and a non-recurrent policy) the n_envs environments are G independent sub-envs behind one VecEnv
-    (EnvGroups): same protocol outwards, and the agent pipelines the groups.  Procgen groups share ONE running return variance, so
-    reward normalisation stays a single statistic over all envs (procgen_wrappers.py:316-355) -- but it is UPDATED per group step:
+    --rollout_groups G > 1 the n_envs environments are G independent sub-envs behind one VecEnv (EnvGroups): same protocol outwards,
+    and the agent pipelines the groups (a recurrent policy's GRU cell runs inside every group step).  A recurrent policy gets groups
+    only from an explicit G >= 2; the automatic setting (0) keeps its single VecEnv.  Procgen groups share ONE running return variance,
+    so reward normalisation stays a single statistic over all envs (procgen_wrappers.py:316-355) -- but it is UPDATED per group step:
     group g's rewards of step t are scaled by a variance that already holds groups < g of step t and not yet groups > g, where the
     reference's VecNormalize folds all n_envs returns in before scaling any.  The statistic converges to the same value; individual
-    scaled rewards differ in the last digits early on.  `--rollout_groups 1` gives the reference's exact scaling (and its serial step)."""
+    scaled rewards differ in the last digits early on.  This holds for recurrent policies with groups as for the others.
+    `--rollout_groups 1` (and, for a recurrent policy, the automatic setting) gives the reference's exact scaling and its serial step."""
     G = int(getattr(args, "rollout_groups", 1))
+    if G <= 0 and hp.get("recurrent", False):
+        G = 1
     if G > 4:
         raise ValueError(f"--rollout_groups {G}: the engine pipelines at most 4 env groups (mi_rollout_groups; more busy streams than that serialise)")
     if G <= 0:
         # auto: 4 chains keep the GPU's stream slots busy; with a validation env the agent runs both rollouts as lanes of one loop, 2 + 2
         G = (2 if getattr(args, "use_valid_env", False) else 4) if n_envs >= 128 and n_envs % 8 == 0 else 2
-    if G == 1 or hp.get("recurrent", False) or n_envs % G or (n_envs // G) % 2 or env_name.startswith("cartpole"):
+    if G == 1 or n_envs % G or (n_envs // G) % 2 or env_name.startswith("cartpole"):
         return _one_env(env_name, n_envs, seed, A, args, hp, is_valid)
     rms = None
     if env_name != "synthetic" and hp.get("normalize_rew", True):
@@ -239,6 +243,8 @@ def train_ppo(args):
     A = (9 if args.reduce_duplicate_actions else 15) if hp.get("architecture", "impala") == "impala" else 2
     env = make_env(env_name, n_envs, args.seed + 2 * rank, A, args, hp)
     env_valid = make_env(env_name, n_envs, args.seed + 2 * rank + 1, A, args, hp, is_valid=True) if args.use_valid_env else None
+    n_groups = len(getattr(env, "env_groups", ()))
+    print(f"rollout: {n_groups} pipelined env groups" if n_groups > 1 else "rollout: serial steps")
     logdir, model_file = create_logdir_train(args.model_file, env_name, args.exp_name, args.seed, f'__rank_{rank}' if world > 1 and rank > 0 else '')
     np.save(os.path.join(logdir, "hyperparameters.npy"), hp)
     print(f'Logging to {logdir}')
