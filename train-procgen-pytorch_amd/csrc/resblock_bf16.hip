@@ -15,14 +15,27 @@
 #include "common.h"
 #include <hip/hip_ext.h>
 #include <mutex>
+#include <type_traits>
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 #define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 __device__ __forceinline__ unsigned short rb_f2bf(float x) { __bf16 h = (__bf16)x; return __builtin_bit_cast(unsigned short, h); }
-__device__ __forceinline__ unsigned rb_relu2(unsigned w) { const unsigned neg = (w >> 15) & 0x00010001u; return w & ~(neg * 0xFFFFu); }
+// ReLU of two packed bf16 as a signed 16-bit max with 0: one v_pk_max_i16.  Every half with its sign bit set (-0 and negative NaNs included)
+// becomes +0, every other half keeps its bits -- the same bits for every input as the shift / mask / multiply form this replaces (4 instructions).
+typedef short rb_s16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned rb_relu2(unsigned w) {
+    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(rb_s16x2, w), (rb_s16x2){0, 0}));
+}
 __device__ __forceinline__ float rb_lane(uint2 w, int r) {          // bf16 element r (0..3) of an 8-byte word, widened
     const unsigned u = (r >> 1) ? w.y : w.x;
     return (r & 1) ? __uint_as_float(u & 0xffff0000u) : __uint_as_float(u << 16);
+}
+// bf16 element r of an 8-byte word is > 0, tested on the bits without widening: the high half of a dword is positive and non-zero <=> the
+// dword as int32 >= 0x10000; the low half is a signed 16-bit compare.  The same truth as rb_lane(w, r) > 0.f for every finite value, +-0 and
+// +-inf (denormals are kept in this build: float_denorm_mode_32 = 3); only a positive NaN, which the float compare calls false, differs.
+__device__ __forceinline__ bool rb_pos(uint2 w, int r) {
+    const unsigned u = (r >> 1) ? w.y : w.x;
+    return (r & 1) ? (int)u >= 0x10000 : (short)(unsigned short)u > (short)0;
 }
 __device__ __forceinline__ uint2 rb_pack(const float (&v)[4]) {
     return (uint2){mi_pk_bf16(v[0], v[1]), mi_pk_bf16(v[2], v[3])};
@@ -76,10 +89,6 @@ struct ResblockArgs {
 };
 
 // one 3x3 conv over a haloed LDS image for up to MTC M tiles (pixel tiles whose LDS base offsets are given)
-typedef short rb_s16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned rb_relu2_max(unsigned w) {      // ReLU of two packed bf16 as a signed 16-bit max with 0 (one v_pk_max_i16)
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(rb_s16x2, w), (rb_s16x2){0, 0}));
-}
 template <class C, int MTC, bool RELU_A = false>
 __device__ __forceinline__ void rb_conv(const unsigned short* s_src, const unsigned short* s_w, const int (&koff)[C::NK], const int (&abase)[MTC],
                                         int i, int kq, f32x4 (&acc)[MTC][C::NB]) {
@@ -96,7 +105,7 @@ __device__ __forceinline__ void rb_conv(const unsigned short* s_src, const unsig
             av[mt] = *(const bf16x8*)(s_src + abase[mt] + koff[m]);
             if (RELU_A) {                                   // the image holds raw values (they also serve as the skip connection)
                 const uint4 u = __builtin_bit_cast(uint4, av[mt]);
-                av[mt] = __builtin_bit_cast(bf16x8, (uint4){rb_relu2_max(u.x), rb_relu2_max(u.y), rb_relu2_max(u.z), rb_relu2_max(u.w)});
+                av[mt] = __builtin_bit_cast(bf16x8, (uint4){rb_relu2(u.x), rb_relu2(u.y), rb_relu2(u.z), rb_relu2(u.w)});
             }
         }
 #pragma unroll
@@ -527,7 +536,7 @@ __global__ __launch_bounds__(512, 2) void resblock_pair32r_bf16_kernel(ResblockP
         bf16x8 av[2][5];
         auto rd = [&](int q, int m) {
             bf16x8 v = *(const bf16x8*)(s_src + org[q] + kq * 8 + koffc(m));
-            if (relu) { const uint4 u = __builtin_bit_cast(uint4, v); v = __builtin_bit_cast(bf16x8, (uint4){rb_relu2_max(u.x), rb_relu2_max(u.y), rb_relu2_max(u.z), rb_relu2_max(u.w)}); }
+            if (relu) { const uint4 u = __builtin_bit_cast(uint4, v); v = __builtin_bit_cast(bf16x8, (uint4){rb_relu2(u.x), rb_relu2(u.y), rb_relu2(u.z), rb_relu2(u.w)}); }
             return v;
         };
 #pragma unroll
@@ -1441,7 +1450,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
     };
     auto relu8 = [](bf16x8 v) {
         const uint4 u = __builtin_bit_cast(uint4, v);
-        return __builtin_bit_cast(bf16x8, (uint4){rb_relu2_max(u.x), rb_relu2_max(u.y), rb_relu2_max(u.z), rb_relu2_max(u.w)});
+        return __builtin_bit_cast(bf16x8, (uint4){rb_relu2(u.x), rb_relu2(u.y), rb_relu2(u.z), rb_relu2(u.w)});
     };
     // weight gradient of one layer over this wave's NR consecutive pixel rows: d = output-gradient tile (row offset d_row), b = RAW input tile
     // RBFULL16D_INTERLEAVE: conv2's weight gradient (phase 1) issues the NEXT item's row DMAs between its MFMA groups, a few per pixel row --
@@ -1491,6 +1500,19 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
     // rows of the first item landed: all but the (NBUF - 2) x rows-per-wave youngest DMAs of this wave
     if (conv_role) rb_wait_vm<(NBUF - 2) * NC>(); else rb_wait_vm<(NBUF - 2) * NWR>();
     rb_raw_barrier();
+    // The item loop is instantiated once per wave role (a generic lambda called with true_type / false_type): with one loop body for both
+    // roles the compiler kept the role-union register array st[] consistent at the back-edge with a copy of all 80 dwords (60 v_mov per
+    // item and wave).  Both instances run the same two barriers per item.
+    // Conv waves: tile t = rw + 4 * mt of a wave starts at pixel 16 * t of the tile = row (rw >> 1) + 2 * mt, column 16 * (rw & 1): every
+    // LDS operand address is a per-lane base (lane0, + the tap offset koff[m] in lk[m]) plus mt * MSTEP, an immediate of the ds_read.
+    static_assert(C::HW == 32 && C::NMT1 % 4 == 0, "tile rows of a conv wave: two image rows per step of four tiles, no ragged last group");
+    constexpr int MSTEP = 2 * C::P * C::S;
+    const int ry0 = rw >> 1, px = (rw & 1) * 16 + i, lane0 = (ry0 * C::P + px) * C::S;
+    int lk[C::NK];
+#pragma unroll
+    for (int m = 0; m < C::NK; ++m) lk[m] = lane0 + koff[m];
+    auto run_items = [&](auto role) {
+    constexpr bool conv_role = decltype(role)::value;
     int b = 0;
     for (int work = blockIdx.x; work < nwork; work += gridDim.x, b = (b + 1 == NBUF ? 0 : b + 1)) {
         const long long img = work / C::TPI; const int ty0 = (work % C::TPI) * C::TH;
@@ -1510,13 +1532,10 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
                 int yb[CG];
 #pragma unroll
                 for (int q = 0; q < CG; ++q) {
-                    const int mt = g0 + q < C::MT1 ? g0 + q : C::MT1 - 1;
-                    int t = rw + 4 * mt; t = t < C::NMT1 ? t : C::NMT1 - 1;            // (a clamped duplicate rewrites the same values)
-                    const int pl = t * 16 + i, px = pl % C::HW, ry = pl / C::HW;
-                    const unsigned short* src = s_x + (ry * C::P + px) * C::S;
-                    yb[q] = (ry * C::P + px + 1) * C::S + kq * 4;
+                    const int mt = g0 + q < C::MT1 ? g0 + q : C::MT1 - 1;                  // (a clamped duplicate rewrites the same values)
+                    yb[q] = lane0 + C::S + kq * 4 + mt * MSTEP;
 #pragma unroll
-                    for (int m = 0; m < C::NK; ++m) av[q][m] = *(const bf16x8*)(src + koff[m]);
+                    for (int m = 0; m < C::NK; ++m) av[q][m] = *(const bf16x8*)(s_x + lk[m] + mt * MSTEP);
                     mk[q] = *(const uint2*)(s_a + yb[q]);
                 }
                 f32x4 acc[CG];
@@ -1530,13 +1549,12 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
                 for (int q = 0; q < CG; ++q) {
                     float v[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = rb_lane(mk[q], r) > 0.f ? acc[q][r] : 0.f;
+                    for (int r = 0; r < 4; ++r) v[r] = rb_pos(mk[q], r) ? acc[q][r] : 0.f;
                     const uint2 raw = rb_pack(v);
                     *(uint2*)(s_y + yb[q]) = raw;
                     if (a.da_out) {
                         const int mt = g0 + q < C::MT1 ? g0 + q : C::MT1 - 1;
-                        int t = rw + 4 * mt; t = t < C::NMT1 ? t : C::NMT1 - 1;
-                        const int pl = t * 16 + i, px = pl % C::HW, ry = pl / C::HW, gy = ty0 - 1 + ry;
+                        const int ry = ry0 + 2 * mt, gy = ty0 - 1 + ry;
                         if (ry >= 1 && ry <= C::TH) *(uint2*)(a.da_out + ((img * C::HW + gy) * C::HW + px) * C::C + kq * 4) = raw;
                     }
                 }
@@ -1557,12 +1575,10 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
                 uint2 mk[CG2], sk[CG2];
 #pragma unroll
                 for (int q = 0; q < CG2; ++q) {
-                    const int pl = (rw + 4 * (g0 + q)) * 16 + i, px = pl % C::HW, oy = pl / C::HW;
-                    const unsigned short* src = s_y + (oy * C::P + px) * C::S;
 #pragma unroll
-                    for (int m = 0; m < C::NK; ++m) av[q][m] = *(const bf16x8*)(src + koff[m]);
-                    mk[q] = *(const uint2*)(s_p + ((oy + 1) * C::P + px + 1) * C::S + kq * 4);
-                    sk[q] = *(const uint2*)(s_x + ((oy + 2) * C::P + px + 1) * C::S + kq * 4);
+                    for (int m = 0; m < C::NK; ++m) av[q][m] = *(const bf16x8*)(s_y + lk[m] + (g0 + q) * MSTEP);
+                    mk[q] = *(const uint2*)(s_p + lane0 + (C::P + 1) * C::S + kq * 4 + (g0 + q) * MSTEP);
+                    sk[q] = *(const uint2*)(s_x + lane0 + (2 * C::P + 1) * C::S + kq * 4 + (g0 + q) * MSTEP);
                 }
                 f32x4 acc[CG2];
 #pragma unroll
@@ -1573,10 +1589,10 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
                     for (int q = 0; q < CG2; ++q) acc[q] = MFMA_BF16(__builtin_bit_cast(bf16x8, st[5 + m]), av[q][m], acc[q]);
 #pragma unroll
                 for (int q = 0; q < CG2; ++q) {
-                    const int pl = (rw + 4 * (g0 + q)) * 16 + i, px = pl % C::HW, oy = pl / C::HW;
+                    const int oy = ry0 + 2 * (g0 + q);
                     float v[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = (rb_lane(mk[q], r) > 0.f ? acc[q][r] : 0.f) + rb_lane(sk[q], r);
+                    for (int r = 0; r < 4; ++r) v[r] = (rb_pos(mk[q], r) ? acc[q][r] : 0.f) + rb_lane(sk[q], r);
                     *(uint2*)(a.dx_out + ((img * C::HW + ty0 + oy) * C::HW + px) * C::C + kq * 4) = rb_pack(v);
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -1589,6 +1605,8 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
         }
         rb_raw_barrier();                                   // everyone is done with this buffer; the other one is complete
     }
+    };
+    if (conv_role) run_items(std::true_type{}); else run_items(std::false_type{});
 #ifdef RBF_TIMING
     if ((tid & 255) == 0) for (int q = 0; q < 4; ++q) atomicAdd(&g_rbf_timing[(tid >> 8) * 4 + q], (unsigned long long)tacc_[q]);
 #endif
@@ -1932,7 +1950,13 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32s_bf16_kernel(RbFul
     // waves may keep live: two separate sets spilled 471 registers).  conv role: st[2m + nb] = B fragment (tap m, output block nb) of
     // conv2's transposed bank, st[18 + 2m + nb] of conv1's.  weight-gradient role: st[2qq + cb] / st[10 + 2qq + cb] = accumulator
     // tiles of conv2 / conv1 for this wave's column qq and output block cb, st[20 + cb] = bias accumulators (rw 2: conv2, rw 3: conv1).
-    constexpr int NT2 = 256, KX2 = (C::NX + NT2 - 1) / NT2, KA2 = (C::NA + NT2 - 1) / NT2;
+    // WHOLE (an item is a whole image, TH == HW): the tile rows outside the image are the same zero rows for every item -- zeroed once
+    // with the column halos, never staged.  Only the image's own HW rows travel: HW * HW * 4 = 1024 words per tensor, exactly 4 per staging
+    // thread, contiguous in HBM, no row tests, no zero words.
+    constexpr bool WHOLE = C::TPI == 1;
+    constexpr int NT2 = 256, NIN = C::HW * C::HW * 4;
+    constexpr int KX2 = WHOLE ? NIN / NT2 : (C::NX + NT2 - 1) / NT2, KA2 = WHOLE ? NIN / NT2 : (C::NA + NT2 - 1) / NT2;
+    static_assert(!WHOLE || NIN % NT2 == 0, "whole words per staging thread");
     constexpr int NST = (22 + KX2 + 2 * KA2) > 36 ? (22 + KX2 + 2 * KA2) : 36;      // 36 fragments (conv role) / 22 accumulators + the prefetch words
     f32x4 st[NST];
     constexpr int QM = 5;
@@ -1957,11 +1981,21 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32s_bf16_kernel(RbFul
     auto koffc = [](int m) { return ((m / 3) * C::P + (m % 3)) * C::S; };
 
     const int nwork = a.n * C::TPI;
-    // Staging (global -> registers one item ahead -> LDS) is the weight-gradient waves' job: their half of st has room for the nine
-    // prefetch words (st[22 .. 30]), the conv waves' half is full of filter fragments.  t2 = thread index among those 256 threads.
+    // Staging (global -> registers one item ahead -> LDS) is the weight-gradient waves' job: their half of st has room for the
+    // prefetch words (st[22 ..]: 12 with whole-image items), the conv waves' half is full of filter fragments.  t2 = thread index among those 256 threads.
     const int t2 = tid - 256;
     auto load = [&](int work) {
         const long long img = work / C::TPI; const int ty0 = (work % C::TPI) * C::TH;
+        if constexpr (WHOLE) {
+            const long long o = img * (C::HW * C::HW * C::C) + t2 * 8;        // word e = t2 + 256 k: pixel e / 4, 8-channel chunk e % 4
+#pragma unroll
+            for (int k = 0; k < KX2; ++k) {
+                st[22 + k] = __builtin_bit_cast(f32x4, *(const uint4*)(a.dy + o + k * NT2 * 8));
+                st[22 + KX2 + k] = __builtin_bit_cast(f32x4, *(const uint4*)(a.a_fwd + o + k * NT2 * 8));
+                st[22 + KX2 + KA2 + k] = __builtin_bit_cast(f32x4, *(const uint4*)(a.x_fwd + o + k * NT2 * 8));
+            }
+            return;
+        }
 #pragma unroll
         for (int k = 0; k < KX2; ++k) {
             const int e = t2 + k * NT2;
@@ -1981,28 +2015,39 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32s_bf16_kernel(RbFul
         }
     };
     // one pixel step (32 pixels) of a layer's weight gradient: d = the layer's output-gradient tile, src = its (ReLU'd) input tile
-    auto wg_step = [&](int t, const unsigned short* s_d, int d_off, const unsigned short* s_src, const int a0, bool bias) {
-        int orow[2];
+    const int orow0 = ((kq >> 1) * C::P + 4 * (kq & 1) + rq) * C::S + 4 * cp;      // this lane's first operand row of step 0 (computed once)
+    // A layer's operand bases are made once per phase (wg_bases: the tile's own LDS offset folded in, then opaque to the compiler, which would
+    // otherwise share one base between the phases and add the tiles' distance -- beyond the 64 KB a ds_read immediate reaches -- at every read);
+    // every read of every step is then base + immediate.
+    struct WgBase { int d, b[QM]; };
+    auto wg_bases = [&](const unsigned short* s_d, int d_off, const unsigned short* s_src) {
+        WgBase w;
+        w.d = (int)(s_d - smem_h) + orow0 + d_off;
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int pl = 32 * t + 16 * (kq >> 1) + 8 * h + 4 * (kq & 1) + rq;
-            orow[h] = ((pl / C::HW) * C::P + pl % C::HW) * C::S + 4 * cp;
+        for (int qq = 0; qq < QM; ++qq) {
+            const int q = rw + 4 * (qq < 4 ? qq : (qcnt > 4 ? 4 : 0)), tap = q >> 1, ib = q & 1;
+            w.b[qq] = (int)(s_src - smem_h) + orow0 + ((tap / 3) * C::P + (tap % 3)) * C::S + ib * 16;
+            asm volatile("" : "+v"(w.b[qq]));
         }
-        auto tr = [&](const unsigned short* base, int off) {
-            const rb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(base + orow[0] + off));
-            const rb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(base + orow[1] + off));
+        asm volatile("" : "+v"(w.d));
+        return w;
+    };
+    auto wg_step = [&](int t, const WgBase& w, const int a0, bool bias) {
+        // pixel 32 t + c of the tile (c < 32: this lane's two operand rows, c and c + 8) lies in row 2 t + (c >> 4), column c & 15: the
+        // address is affine in t, and the second row is the first + 8 pixels
+        auto tr = [&](int base, int off) {
+            const unsigned short* p = smem_h + base + t * (2 * C::P * C::S) + off;
+            const rb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)p);
+            const rb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(p + 8 * C::S));
             return (bf16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
         };
         // all operand reads of the step go out before its first MFMA: with one column's read in flight the MFMA stream runs at the
         // LDS latency (200+ cycles with eight waves on the pipe) instead of 32 cycles per column
         bf16x8 d[2], b[QM];
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) d[cb] = tr(s_d, d_off + cb * 16);
+        for (int cb = 0; cb < 2; ++cb) d[cb] = tr(w.d, cb * 16);
 #pragma unroll
-        for (int qq = 0; qq < QM; ++qq) {
-            const int q = rw + 4 * (qq < 4 ? qq : (qcnt > 4 ? 4 : 0)), tap = q >> 1, ib = q & 1;
-            b[qq] = tr(s_src, ((tap / 3) * C::P + (tap % 3)) * C::S + ib * 16);
-        }
+        for (int qq = 0; qq < QM; ++qq) b[qq] = tr(w.b[qq], 0);
         asm volatile("" ::: "memory");
         if (bias) { st[20] = MFMA_BF16(d[0], ones, st[20]); st[21] = MFMA_BF16(d[1], ones, st[21]); }
 #pragma unroll
@@ -2018,7 +2063,17 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32s_bf16_kernel(RbFul
         const long long img = work / C::TPI; const int ty0 = (work % C::TPI) * C::TH;
         __syncthreads();
         RTCK(3);                                            // phase-2 work + wait at the top barrier
-        if (!conv_role) {
+        if (!conv_role && WHOLE) {
+            const int o = ((t2 >> 6) * C::P + ((t2 >> 2) & (C::HW - 1)) + 1) * C::S + (t2 & 3) * 8;      // image row e / 64 -> tile row + 2 (s_x) / + 1 (s_a, s_p)
+#pragma unroll
+            for (int k = 0; k < KX2; ++k) {
+                const int ok = o + k * (NT2 / 64) * C::P * C::S;
+                const uint4 va = __builtin_bit_cast(uint4, st[22 + KX2 + k]), vp = __builtin_bit_cast(uint4, st[22 + KX2 + KA2 + k]);
+                *(uint4*)(s_x + ok + 2 * C::P * C::S) = __builtin_bit_cast(uint4, st[22 + k]);
+                *(uint4*)(s_a + ok + C::P * C::S) = (uint4){rb_relu2(va.x), rb_relu2(va.y), rb_relu2(va.z), rb_relu2(va.w)};
+                *(uint4*)(s_p + ok + C::P * C::S) = (uint4){rb_relu2(vp.x), rb_relu2(vp.y), rb_relu2(vp.z), rb_relu2(vp.w)};
+            }
+        } else if (!conv_role) {
 #pragma unroll
             for (int k = 0; k < KX2; ++k) {
                 const int e = t2 + k * NT2;
@@ -2064,7 +2119,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32s_bf16_kernel(RbFul
                     const uint2 mk = nb ? mk1 : mk0;
                     float v[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = rb_lane(mk, r) > 0.f ? acc[nb][r] : 0.f;
+                    for (int r = 0; r < 4; ++r) v[r] = rb_pos(mk, r) ? acc[nb][r] : 0.f;
                     const uint2 raw = rb_pack(v);
                     *(uint2*)(s_y + yb + nb * 16) = raw;
                     if (a.da_out) {
@@ -2075,8 +2130,9 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32s_bf16_kernel(RbFul
             }
         } else {
             // ---- conv2's weight / bias gradient from (dy, relu(a)): needs nothing the conv waves are producing
-#pragma unroll 4                                             // (16-row items have 8 steps: unrolled by 8 the kernel spills -- hoisted operand addresses)
-            for (int t = 0; t < C::NSTEP; ++t) wg_step(t, s_x, (2 * C::P + 1) * C::S, s_a, 0, rw == 2);
+            const WgBase wb = wg_bases(s_x, (2 * C::P + 1) * C::S, s_a);
+#pragma unroll
+            for (int t = 0; t < C::NSTEP; ++t) wg_step(t, wb, 0, rw == 2);
         }
         RTCK(1);                                            // phase-1 work
         __syncthreads();
@@ -2106,14 +2162,15 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32s_bf16_kernel(RbFul
                     const uint2 mk = nb ? mk1 : mk0, sk = nb ? sk1 : sk0;
                     float v[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = (rb_lane(mk, r) > 0.f ? acc[nb][r] : 0.f) + rb_lane(sk, r);
+                    for (int r = 0; r < 4; ++r) v[r] = (rb_pos(mk, r) ? acc[nb][r] : 0.f) + rb_lane(sk, r);
                     *(uint2*)(a.dx_out + ((img * C::HW + ty0 + oy) * C::HW + px) * C::C + nb * 16 + kq * 4) = rb_pack(v);
                 }
             }
         } else {
             // ---- conv1's weight / bias gradient from (da, relu(x))
-#pragma unroll 4
-            for (int t = 0; t < C::NSTEP; ++t) wg_step(t, s_y, (C::P + 1) * C::S, s_p, 10, rw == 3);
+            const WgBase wb = wg_bases(s_y, (C::P + 1) * C::S, s_p);
+#pragma unroll
+            for (int t = 0; t < C::NSTEP; ++t) wg_step(t, wb, 10, rw == 3);
         }
     }
 #ifdef WG_TIMING
@@ -2219,27 +2276,39 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32q_bf16_kernel(RbFul
             st[22 + 2 * C::KW + k] = __builtin_bit_cast(f32x4, *(const uint4*)(a.x_fwd + o));
         }
     };
-    // one pixel step (32 pixels = half an image) of a layer's weight gradient, operands as in the 16x16 kernel.  The step loops below are
-    // unrolled by 4, not 8: fully unrolled, the compiler hoists every step's operand addresses out of the item loop and 54 registers
-    // spill (rolled 56.9, by 2 54.4, by 4 53.8 us per 8192 images).  Issuing the reads of step t + 1 before the MFMAs of step t by hand:
-    // 59.6 us -- the phases do not wait for these reads.
-    auto wg_step = [&](int t, const unsigned short* s_d, const unsigned short* s_src, const int a0, bool bias) {
-        int orow[2];
+    // one pixel step (32 pixels = half an image) of a layer's weight gradient, operands as in the 16x16 kernel: per phase one base per
+    // operand (wg_bases, the tile's own LDS offset folded in and opaque to the compiler), every read of every step base + immediate, the
+    // eight steps unrolled.  (With the addresses rebuilt per step the full unroll hoisted them all and spilled 54 registers: rolled
+    // 56.9, by 2 54.4, by 4 53.8 us per 8192 images.  Issuing the reads of step t + 1 before the MFMAs of step t by hand: 59.6 us --
+    // the phases do not wait for these reads.)
+    const int orow0 = porg(16 * (kq >> 1) + 4 * (kq & 1) + rq) + 4 * cp;       // this lane's first operand row of step 0
+    struct WgBase { int d, b[QM]; };
+    auto wg_bases = [&](const unsigned short* s_d, const unsigned short* s_src) {
+        WgBase w;
+        w.d = (int)(s_d - smem_h) + orow0 + CENTER;
 #pragma unroll
-        for (int h = 0; h < 2; ++h) orow[h] = porg(32 * t + 16 * (kq >> 1) + 8 * h + 4 * (kq & 1) + rq) + 4 * cp;
-        auto tr = [&](const unsigned short* base, int off) {
-            const rb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(base + orow[0] + off));
-            const rb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(base + orow[1] + off));
+        for (int qq = 0; qq < QM; ++qq) {
+            const int q = rw + 4 * (qq < 4 ? qq : (qcnt > 4 ? 4 : 0)), tap = q >> 1, ib = q & 1;
+            w.b[qq] = (int)(s_src - smem_h) + orow0 + koffc(tap) + ib * 16;
+            asm volatile("" : "+v"(w.b[qq]));
+        }
+        asm volatile("" : "+v"(w.d));
+        return w;
+    };
+    auto wg_step = [&](int t, const WgBase& w, const int a0, bool bias) {
+        // pixel 32 t + c of the item (c < 32: this lane's two operand rows, c and c + 8): image t >> 1, row 4 (t & 1) + (c >> 3), column c & 7.
+        // The step only adds a constant to the lane's base, and the second row is the tile row below the first.
+        auto tr = [&](int base, int off) {
+            const unsigned short* p = smem_h + base + ((t >> 1) * C::R + 4 * (t & 1)) * C::P * C::S + off;
+            const rb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)p);
+            const rb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(p + C::P * C::S));
             return (bf16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
         };
         bf16x8 d[2], b[QM];
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) d[cb] = tr(s_d, CENTER + cb * 16);
+        for (int cb = 0; cb < 2; ++cb) d[cb] = tr(w.d, cb * 16);
 #pragma unroll
-        for (int qq = 0; qq < QM; ++qq) {
-            const int q = rw + 4 * (qq < 4 ? qq : (qcnt > 4 ? 4 : 0)), tap = q >> 1, ib = q & 1;
-            b[qq] = tr(s_src, koffc(tap) + ib * 16);
-        }
+        for (int qq = 0; qq < QM; ++qq) b[qq] = tr(w.b[qq], 0);
         asm volatile("" ::: "memory");
         if (bias) { st[20] = MFMA_BF16(d[0], ones, st[20]); st[21] = MFMA_BF16(d[1], ones, st[21]); }
 #pragma unroll
@@ -2297,7 +2366,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32q_bf16_kernel(RbFul
                     const uint2 mk = nb ? mk1 : mk0;
                     float v[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = rb_lane(mk, r) > 0.f ? acc[nb][r] : 0.f;
+                    for (int r = 0; r < 4; ++r) v[r] = rb_pos(mk, r) ? acc[nb][r] : 0.f;
                     const uint2 raw = rb_pack(v);
                     *(uint2*)(s_y + yb + nb * 16) = raw;
                     if (a.da_out) {
@@ -2308,8 +2377,9 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32q_bf16_kernel(RbFul
             }
         } else {
             // ---- conv2's weight / bias gradient from (dy, relu(a))
-#pragma unroll 4
-            for (int t = 0; t < C::NSTEP; ++t) wg_step(t, s_x, s_a, 0, rw == 2);
+            const WgBase wb = wg_bases(s_x, s_a);
+#pragma unroll
+            for (int t = 0; t < C::NSTEP; ++t) wg_step(t, wb, 0, rw == 2);
         }
         RTCK(1);
         __syncthreads();
@@ -2340,15 +2410,16 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32q_bf16_kernel(RbFul
                         const uint2 mk = nb ? mk1 : mk0, sk = nb ? sk1 : sk0;
                         float v[4];
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = (rb_lane(mk, r) > 0.f ? acc[nb][r] : 0.f) + rb_lane(sk, r);
+                        for (int r = 0; r < 4; ++r) v[r] = (rb_pos(mk, r) ? acc[nb][r] : 0.f) + rb_lane(sk, r);
                         *(uint2*)(a.dx_out + ((long long)img0 * 64 + pl) * C::C + nb * 16 + kq * 4) = rb_pack(v);
                     }
                 }
             }
         } else {
             // ---- conv1's weight / bias gradient from (da, relu(x))
-#pragma unroll 4
-            for (int t = 0; t < C::NSTEP; ++t) wg_step(t, s_y, s_p, 10, rw == 3);
+            const WgBase wb = wg_bases(s_y, s_p);
+#pragma unroll
+            for (int t = 0; t < C::NSTEP; ++t) wg_step(t, wb, 10, rw == 3);
         }
     }
 #ifdef WG_TIMING
