@@ -187,6 +187,29 @@ int mi_minibatch_multi(mi_ctx* ctx, const int64_t* idx, int32_t n_idx, const int
 int mi_optimizer_step(mi_ctx* ctx, float lr, float max_grad_norm, int32_t adam_step, float* grad_norm_out);
 int mi_loss_log_read(mi_ctx* ctx, float* out, int32_t max_records, int32_t* n_records, int32_t reset);
 
+/* ---- training the recurrence (algo: ppo-pure, agents/ppo_pure.py:98-176: optimize() calls policy(obs, hidden_state, mask), which for a
+ *      recurrent policy is the training branch of GRU.forward, common/model.py:226-277 -- the hidden state is recomputed over the whole
+ *      trajectory of the minibatch's envs and the gradient flows back through time).  Single GPU; the GRU arithmetic is fp32 in both
+ *      precision modes.  Off (the default, algo: ppo, agents/ppo.py:125-128) the GRU stays frozen and nothing here changes a number.
+ *      mi_gru_train(1) (after mi_set_gru; width a multiple of 64 in [64, 512]) allocates the GRU's gradient and Adam moments -- one
+ *      vector {weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0} of 2 * 3H^2 + 2 * 3H floats, beside the flat vectors (mi_param_count
+ *      does not change).  From then on mi_optimizer_step clips by the global norm over the flat AND the GRU gradients (one coefficient,
+ *      clip_grad_norm_(policy.parameters()), ppo_pure.py:160), reports that norm, steps Adam on both and zeroes both; mi_copy_params from
+ *      such a context also copies the GRU weights (the destination needs mi_set_gru).
+ *      mi_minibatch_rec: one recurrent minibatch (ppo_pure.py:121-156 with Storage.fetch_train_generator(recurrent=True),
+ *      common/storage.py:93-110) = the n_env envs of env_idx x all T steps, rows time-major; h0 = hidden_states_batch[0, envs] (n_env x H);
+ *      the mask of step t is 1 - done[t, e], the done stored WITH step t (ppo_pure.py:124), where the rollout masks with the done of step
+ *      t - 1.  n_env * T <= max_batch; n_global as in mi_minibatch; fs_coef must be 0 (ppo-pure has no such term); multirank modes 1 / 2
+ *      and the in-library gradient exchange are refused.  Gradients accumulate until mi_optimizer_step; one loss-log record per call.
+ *      mi_get_gru / mi_get_gru_grads read the weights / accumulated gradients in nn.GRU's layout; the Adam moments travel as the one
+ *      vector above (n = 2 * 3H^2 + 2 * 3H). */
+int mi_gru_train(mi_ctx* ctx, int32_t enabled);
+int mi_minibatch_rec(mi_ctx* ctx, const int64_t* env_idx, int32_t n_env, const float* h0 /* n_env x H */, int32_t n_global, const mi_hparams* hp);
+int mi_get_gru(mi_ctx* ctx, float* w_ih, float* w_hh, float* b_ih, float* b_hh);
+int mi_get_gru_grads(mi_ctx* ctx, float* w_ih, float* w_hh, float* b_ih, float* b_hh);
+int mi_get_gru_adam_state(mi_ctx* ctx, float* exp_avg, float* exp_avg_sq, int64_t n);
+int mi_set_gru_adam_state(mi_ctx* ctx, const float* exp_avg, const float* exp_avg_sq, int64_t n);
+
 /* ---- data-parallel collectives inside the boundary: RCCL over xGMI, one communicator per context (SURVEY 8(b) mi_allreduce_grads,
  *      8(e) C1-C3).  Rank 0 obtains a 128-byte id (mi_comm_unique_id) and hands it to every rank by any host channel
  *      (mi355/dist.py uses torch.distributed.broadcast_object_list); every rank then calls mi_comm_init(id, rank, world).
@@ -257,7 +280,8 @@ int mi_op_gemm(mi_ctx* ctx, int32_t M, int32_t N, int32_t K, const float* A, int
                const float* B, int64_t sbk, int64_t sbn, float* C);
 int mi_selftest_mfma(mi_ctx* ctx, float* max_err);
 /* what the last mi_minibatch left in the activation buffers (first n samples), fp32 NHWC: which = 8 * block + k, k = 0 pooled map,
- * 1 res1.conv1 out, 2 res1 out, 3 res2.conv1 out, 4 block out, 5 max-pool arg-max (window position ky*3+kx); which = 100: features.
+ * 1 res1.conv1 out, 2 res1 out, 3 res2.conv1 out, 4 block out, 5 max-pool arg-max (window position ky*3+kx); which = 100: features
+ * (after mi_minibatch_rec: the embedder output x; 101 = h_t, 102 = dX of that pass).
  * Lets a parity test run the oracle's backward pass on the ENGINE's forward tensors (teacher forcing, tests/test_gpu_bf16.py). */
 int mi_debug_read(mi_ctx* ctx, int32_t which, int32_t n, float* out);
 /* The production sampler's generator (dist.sample() of agents/ppo.py:77 is torch's; here Philox4x32-10 keyed by (seed, t*E + e)):
@@ -269,6 +293,13 @@ int mi_debug_philox(mi_ctx* ctx, const uint32_t* ctr_key6, int32_t n, uint32_t* 
  * be NULL) = the kernel's second copy of h' (the hidden ring's next slot in the rollout) */
 int mi_debug_gru_step(mi_ctx* ctx, int32_t n, int32_t H, const float* x, const float* h, const float* done, const float* w_ih,
                       const float* w_hh, const float* b_ih, const float* b_hh, float* h_out, float* h_copy);
+/* test hook: the GRU over a trajectory (the sequential kernels of mi_minibatch_rec and the GEMMs around them; GRU.forward's training branch,
+ * common/model.py:226-277, and its autograd) on caller data -- n envs x T steps, rows time-major (row t * n + i), width H (a multiple of 64 in
+ * [64, 512], independent of the context's); x: T*n x H, h0: n x H, mask: T*n (multiplies the state that enters step t), weights in nn.GRU's
+ * layout.  out_h = h_t of all rows.  dOut (T*n x H = dL/dh_t, or NULL: forward only) -> dX (T*n x H), dW_ih, dW_hh (3H x H), db_ih, db_hh (3H). */
+int mi_debug_gru_seq(mi_ctx* ctx, int32_t T, int32_t n, int32_t H, const float* x, const float* h0, const float* mask, const float* w_ih,
+                     const float* w_hh, const float* b_ih, const float* b_hh, const float* dOut, float* out_h, float* dX, float* dW_ih,
+                     float* dW_hh, float* db_ih, float* db_hh);
 /* measurement hook: wall-clock microseconds per policy step of slot t (the step's launches + a stream wait, `iters` times), issued
  * eagerly (mode 0) or as one replay of a hipGraph captured from the same launches (mode 1) */
 int mi_debug_step_latency(mi_ctx* ctx, int32_t t, int32_t iters, int32_t mode, float* us_out);

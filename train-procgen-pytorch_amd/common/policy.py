@@ -34,6 +34,7 @@ class CategoricalPolicy(nn.Module):
             self.gru = GRU(embedder.output_dim, embedder.output_dim)
         object.__setattr__(self, "engine", None)
         object.__setattr__(self, "_device_is_newer", False)
+        object.__setattr__(self, "_gru_trained", False)
         self.device = None
         embedder._bind(self)
 
@@ -68,6 +69,18 @@ class CategoricalPolicy(nn.Module):
             g = self.gru.gru
             engine.set_gru(*(t.detach().cpu().numpy() for t in (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0)))
 
+    def enable_gru_training(self):
+        """algo ppo-pure: the GRU becomes a trained parameter set on the device (mi_gru_train).  From here on state_dict() pulls it like
+        the flat parameters, and the optimiser's state covers its four tensors (mi355/optim.py)."""
+        if not self.recurrent:
+            raise ValueError("enable_gru_training: the policy is not recurrent")
+        self.engine.gru_train(True)
+        object.__setattr__(self, "_gru_trained", True)
+
+    def gru_parameters(self):
+        g = self.gru.gru
+        return [g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0]
+
     def sync_to_device(self):
         self.engine.set_params(layout.flatten(self.param_shapes(), self._host_tensors()))
         object.__setattr__(self, "_device_is_newer", False)
@@ -80,6 +93,9 @@ class CategoricalPolicy(nn.Module):
         with torch.no_grad():
             for k, v in fresh.items():
                 own[k].copy_(torch.from_numpy(v))
+            if self._gru_trained:
+                for p, v in zip(self.gru_parameters(), self.engine.get_gru()):
+                    p.copy_(torch.from_numpy(v))
         object.__setattr__(self, "_device_is_newer", False)
 
     def mark_device_updated(self):

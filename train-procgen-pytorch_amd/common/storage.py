@@ -191,6 +191,22 @@ class Storage:
                 envs = perm[s:s + per].astype(np.int64)
                 yield (np.arange(T, dtype=np.int64)[:, None] * E + envs[None, :]).reshape(-1)
 
+    def recurrent_minibatch_stream(self, mini_batch_size=None, n_envs_global=None):
+        """(envs, h0) of each recurrent minibatch of one epoch: the env group and hidden_states_batch[0, envs] (storage.py:93-110; a
+        minibatch is these envs x all T steps, time-major).  Consumes the global torch CPU generator exactly like
+        minibatch_index_stream(recurrent=True): ONE torch.randperm(E), envs in consecutive groups of E // (N // B)."""
+        E = self.num_envs if n_envs_global is None else n_envs_global
+        N = self.num_steps * E
+        B = N if mini_batch_size is None else mini_batch_size
+        ahead, self._perm_ahead = self._perm_ahead, None
+        perm = ahead.take(E) if ahead is not None else None
+        if perm is None:
+            perm = _randperm_serial(E)
+        per = E // (N // B)
+        for s in range(0, E, per):
+            envs = perm[s:s + per].astype(np.int64)
+            yield envs, np.ascontiguousarray(self._hidden[0, envs], dtype=np.float32)
+
     def draw_permutation_ahead(self, n):
         """Start drawing the next update's first torch.randperm(n) now (see _PermutationAhead): call when nothing else will use torch's
         CPU generator until that update -- PPO.train does, right after an iteration's logging."""

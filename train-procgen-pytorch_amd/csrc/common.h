@@ -228,6 +228,16 @@ void launch_gru_gates(const float* gi, const float* gh, const float* hm, float* 
 void launch_gru_step(const float* x, const float* h_in, const float* done, const float* w_ih, const float* w_hh, const float* b_ih,
                      const float* b_hh, float* h_out, float* h_copy, int n, int H, hipStream_t st);
 
+// GRU over a trajectory (gru_seq.hip): n envs x T steps, rows time-major (t*n + i), H a multiple of 64 in [64, 512].  gi = W_ih x + b_ih of all
+// rows; mask[t*n + i] multiplies the state that enters step t; sv (may be null: inference) = [T*n][4][H] r, z, n, gh_n for the backward pass.
+bool gru_seq_width_ok(int H);
+void launch_gru_seq_mask(const float* done, const int32_t* idx, float* mask, int N, hipStream_t st);      // mask[k] = 1 - done[idx[k]]
+void launch_gru_seq_fwd(const float* gi, const float* h0, const float* mask, const float* w_hh, const float* b_hh, float* out_h, float* sv, int T, int n, int H,
+                        hipStream_t st);
+// dout = dL/dh_t of all rows -> dgi, dgh ([T*n][3H]: gradients of the two gate pre-activation products) and hm ([T*n][H]: the masked input states)
+void launch_gru_seq_bwd(const float* dout, const float* out_h, const float* h0, const float* mask, const float* sv, const float* w_hh, float* dgi, float* dgh,
+                        float* hm_out, int T, int n, int H, hipStream_t st);
+
 // ---------------------------------------------------------------- embedder.fc on the bf16 matrix cores (fc_bf16.hip)
 // IMPALA embedder widths (output_dim): the multiples of 64 in [64, 512] (mi_create).  The bf16 fc kernels and the fc section of
 // repack_all_kernel are templates on the width; this maps a run-time width onto F<D>::run(args...) and returns false for any other.

@@ -186,6 +186,12 @@ struct mi_ctx {
     // mi_rec_begin, slot t+1 written by step t's fused cell); pinned staging of mi_rec_begin's upload {hidden [E][H], done [E]} and the event
     // that frees it; g_rec_ok[g]: mi_rec_begin has run since group g last started a rollout (t == 0)
     float *h_ring, *h_rec_stage; hipEvent_t ev_rec; bool g_rec_ok[MAX_GROUPS];
+    // GRU training (mi_gru_train, mi_minibatch_rec: algo ppo-pure): gradients and Adam moments of the four GRU tensors as ONE vector
+    // {w_ih, w_hh, b_ih, b_hh} beside the flat ones, the partial sums of the global gradient norm (128 flat + 128 GRU), and the buffers of a
+    // recurrent minibatch pass, max_batch rows each: the embedder output x (the sequence forward overwrites feat with h_t), gi, the saved
+    // gates, dgi / dgh, the masked input states, the masks 1 - done and the minibatch's initial states
+    bool gru_train, rec_last; float *gru_g, *gru_m, *gru_v; double* gru_sumsq;
+    float *rec_x, *rec_gi, *rec_sv, *rec_dgi, *rec_dgh, *rec_hm, *rec_mask, *rec_h0;
 };
 
 // ------------------------------------------------------------------------------------------ layout tables
@@ -461,6 +467,8 @@ int mi_create(const mi_config* cfg, mi_ctx** out) {
     c->gru_x = c->gru_dg = nullptr; c->sal_keep_x = c->bwd_from_dfeat = false;
     c->gru_on = false; c->gru_wih = c->gru_whh = c->gru_bih = c->gru_bhh = c->h_state = c->h_masked = c->gru_gi = c->gru_gh = c->d_done = nullptr;
     c->h_ring = c->h_rec_stage = nullptr; c->ev_rec = nullptr; for (bool& b : c->g_rec_ok) b = false;
+    c->gru_train = c->rec_last = false; c->gru_g = c->gru_m = c->gru_v = nullptr; c->gru_sumsq = nullptr;
+    c->rec_x = c->rec_gi = c->rec_sv = c->rec_dgi = c->rec_dgh = c->rec_hm = c->rec_mask = c->rec_h0 = nullptr;
     HIPC(hipDeviceSynchronize());
     *out = c;
     return 0;
@@ -496,6 +504,8 @@ int mi_destroy(mi_ctx* c) {
     hipFree(c->stats_ring); hipFree(c->fs_ring); hipFree(c->fs_parts); if (c->d_slab_desc) hipFree(c->d_slab_desc); if (c->sal_dc) hipFree(c->sal_dc); if (c->sal_dx) hipFree(c->sal_dx); hipFree(c->d_pack); hipFree(c->d_rd); hipHostFree(c->h_pack); hipHostFree(c->h_rd); hipFree(c->d_done_ctr); if (c->side_stream) hipStreamDestroy(c->side_stream); hipEventDestroy(c->ev_side_fork); hipEventDestroy(c->ev_side_join); hipHostFree(c->h_flag);
     { float* gr[] = {c->gru_wih, c->gru_whh, c->gru_bih, c->gru_bhh, c->h_state, c->h_masked, c->gru_gi, c->gru_gh, c->d_done, c->gru_x, c->gru_dg}; for (float* q : gr) if (q) hipFree(q); }
     if (c->h_ring) hipFree(c->h_ring); if (c->h_rec_stage) hipHostFree(c->h_rec_stage); if (c->ev_rec) hipEventDestroy(c->ev_rec);
+    { float* gt[] = {c->gru_g, c->gru_m, c->gru_v, c->rec_x, c->rec_gi, c->rec_sv, c->rec_dgi, c->rec_dgh, c->rec_hm, c->rec_mask, c->rec_h0}; for (float* q : gt) if (q) hipFree(q); }
+    if (c->gru_sumsq) hipFree(c->gru_sumsq);
     hipFree(c->act); hipFree(c->adv_stats); hipFree(c->d_idx); hipFree(c->sumsq);
     if (c->fs_colmax) hipFree(c->fs_colmax); if (c->fs_arg) hipFree(c->fs_arg);
     if (c->fs_keys) hipFree(c->fs_keys); if (c->fs_keys_local) hipFree(c->fs_keys_local); if (c->d_gpos) hipFree(c->d_gpos); if (c->h_gpos) hipHostFree(c->h_gpos);
@@ -541,6 +551,14 @@ int mi_copy_params(mi_ctx* dst, mi_ctx* src) {
     HIPC(hipEventRecord(ready, src->stream));                      // the optimizer step that wrote src's parameters
     HIPC(hipStreamWaitEvent(dst->stream, ready, 0));
     HIPC(hipMemcpyAsync(dst->params, src->params, (size_t)src->n_params * 4, hipMemcpyDeviceToDevice, dst->stream));
+    if (src->gru_train) {          // a trained GRU is part of the policy: the twin acts with the weights the optimizer just wrote
+        if (!dst->gru_on) { hipEventDestroy(ready); hipEventDestroy(done); return fail(-1, "invalid argument: the source trains its GRU but the destination has none (mi_set_gru)"); }
+        const size_t H = src->H;
+        HIPC(hipMemcpyAsync(dst->gru_wih, src->gru_wih, 3 * H * H * 4, hipMemcpyDeviceToDevice, dst->stream));
+        HIPC(hipMemcpyAsync(dst->gru_whh, src->gru_whh, 3 * H * H * 4, hipMemcpyDeviceToDevice, dst->stream));
+        HIPC(hipMemcpyAsync(dst->gru_bih, src->gru_bih, 3 * H * 4, hipMemcpyDeviceToDevice, dst->stream));
+        HIPC(hipMemcpyAsync(dst->gru_bhh, src->gru_bhh, 3 * H * 4, hipMemcpyDeviceToDevice, dst->stream));
+    }
     HIPC(hipEventRecord(done, dst->stream));
     HIPC(hipStreamWaitEvent(src->stream, done, 0));                // src's next optimizer step must not overtake the copy
     dst->fc_packed_valid = false;                                  // packed bf16 filter images are rebuilt before dst's next pass
@@ -1635,6 +1653,7 @@ static int minibatch_impl(mi_ctx* c, const int64_t* idx, int32_t n, const int32_
     InputSrc src = minibatch_src(c);
     c->prof.phase = 1;
     c->prof.sample_now = (c->prof.mb_count++ % c->prof.period) == 0;
+    c->rec_last = false;
     net_forward(c, src, n, false, true, true);
     const bool impala = c->cfg.arch == MI_ARCH_IMPALA;
     LossArgs a{};
@@ -1746,9 +1765,24 @@ int mi_optimizer_step(mi_ctx* c, float lr, float max_norm, int32_t step, float* 
     const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
     if (c->ar_inflight) { HIPC(hipStreamWaitEvent(c->stream, c->ev_ar_done, 0)); c->ar_inflight = false; }
     c->ar_issued = false; c->ar_armed = false;
+    if (c->gru_train) {
+        // clip_grad_norm_(policy.parameters()) with the GRU among the parameters (agents/ppo_pure.py:160): ONE norm over the flat and the GRU
+        // gradients -- 128 partial sums each, every Adam launch adds up all 256 -- and one coefficient for both; same Adam, both zeroed
+        const size_t H = c->H, W = 3 * H * H, B = 3 * H;
+        launch_sumsq_partials(c->grads, c->n_params, c->gru_sumsq, c->stream);
+        launch_sumsq_partials(c->gru_g, (long long)(2 * W + 2 * B), c->gru_sumsq + 128, c->stream);
+        launch_adam(c->params, c->grads, c->adam_m, c->adam_v, c->n_params, c->gru_sumsq, 256, max_norm, lr, (float)b1, (float)b2, 1e-5f,
+                    step_size, bc2_sqrt, c->gnorm, c->stream);
+        float* gw[4] = {c->gru_wih, c->gru_whh, c->gru_bih, c->gru_bhh};
+        const size_t off[4] = {0, W, 2 * W, 2 * W + B}, len[4] = {W, W, B, B};
+        for (int k = 0; k < 4; ++k)
+            launch_adam(gw[k], c->gru_g + off[k], c->gru_m + off[k], c->gru_v + off[k], (long long)len[k], c->gru_sumsq, 256, max_norm, lr, (float)b1,
+                        (float)b2, 1e-5f, step_size, bc2_sqrt, nullptr, c->stream);
+    } else {
     launch_sumsq_partials(c->grads, c->n_params, c->sumsq + 2, c->stream);          // 128 partial sums; the Adam kernel's waves add them up themselves
     launch_adam(c->params, c->grads, c->adam_m, c->adam_v, c->n_params, c->sumsq + 2, 128, max_norm, lr, (float)b1, (float)b2, 1e-5f,
                 step_size, bc2_sqrt, c->gnorm, c->stream);
+    }
     c->fc_packed_valid = false;
     HIPC(hipGetLastError()); NETCHK(c);
     if (gnorm_out) {
@@ -1756,6 +1790,130 @@ int mi_optimizer_step(mi_ctx* c, float lr, float max_norm, int32_t step, float* 
         HIPC(hipStreamSynchronize(c->stream));
         *gnorm_out = c->h_f[0];
     }
+    return 0;
+}
+
+
+// ------------------------------------------------------------------------------------------ GRU training (algo: ppo-pure)
+// PPOPure.optimize of a recurrent policy (agents/ppo_pure.py:98-176; the training branch of GRU.forward, common/model.py:226-277): the
+// hidden state is recomputed over the whole trajectory of the minibatch's envs and the gradient runs back through time into the GRU's
+// four tensors.  They live beside the flat vector: their gradients and Adam moments are one vector {w_ih, w_hh, b_ih, b_hh} of
+// 2 * 3H^2 + 2 * 3H floats.  Single rank, fp32 GRU arithmetic in both precision modes.
+static int64_t gru_count(const mi_ctx* c) { return 2 * (int64_t)3 * c->H * c->H + 2 * (int64_t)3 * c->H; }
+int mi_gru_train(mi_ctx* c, int32_t enabled) {
+    ARG(c, "null"); JOIN(c); ARG(c->gru_on, "no GRU set: call mi_set_gru first");
+    ARG(!enabled || gru_seq_width_ok(c->H), "GRU training needs a width (out_dim) that is a multiple of 64 in [64, 512]");
+    if (enabled && !c->gru_g) {
+        const size_t G = (size_t)gru_count(c), NB = c->NB, H = c->H;
+        HIPC(dalloc(&c->gru_g, G)); HIPC(dalloc(&c->gru_m, G)); HIPC(dalloc(&c->gru_v, G)); HIPC(dalloc(&c->gru_sumsq, (size_t)256));
+        HIPC(dalloc(&c->rec_x, NB * H)); HIPC(dalloc(&c->rec_gi, NB * 3 * H)); HIPC(dalloc(&c->rec_sv, NB * 4 * H));
+        HIPC(dalloc(&c->rec_dgi, NB * 3 * H)); HIPC(dalloc(&c->rec_dgh, NB * 3 * H)); HIPC(dalloc(&c->rec_hm, NB * H));
+        HIPC(dalloc(&c->rec_mask, NB)); HIPC(dalloc(&c->rec_h0, NB * H));
+    }
+    HIPC(hipStreamSynchronize(c->stream));
+    c->gru_train = enabled != 0;
+    return 0;
+}
+int mi_get_gru(mi_ctx* c, float* w_ih, float* w_hh, float* b_ih, float* b_hh) {
+    ARG(c && w_ih && w_hh && b_ih && b_hh, "null"); JOIN(c); ARG(c->gru_on, "no GRU set");
+    const size_t H = c->H;
+    HIPC(hipMemcpyAsync(w_ih, c->gru_wih, 3 * H * H * 4, hipMemcpyDeviceToHost, c->stream)); HIPC(hipMemcpyAsync(w_hh, c->gru_whh, 3 * H * H * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(b_ih, c->gru_bih, 3 * H * 4, hipMemcpyDeviceToHost, c->stream)); HIPC(hipMemcpyAsync(b_hh, c->gru_bhh, 3 * H * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return 0;
+}
+int mi_get_gru_grads(mi_ctx* c, float* w_ih, float* w_hh, float* b_ih, float* b_hh) {
+    ARG(c && w_ih && w_hh && b_ih && b_hh, "null"); JOIN(c); ARG(c->gru_g, "GRU training is off: call mi_gru_train first");
+    const size_t H = c->H, W = 3 * H * H, B = 3 * H;
+    HIPC(hipMemcpyAsync(w_ih, c->gru_g, W * 4, hipMemcpyDeviceToHost, c->stream)); HIPC(hipMemcpyAsync(w_hh, c->gru_g + W, W * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(b_ih, c->gru_g + 2 * W, B * 4, hipMemcpyDeviceToHost, c->stream)); HIPC(hipMemcpyAsync(b_hh, c->gru_g + 2 * W + B, B * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return 0;
+}
+int mi_get_gru_adam_state(mi_ctx* c, float* m, float* v, int64_t n) {
+    ARG(c && m && v, "null"); JOIN(c); ARG(c->gru_g, "GRU training is off: call mi_gru_train first"); ARG(n == gru_count(c), "n != 2 * 3H^2 + 2 * 3H");
+    HIPC(hipMemcpyAsync(m, c->gru_m, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)); HIPC(hipMemcpyAsync(v, c->gru_v, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return 0;
+}
+int mi_set_gru_adam_state(mi_ctx* c, const float* m, const float* v, int64_t n) {
+    ARG(c && m && v, "null"); JOIN(c); ARG(c->gru_g, "GRU training is off: call mi_gru_train first"); ARG(n == gru_count(c), "n != 2 * 3H^2 + 2 * 3H");
+    HIPC(hipMemcpyAsync(c->gru_m, m, (size_t)n * 4, hipMemcpyHostToDevice, c->stream)); HIPC(hipMemcpyAsync(c->gru_v, v, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// One recurrent minibatch: the n_env envs of env_idx x all T steps, rows time-major (row t * n_env + i = step t of env env_idx[i], the order
+// of Storage.fetch_train_generator(recurrent=True), common/storage.py:93-110).  Embedder forward on all rows, the GRU over the
+// trajectories from h0 with the masks 1 - done[t, e] (the done stored WITH step t, agents/ppo_pure.py:124 -- the rollout masks with the done
+// of step t - 1), heads on h_t, the loss kernels of mi_minibatch, then back: heads, GRU through time, embedder from dX.
+int mi_minibatch_rec(mi_ctx* c, const int64_t* env_idx, int32_t n_env, const float* h0, int32_t n_global, const mi_hparams* hp) {
+    ARG(c && hp && env_idx && h0, "null"); JOIN(c);
+    ARG(c->gru_train, "GRU training is off: call mi_gru_train first");
+    ARG(hp->fs_coef == 0.f, "algo ppo-pure has no feature-sparsity term: fs_coef must be 0");
+    ARG(c->multirank == 0 && !c->ar_armed && !c->comm, "GRU training runs on a single rank: multirank modes 1 / 2 and the in-library gradient exchange are refused");
+    ARG(n_env >= 1 && n_global >= 1, "n_env / n_global");
+    ARG((int64_t)n_env * c->T <= c->NB, "n_env * T must not exceed max_batch");
+    ARG(c->log_count + 1 <= c->log_cap, "loss log full: call mi_loss_log_read(reset=1)");
+    ARG(c->pending_n < 0, "previous multirank minibatch not finished");
+    for (int i = 0; i < n_env; ++i) ARG(env_idx[i] >= 0 && env_idx[i] < c->E, "env index out of range");
+    const int T = c->T, E = c->E, H = c->H, n = n_env, N = n_env * T;
+    {
+        const int slot = c->idx_next;
+        c->idx_next = (slot + 1) % mi_ctx::IDX_RING;
+        if (c->idx_used[slot]) HIPC(hipEventSynchronize(c->idx_ev[slot]));
+        int32_t* h = c->h_idx_ring[slot];
+        for (int t = 0; t < T; ++t) for (int i = 0; i < n; ++i) h[t * n + i] = (int32_t)(t * E + env_idx[i]);
+        launch_pull_i32(h, c->d_idx, N, c->stream);
+        HIPC(hipEventRecord(c->idx_ev[slot], c->stream));
+        c->idx_used[slot] = true;
+    }
+    HIPC(hipMemcpyAsync(c->rec_h0, h0, (size_t)n * H * 4, hipMemcpyHostToDevice, c->stream));      // (pageable source: copied at call time)
+    InputSrc src = minibatch_src(c);
+    c->prof.phase = 1;
+    c->prof.sample_now = (c->prof.mb_count++ % c->prof.period) == 0;
+    const bool impala = c->cfg.arch == MI_ARCH_IMPALA;
+    net_forward(c, src, N, false, false, true);                                 // embedder only: feat = x
+    // the sequence forward writes h_t over feat (the heads and their backward read it there); x is needed again for dW_ih and, for IMPALA,
+    // as the ReLU mask of dX
+    HIPC(hipMemcpyAsync(c->rec_x, c->feat, (size_t)N * H * 4, hipMemcpyDeviceToDevice, c->stream));
+    launch_gru_seq_mask(c->done, c->d_idx, c->rec_mask, N, c->stream);          // m[t, i] = 1 - done[t, e_i]
+    linear_fwd(c, c->rec_x, 0, c->gru_wih, c->gru_bih, c->rec_gi, N, H, 3 * H, 0);
+    launch_gru_seq_fwd(c->rec_gi, c->rec_h0, c->rec_mask, c->gru_whh, c->gru_bhh, c->feat, c->rec_sv, T, n, H, c->stream);
+    net_heads(c, N);
+    LossArgs a{};
+    a.hout = c->hout; a.idx = c->d_idx; a.act = c->act; a.old_logp = c->logp; a.old_value = c->value; a.ret = c->ret; a.adv = c->adv;
+    a.dY = c->dY; a.partial = c->loss_partial; a.n = N; a.A = c->A;
+    a.inv_n_global = 1.0f / (float)n_global;
+    a.hp = LossHP{hp->eps_clip, hp->value_coef, hp->entropy_coef, hp->x_entropy_coef, hp->entropy_multiplier, 0.f};
+    const bool batch_terms = hp->x_entropy_coef != 0.f;
+    SegTab st{};
+    st.n_seg = 1; st.start[1] = N;
+    float* ring = c->stats_ring + (size_t)c->log_count * 32;
+    a.stats = ring;
+    if (impala) launch_fs_metric_seg(c->blk[2].P2, c->bf, st, 2048, c->fs_scratch, c->fs_parts, c->stream);
+    launch_loss_fwd_seg(a, st, !batch_terms, c->stream);
+    launch_loss_finalize_seg(a, st, 3, ring, impala ? c->fs_parts : nullptr, 2048, c->fs_ring + c->log_count, c->loss_log + (size_t)c->log_count * 8, c->stream);
+    c->ring_args = a;
+    c->log_count += 1;
+    if (batch_terms) launch_loss_bwd(a, c->stream);
+    // heads backward on h_t: no ReLU mask here (for IMPALA the embedder's final ReLU sits under x, not under h_t)
+    if (H <= 256 && c->A + 1 <= 16)
+        launch_heads_bwd(c->dY, c->feat, c->params + c->wh_off, 0, c->dfeat, c->grads + c->wh_off, c->grads + c->bh_off, c->gemm_ws, N, H, c->A + 1, c->stream);
+    else {
+        linear_wgrad(c, c->dY, c->feat, 0, c->grads + c->wh_off, c->grads + c->bh_off, N, H, c->A + 1);
+        linear_dgrad(c, c->dY, c->params + c->wh_off, nullptr, c->dfeat, N, H, c->A + 1);
+    }
+    launch_gru_seq_bwd(c->dfeat, c->feat, c->rec_h0, c->rec_mask, c->rec_sv, c->gru_whh, c->rec_dgi, c->rec_dgh, c->rec_hm, T, n, H, c->stream);
+    const size_t W = (size_t)3 * H * H, B = (size_t)3 * H;
+    linear_wgrad(c, c->rec_dgi, c->rec_x, 0, c->gru_g, c->gru_g + 2 * W, N, H, 3 * H);                    // dW_ih += dGI^T X ; db_ih += colsum dGI
+    linear_wgrad(c, c->rec_dgh, c->rec_hm, 0, c->gru_g + W, c->gru_g + 2 * W + B, N, H, 3 * H);           // dW_hh += dGH^T HM ; db_hh += colsum dGH
+    linear_dgrad(c, c->rec_dgi, c->gru_wih, impala ? c->rec_x : nullptr, c->dfeat, N, H, 3 * H);          // dX = dGI W_ih (* x > 0: the embedder's final ReLU)
+    c->bwd_from_dfeat = true;
+    net_backward(c, src, N);
+    c->bwd_from_dfeat = false;
+    c->rec_last = true;
+    HIPC(hipGetLastError()); NETCHK(c);
     return 0;
 }
 
@@ -2222,6 +2380,44 @@ int mi_debug_gru_step(mi_ctx* c, int32_t n, int32_t H, const float* x, const flo
     return rc;
 }
 
+// The GRU over a trajectory (gru_seq.hip) on caller data, for tests: n envs x T steps, rows time-major, width H (independent of the context's).
+// Forward: out_h = h_t of all rows.  With dOut (dL/dh_t of all rows) also the backward pass through time and the GEMMs behind it, exactly as
+// mi_minibatch_rec issues them: dX, dW_ih, dW_hh, db_ih, db_hh (from zero).
+int mi_debug_gru_seq(mi_ctx* c, int32_t T, int32_t n, int32_t H, const float* x, const float* h0, const float* mask, const float* w_ih, const float* w_hh,
+                     const float* b_ih, const float* b_hh, const float* dOut, float* out_h, float* dX, float* dW_ih, float* dW_hh, float* db_ih, float* db_hh) {
+    ARG(c && x && h0 && mask && w_ih && w_hh && b_ih && b_hh && out_h, "null"); JOIN(c);
+    ARG(!dOut || (dX && dW_ih && dW_hh && db_ih && db_hh), "null gradient outputs");
+    ARG(gru_seq_width_ok(H), "H must be a multiple of 64 in [64, 512]");
+    ARG(T >= 1 && n >= 1 && (int64_t)T * n <= 65536, "T, n >= 1 and T * n <= 65536");
+    const size_t N = (size_t)T * n, NH = N * H, W = (size_t)3 * H * H, B = (size_t)3 * H;
+    enum { X = 0, H0, MK, WIH, WHH, BIH, BHH, DOUT, GI, OUT, SV, DGI, DGH, HM, DX, GWIH, GWHH, GBIH, GBHH, NBUF };
+    const size_t sz[NBUF] = {NH, (size_t)n * H, N, W, W, B, B, NH, 3 * NH, NH, 4 * NH, 3 * NH, 3 * NH, NH, NH, W, W, B, B};
+    const float* src[8] = {x, h0, mask, w_ih, w_hh, b_ih, b_hh, dOut};
+    std::vector<float*> d(NBUF, nullptr);
+    int rc = 0;
+    for (int i = 0; i < NBUF && !rc; ++i) if (hipMalloc((void**)&d[i], sz[i] * 4) != hipSuccess) rc = fail(-2, "hipMalloc failed");
+    for (int i = 0; i < 8 && !rc; ++i) if (src[i] && hipMemcpy(d[i], src[i], sz[i] * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(-2, "upload failed");
+    for (int i = GWIH; i < NBUF && !rc; ++i) if (hipMemset(d[i], 0, sz[i] * 4) != hipSuccess) rc = fail(-2, "hipMemset failed");
+    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(-2, "sync failed");
+    if (!rc) {
+        linear_fwd(c, d[X], 0, d[WIH], d[BIH], d[GI], (int)N, H, 3 * H, 0);
+        launch_gru_seq_fwd(d[GI], d[H0], d[MK], d[WHH], d[BHH], d[OUT], d[SV], T, n, H, c->stream);
+        if (dOut) {
+            launch_gru_seq_bwd(d[DOUT], d[OUT], d[H0], d[MK], d[SV], d[WHH], d[DGI], d[DGH], d[HM], T, n, H, c->stream);
+            linear_wgrad(c, d[DGI], d[X], 0, d[GWIH], d[GBIH], (int)N, H, 3 * H);
+            linear_wgrad(c, d[DGH], d[HM], 0, d[GWHH], d[GBHH], (int)N, H, 3 * H);
+            linear_dgrad(c, d[DGI], d[WIH], nullptr, d[DX], (int)N, H, 3 * H);
+        }
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(-4, "GRU sequence kernels failed");
+        if (!rc) if (const char* lf = mi_launch_failed_take()) rc = fail(-4, lf);
+    }
+    auto down = [&](float* dst, int k) { if (!rc && hipMemcpy(dst, d[k], sz[k] * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(-2, "download failed"); };
+    down(out_h, OUT);
+    if (dOut) { down(dX, DX); down(dW_ih, GWIH); down(dW_hh, GWHH); down(db_ih, GBIH); down(db_hh, GBHH); }
+    for (float* p : d) if (p) hipFree(p);
+    return rc;
+}
+
 // Measurement hook ("hipGraph"): wall-clock microseconds per policy step of slot t -- the step's launches (conv stack,
 // embedder.fc, fused heads + sample: 5 kernels in bf16 mode) followed by a stream wait, `iters` times back to back -- issued eagerly
 // (mode 0) or as ONE replay of a graph captured from the same launches (mode 1).  What a captured group step could save on the
@@ -2267,8 +2463,11 @@ int mi_debug_step_latency(mi_ctx* c, int32_t t, int32_t iters, int32_t mode, flo
 // (window position ky*3+kx as float); which = 100: the 256 features.  For teacher-forced backward parity tests.
 int mi_debug_read(mi_ctx* c, int32_t which, int32_t n, float* out) {
     ARG(c && out, "null"); JOIN(c); ARG(n >= 1 && n <= c->NB, "n must be in [1, max_batch]");
-    if (which == 100) {
-        HIPC(hipMemcpyAsync(out, c->feat, (size_t)n * c->H * 4, hipMemcpyDeviceToHost, c->stream));
+    if (which == 100 || which == 101 || which == 102) {
+        // after a recurrent pass (mi_minibatch_rec) the features -- the embedder output x -- sit in their own buffer: feat holds h_t (101), dfeat dX (102)
+        ARG(which == 100 || c->rec_last, "which = 101 / 102: only after mi_minibatch_rec");
+        const float* srcp = which == 102 ? c->dfeat : (which == 100 && c->rec_last) ? c->rec_x : c->feat;
+        HIPC(hipMemcpyAsync(out, srcp, (size_t)n * c->H * 4, hipMemcpyDeviceToHost, c->stream));
         HIPC(hipStreamSynchronize(c->stream));
         return 0;
     }

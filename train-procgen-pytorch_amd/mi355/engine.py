@@ -41,7 +41,8 @@ EXPORTS = ("mi_last_error mi_create mi_destroy mi_sync mi_host_alloc mi_host_fre
            "mi_get_params mi_copy_params mi_get_grads mi_set_adam_state mi_get_adam_state mi_put_obs mi_get_obs mi_put_step "
            "mi_put_policy_outputs mi_read_field mi_write_field mi_policy_step mi_rollout_step mi_rollout_groups mi_rollout_submit mi_rollout_wait mi_predict_staged mi_value_saliency mi_commit_staged mi_set_gru mi_rec_state mi_get_hidden mi_rec_begin mi_get_hidden_ring mi_forward_rec mi_forward mi_compute_estimates "
            "mi_adv_stats mi_adv_apply mi_minibatch mi_minibatch_multi mi_optimizer_step mi_loss_log_read mi_device_ptr "
-           "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_gru_step mi_debug_step_latency").split()
+           "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_gru_step mi_debug_step_latency "
+           "mi_gru_train mi_minibatch_rec mi_get_gru mi_get_gru_grads mi_get_gru_adam_state mi_set_gru_adam_state mi_debug_gru_seq").split()
 
 
 def load_library():
@@ -319,6 +320,65 @@ class Engine:
         a = [_f32(x) for x in (w_ih, w_hh, b_ih, b_hh)]
         self._chk(self.lib.mi_set_gru(self._ctx, *[_fp(x) for x in a]))
 
+    # ------------------------------------------------------------------ GRU training (algo: ppo-pure)
+    GRU_NAMES = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+
+    def gru_shapes(self):
+        H = self.H
+        return ((3 * H, H), (3 * H, H), (3 * H,), (3 * H,))
+
+    def gru_count(self):
+        return 2 * 3 * self.H * self.H + 2 * 3 * self.H
+
+    def gru_train(self, enabled=True):
+        """The GRU becomes a trained parameter set: gradient + Adam moments beside the flat vectors, one global clip norm (mi_gru_train)."""
+        self._chk(self.lib.mi_gru_train(self._ctx, C.c_int32(int(enabled))))
+        self.gru_trained = bool(enabled)
+
+    def _gru4(self, fn):
+        out = [np.empty(sh, np.float32) for sh in self.gru_shapes()]
+        self._chk(fn(self._ctx, *[_fp(x) for x in out]))
+        return tuple(out)
+
+    def get_gru(self):
+        """(w_ih, w_hh, b_ih, b_hh) as they are on the device, nn.GRU's layout."""
+        return self._gru4(self.lib.mi_get_gru)
+
+    def get_gru_grads(self):
+        return self._gru4(self.lib.mi_get_gru_grads)
+
+    def get_gru_adam_state(self):
+        """(exp_avg, exp_avg_sq), each one vector {w_ih, w_hh, b_ih, b_hh}."""
+        n = self.gru_count()
+        m, v = np.empty(n, np.float32), np.empty(n, np.float32)
+        self._chk(self.lib.mi_get_gru_adam_state(self._ctx, _fp(m), _fp(v), C.c_int64(n)))
+        return m, v
+
+    def set_gru_adam_state(self, m, v):
+        m, v = _f32(m).reshape(-1), _f32(v).reshape(-1)
+        self._chk(self.lib.mi_set_gru_adam_state(self._ctx, _fp(m), _fp(v), C.c_int64(m.size)))
+
+    def minibatch_rec(self, envs, h0, n_global, hp):
+        """One recurrent minibatch: the envs of `envs` x all T steps, from the initial hidden states h0 (len(envs), H) (mi_minibatch_rec)."""
+        envs = np.ascontiguousarray(envs, dtype=np.int64).reshape(-1)
+        h0 = _f32(h0)
+        if h0.size != envs.size * self.H:
+            raise EngineError(f"minibatch_rec: h0 must be (n_env, H) = ({envs.size}, {self.H})")
+        self._chk(self.lib.mi_minibatch_rec(self._ctx, _fp(envs), C.c_int32(envs.size), _fp(h0), C.c_int32(n_global), C.byref(hp)))
+
+    def debug_gru_seq(self, x, h0, mask, w_ih, w_hh, b_ih, b_hh, d_out=None):
+        """The GRU over a trajectory on caller data (mi_debug_gru_seq): x (T, n, H), h0 (n, H), mask (T, n), nn.GRU-layout weights -> h (T, n, H);
+        with d_out (T, n, H) = dL/dh also (h, dX, dW_ih, dW_hh, db_ih, db_hh)."""
+        x = _f32(x)
+        T, n, H = x.shape
+        a = [_f32(v) for v in (h0, mask, w_ih, w_hh, b_ih, b_hh)]
+        d_out = None if d_out is None else _f32(d_out)
+        out = np.empty((T, n, H), np.float32)
+        g = [None] * 5 if d_out is None else [np.empty(sh, np.float32) for sh in ((T, n, H), (3 * H, H), (3 * H, H), (3 * H,), (3 * H,))]
+        self._chk(self.lib.mi_debug_gru_seq(self._ctx, C.c_int32(T), C.c_int32(n), C.c_int32(H), _fp(x), *[_fp(v) for v in a], _fp(d_out),
+                                            _fp(out), *[_fp(v) for v in g]))
+        return out if d_out is None else (out, *g)
+
     def rec_state(self, hidden=None, done=None):
         hidden = None if hidden is None else _f32(hidden)
         done = None if done is None else _f32(done)
@@ -523,7 +583,7 @@ class Engine:
 
     def debug_read(self, which, n):
         """Activation tensor `which` (see include/mi355ppo.h mi_debug_read) of the last minibatch pass, first n samples, fp32 NHWC."""
-        if which == 100:
+        if which in (100, 101, 102):        # features; after minibatch_rec: 100 the embedder output x, 101 h_t, 102 dX
             out = np.empty((n, self.H), np.float32)
         else:
             b = which >> 3

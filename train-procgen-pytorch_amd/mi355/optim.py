@@ -38,6 +38,9 @@ class DeviceAdam:
         self.policy.mark_device_updated()
         return out
 
+    def _gru_trained(self):
+        return bool(getattr(self.policy, "_gru_trained", False))
+
     def state_dict(self):
         if self.step_count > 0:
             shapes = self.policy.param_shapes()
@@ -46,6 +49,17 @@ class DeviceAdam:
             for n, p in zip(self._names, self._params):
                 self._adam.state[p] = {'step': torch.tensor(float(self.step_count)),
                                        'exp_avg': torch.from_numpy(m[n]), 'exp_avg_sq': torch.from_numpy(v[n])}
+            if self._gru_trained():
+                # algo ppo-pure: the GRU's four tensors are trained, so they carry state like every other parameter (they come last
+                # in policy.parameters()); the device keeps their moments as one vector {w_ih, w_hh, b_ih, b_hh}
+                gm, gv = self.engine.get_gru_adam_state()
+                off = 0
+                for p in self.policy.gru_parameters():
+                    k = p.numel()
+                    self._adam.state[p] = {'step': torch.tensor(float(self.step_count)),
+                                           'exp_avg': torch.from_numpy(gm[off:off + k].reshape(tuple(p.shape)).copy()),
+                                           'exp_avg_sq': torch.from_numpy(gv[off:off + k].reshape(tuple(p.shape)).copy())}
+                    off += k
         return self._adam.state_dict()
 
     def load_state_dict(self, sd):
@@ -57,4 +71,10 @@ class DeviceAdam:
         m = {n: st[p]['exp_avg'].numpy() for n, p in zip(self._names, self._params)}
         v = {n: st[p]['exp_avg_sq'].numpy() for n, p in zip(self._names, self._params)}
         self.engine.set_adam_state(layout.flatten(shapes, m), layout.flatten(shapes, v))
+        if self._gru_trained():
+            gp = self.policy.gru_parameters()
+            if all(p in st for p in gp):
+                import numpy as np
+                self.engine.set_gru_adam_state(np.concatenate([st[p]['exp_avg'].numpy().ravel() for p in gp]),
+                                               np.concatenate([st[p]['exp_avg_sq'].numpy().ravel() for p in gp]))
         self.step_count = int(float(st[self._params[0]]['step']))

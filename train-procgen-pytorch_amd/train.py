@@ -33,6 +33,7 @@ import torch
 import yaml
 
 from agents.ppo import PPO
+from agents.ppo_pure import PPOPure
 from common.env.vec_envs import EnvGroups, SyntheticFrames, create_cartpole, create_procgen_env
 from common.logger import Logger
 from common.misc_util import set_global_seeds
@@ -114,6 +115,8 @@ def add_training_args(p):
     p.add_argument('--rollout_groups', type=int, default=0,
                    help="env groups of the pipelined rollout (one group's frame upload + forward beside the host's env.step of another); 0 = auto (from 128 envs per rank: 4, or 2 + 2 when a validation env runs beside the training env; else 2; a recurrent policy: 1); 1 = the reference's serial step; a recurrent policy is pipelined only with an explicit G >= 2")
     p.add_argument('--x_entropy_coef', type=float, default=None)
+    p.add_argument('--algo', type=str, default=None, choices=['ppo', 'ppo-pure'],
+                   help="overrides the set's `algo`: ppo = the reference's agents/ppo.py (a recurrent policy's GRU stays frozen), ppo-pure = agents/ppo_pure.py (a recurrent policy is trained through its GRU with BPTT; single GPU)")
     return p
 
 
@@ -215,8 +218,9 @@ def train_ppo(args):
     env_name = hp.get("env_name", args.env_name)
     for key, value in hp.items():
         print(key, ':', value)
-    if hp.get("algo", "ppo") != "ppo":
-        raise NotImplementedError("only algo: ppo is accelerated")
+    algo = hp.get("algo", "ppo")
+    if algo not in ("ppo", "ppo-pure"):
+        raise NotImplementedError("only algo: ppo and algo: ppo-pure are accelerated")
     if hp.get("continuous", False):
         raise NotImplementedError("continuous actions are not part of the accelerated PPO path")
     if args.device != 'gpu':
@@ -234,6 +238,8 @@ def train_ppo(args):
         seed_t = torch.tensor([args.seed], dtype=torch.int64, device=torch.device("cuda", args.gpu_device))
         torch.distributed.broadcast(seed_t, 0)              # same initial weights and minibatch permutations on every rank
         args.seed = int(seed_t.item())
+    if world > 1 and algo == "ppo-pure" and hp.get("recurrent", False):
+        raise NotImplementedError("algo: ppo-pure with a recurrent policy trains the GRU on a single GPU only (WORLD_SIZE must be 1)")
     set_global_seeds(args.seed)
     from mi355.numa import pin_to_gpu_node
     pin_to_gpu_node(int(getattr(args, "gpu_device", 0) or 0))      # (new) host threads + pinned buffers on the GPU's NUMA node
@@ -251,11 +257,12 @@ def train_ppo(args):
     cfg = dict(vars(args)); cfg.update(hp)
     np.save(os.path.join(logdir, "config.npy"), cfg)
     model, obs_shape, policy = initialize_model(device, env, hp)
-    logger = Logger(n_envs, logdir, use_wandb=args.use_wandb)
+    logger = Logger(n_envs, logdir, use_wandb=args.use_wandb, algo=algo)
     logger.max_steps = hp.get("max_steps", 10 ** 3)
     storage = Storage(obs_shape, model.output_dim, n_steps, n_envs, device)
     storage_valid = Storage(obs_shape, model.output_dim, n_steps, n_envs, device) if args.use_valid_env else None
-    agent = PPO(env, policy, logger, storage, device, args.num_checkpoints, env_valid=env_valid, storage_valid=storage_valid,
+    agent_cls = PPOPure if algo == "ppo-pure" else PPO
+    agent = agent_cls(env, policy, logger, storage, device, args.num_checkpoints, env_valid=env_valid, storage_valid=storage_valid,
                 seed=args.seed + rank, detect_nan=args.detect_nan, **hp)
     if model_file is not None:
         print("Loading agent from %s" % model_file)
