@@ -39,7 +39,11 @@ typedef struct mi_config {
     int32_t precision;     /* IMPALA activations / activation gradients in HBM: 0 = fp32 (parity mode), 1 = bf16 storage +
                               bf16 matrix cores with fp32 accumulation for the 16/32-channel convs (BASELINE config 3);
                               parameters, gradients of parameters, Adam, losses and GAE are fp32 in both modes */
-    int32_t reserved[5];
+    int32_t value_from_logits; /* 0: value = fc_value(hidden) (common/policy.py:79-80); 1: CategoricalPolicy(logsumexp_logits_is_v=True),
+                              value = logsumexp of the raw fc_policy logits (policy.py:77-78).  fc_value keeps its place in the flat vectors,
+                              receives an exactly zero gradient and never changes; the value-loss gradient flows into the logits.
+                              Any other value is refused.  (The first slot of what was reserved[5]: 0 is the earlier behaviour.) */
+    int32_t reserved[4];
     void*   stream;        /* hipStream_t to issue on, or NULL for a stream owned by the context */
 } mi_config;
 
@@ -128,7 +132,9 @@ int mi_predict_staged(mi_ctx* ctx, const void* obs, size_t bytes, uint64_t seed,
  * [E][64][64][3] floats (NHWC, with respect to the k/255 float frames) for IMPALA, [E][obs_dim] for the MLP.  With a GRU set (mi_set_gru)
  * the step is the recurrent one -- it consumes the hidden state / done flags of mi_rec_state and advances the state like a policy step --
  * and the gradient runs back through the GRU cell's input path (common/model.py:219-225 under autograd).  Discards (zeroes) the
- * parameter-gradient buffer, so not inside an accumulating update. */
+ * parameter-gradient buffer, so not inside an accumulating update.  With mi_config.value_from_logits the value differentiated is the
+ * logsumexp of the logits: the backward pass is seeded with softmax(logits) in the logit columns (recurrent: softmax(logits) W_pi per row
+ * into the GRU cell) instead of a 1 in the value column. */
 int mi_value_saliency(mi_ctx* ctx, const void* obs, size_t bytes, uint64_t seed, uint64_t counter, const float* u,
                       int64_t* act_out, float* logp_out, float* value_out, float* grad_out);
 int mi_commit_staged(mi_ctx* ctx, int32_t t);
@@ -200,7 +206,7 @@ int mi_loss_log_read(mi_ctx* ctx, float* out, int32_t max_records, int32_t* n_re
  *      common/storage.py:93-110) = the n_env envs of env_idx x all T steps, rows time-major; h0 = hidden_states_batch[0, envs] (n_env x H);
  *      the mask of step t is 1 - done[t, e], the done stored WITH step t (ppo_pure.py:124), where the rollout masks with the done of step
  *      t - 1.  n_env * T <= max_batch; n_global as in mi_minibatch; fs_coef must be 0 (ppo-pure has no such term); multirank modes 1 / 2
- *      and the in-library gradient exchange are refused.  Gradients accumulate until mi_optimizer_step; one loss-log record per call.
+ *      and the in-library gradient exchange are refused, and so is a context created with value_from_logits.  Gradients accumulate until mi_optimizer_step; one loss-log record per call.
  *      mi_get_gru / mi_get_gru_grads read the weights / accumulated gradients in nn.GRU's layout; the Adam moments travel as the one
  *      vector above (n = 2 * 3H^2 + 2 * 3H). */
 int mi_gru_train(mi_ctx* ctx, int32_t enabled);

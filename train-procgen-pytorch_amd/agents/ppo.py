@@ -84,7 +84,7 @@ class PPO(BaseAgent):
                              obs_dim=getattr(emb, "input_size", 0), mlp_depth=getattr(emb, "depth", 0),
                              mlp_width=getattr(emb, "mid_weight", 0), out_dim=emb.output_dim, device=dev_index,
                              stream=self._tstream.cuda_stream if self._tstream is not None else None,
-                             precision=self.precision)
+                             precision=self.precision, value_from_logits=policy.logsumexp_logits_is_v)
         policy.attach_engine(self.engine)
         storage.attach_engine(self.engine)
         self.engine_valid = None
@@ -93,7 +93,7 @@ class PPO(BaseAgent):
             self.engine_valid = Engine(arch, n_steps, n_envs, policy.action_size, max_batch=n_envs,
                                        obs_dim=getattr(emb, "input_size", 0), mlp_depth=getattr(emb, "depth", 0),
                                        mlp_width=getattr(emb, "mid_weight", 0), out_dim=emb.output_dim, device=dev_index,
-                                       precision=self.precision)
+                                       precision=self.precision, value_from_logits=policy.logsumexp_logits_is_v)
             storage_valid.attach_engine(self.engine_valid)
             policy.attach_aux_engine(self.engine_valid)          # frozen GRU weights, now and after load_state_dict
         self.optimizer = DeviceAdam(policy, self.engine, learning_rate, eps=1e-5)

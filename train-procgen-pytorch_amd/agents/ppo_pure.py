@@ -22,6 +22,9 @@ class PPOPure(PPO):
                  x_entropy_coef=0., normalize_adv=True, normalize_rew=True, use_gae=True, entropy_scaling=None,
                  increasing_lr=False, sparsity_coef=0., fs_coef=0., **kwargs):
         recurrent = policy.is_recurrent()
+        if recurrent and getattr(policy, "logsumexp_logits_is_v", False):
+            raise NotImplementedError("algo: ppo-pure with a recurrent policy and logsumexp_logits_is_v: training through the GRU with the "
+                                      "logsumexp value head is not built (use algo: ppo, or a non-recurrent policy)")
         if recurrent:
             self._check_recurrent(n_steps, n_envs, n_minibatch, mini_batch_size)
             # a recurrent minibatch is whole trajectories: the engine's batch capacity must hold one env group x T steps (PPO sizes it

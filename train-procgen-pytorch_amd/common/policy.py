@@ -19,13 +19,17 @@ class CategoricalPolicy(nn.Module):
     def __init__(self, embedder, recurrent, action_size, has_vq=False, continuous_actions=False,
                  logsumexp_logits_is_v=False, extra_params=False):
         super().__init__()
-        if has_vq or continuous_actions or logsumexp_logits_is_v or extra_params:
-            raise NotImplementedError("only the discrete-action CategoricalPolicy of algo: ppo is accelerated")
+        refused = [n for n, v in (("has_vq", has_vq), ("continuous_actions", continuous_actions), ("extra_params", extra_params)) if v]
+        if refused:
+            raise NotImplementedError(f"CategoricalPolicy({', '.join(n + '=True' for n in refused)}) is not accelerated: only the discrete-action "
+                                      "policy of algo: ppo / ppo-pure is (logsumexp_logits_is_v is the one switch that is)")
         self.embedder = embedder
         self.has_vq = False
         self.continuous_actions = False
         self.action_size = action_size
-        self.logsumexp_logits_is_v = False
+        # policy.py:77-78: v = logits.logsumexp(-1) of the raw fc_policy outputs.  fc_value below still exists (state_dict keys, its place in
+        # policy.parameters()) but is never used: no gradient, no Adam state, never changes (mi_config.value_from_logits)
+        self.logsumexp_logits_is_v = bool(logsumexp_logits_is_v)
         self.fc_policy = orthogonal_init(nn.Linear(embedder.output_dim, action_size), gain=0.01)
         self.fc_value = orthogonal_init(nn.Linear(embedder.output_dim, 1), gain=1.0)
         self.target_entropy = np.log(action_size)

@@ -167,12 +167,13 @@ struct LossArgs {
     int n, A;
     float inv_n_global;       // 1 / (global minibatch size)
     LossHP hp;
+    int value_from_logits;    // mi_config.value_from_logits: v = logsumexp(logits); the launchers pick the kernels' LSE instantiation by it
 };
 int  loss_blocks(int n);
 void launch_loss_fwd(const LossArgs& a, hipStream_t st);
 // phase bit 0: block partials -> this rank's share of the global means; bit 1: derived terms + log record
 void launch_loss_finalize(const LossArgs& a, int nblk, int phase, const float* fs_ptr, float* log_slot, hipStream_t st);
-void launch_logp_all(const float* hout, int n, int A, float* lp_out, float* value_out, hipStream_t st);
+void launch_logp_all(const float* hout, int n, int A, float* lp_out, float* value_out, hipStream_t st, int value_from_logits = 0);
 void launch_loss_bwd(const LossArgs& a, hipStream_t st);
 // several global minibatches in one gathered batch (mi_minibatch_multi): samples of segment k are [start[k], start[k+1])
 constexpr int MI_MAX_SEG = 16;
@@ -205,14 +206,14 @@ void launch_advnorm_apply(float* adv, int n, const double* stats3, hipStream_t s
 void launch_advnorm_merge(const double* all, int R, double* stats3, hipStream_t st);   // all: R x {count, mean, M2}
 
 void launch_sample(const float* hout, int n, int A, const float* u, unsigned long long seed, unsigned long long ctr,
-                   int32_t* act, float* logp, float* value, hipStream_t st);
+                   int32_t* act, float* logp, float* value, hipStream_t st, int value_from_logits = 0);
 
 void launch_philox_debug(const uint32_t* in6, int n, uint32_t* out4, float* u_out, hipStream_t st);   // test hook (mi_debug_philox)
 
 void launch_heads_sample(const float* feat, const float* Wh, const float* bh, int n, int H, int A, const float* u,
                          unsigned long long seed, unsigned long long ctr, int32_t* act, float* logp, float* value, float* pack,
                          float* hout, const float* rd, float* rew_dst, float* done_dst, hipStream_t st,
-                         unsigned* done_ctr = nullptr, unsigned* host_flag = nullptr, unsigned ticket = 0);
+                         unsigned* done_ctr = nullptr, unsigned* host_flag = nullptr, unsigned ticket = 0, int value_from_logits = 0);
 void launch_sumsq(const float* g, long long n, double* out, double* part, hipStream_t st);          // out[0] = sum g^2 (deterministic)
 void launch_sumsq_partials(const float* g, long long n, double* part /* 128 doubles */, hipStream_t st);
 void launch_adam(float* p, float* g, float* m, float* v, long long n, const double* sumsq /* the sum, or npart partial sums */, int npart, float max_norm, float lr,
@@ -220,9 +221,14 @@ void launch_adam(float* p, float* g, float* m, float* v, long long n, const doub
                  hipStream_t st);
 void launch_fill(float* p, long long n, float v, hipStream_t st);
 void launch_value_seed(float* dY, int n, int A, hipStream_t st);
+// value_from_logits: d logsumexp(logits) / d (logits, value column) of n head rows -> dY; and the same gradient carried through fc_policy
+// to the heads' input, seed [n][H] (recurrent saliency: launch_gru_value_bwd with row_seed)
+void launch_lse_value_seed(const float* hout, float* dY, int n, int A, hipStream_t st);
+void launch_lse_hidden_seed(const float* hout, const float* Wh, float* seed, int n, int H, int A, hipStream_t st);
 void launch_conv1_input_grad(const void* dC, int bf16, const float* W, float* dX, int n, hipStream_t st);
 void launch_mask_rows(const float* h, const float* done, float* out, int n, int H, hipStream_t st);   // out = h * (1 - done[row])
-void launch_gru_value_bwd(const float* gi, const float* gh, const float* hm, const float* wv, float* dgates, int n, int H, hipStream_t st);
+void launch_gru_value_bwd(const float* gi, const float* gh, const float* hm, const float* wv /* [H], or [n][H] with row_seed */, float* dgates, int n, int H, hipStream_t st,
+                          int row_seed = 0);
 void launch_gru_gates(const float* gi, const float* gh, const float* hm, float* h_out, float* feat_out, int n, int H, hipStream_t st);
 // h' = GRU(x, h_in * (1 - done)) for n rows in one launch -> h_out (and h_copy unless null); h_in aliases none of x / h_out / h_copy
 void launch_gru_step(const float* x, const float* h_in, const float* done, const float* w_ih, const float* w_hh, const float* b_ih,

@@ -127,6 +127,7 @@ struct mi_ctx {
     std::vector<float*> mlp_act;   // X0 (input), h1..hL
     int64_t wh_off, bh_off;        // heads: (A+1) x H weights, (A+1) bias (device order)
     float *feat, *hout, *dY, *dfeat, *GC, *GP[3];
+    int lse = 0; float* d_val = nullptr;                  // value_from_logits (common/policy.py:77-78); d_val: mi_forward's values [NB] in that mode
     float* slabs; size_t slab_floats;
     void* sal_dc; float* sal_dx; const float* sal_src;       // value saliency: conv-out gradient temp (bf16 mode), input gradient, where net_backward left block 1's gradient
     long long slab_off[15]; SlabDesc h_slab_desc[15]; SlabDesc* d_slab_desc; int slab_desc_n, slab_desc_cached_n;   // per-layer slab regions; ONE reduce launch per backward pass
@@ -324,6 +325,7 @@ int mi_create(const mi_config* cfg, mi_ctx** out) {
     ARG(cfg->n_actions >= 1 && cfg->n_actions <= 16, "n_actions must be in [1,16]");
     ARG(cfg->n_steps >= 1 && cfg->n_envs >= 1 && cfg->max_batch >= 1, "n_steps/n_envs/max_batch");
     ARG(cfg->precision == 0 || cfg->precision == 1, "precision must be 0 (fp32) or 1 (bf16 activations)");
+    ARG(cfg->value_from_logits == 0 || cfg->value_from_logits == 1, "value_from_logits must be 0 (fc_value head) or 1 (logsumexp of the logits)");
     if (cfg->arch == MI_ARCH_MLP) ARG(cfg->obs_dim >= 1 && cfg->mlp_depth >= 2 && cfg->mlp_width >= 1 && cfg->out_dim >= 1, "mlp dims");
     if (cfg->arch == MI_ARCH_IMPALA)          // out_dim 0: unset by a C caller, the reference's default 256
         ARG(cfg->out_dim == 0 || (cfg->out_dim >= 64 && cfg->out_dim <= 512 && cfg->out_dim % 64 == 0),
@@ -337,6 +339,7 @@ int mi_create(const mi_config* cfg, mi_ctx** out) {
     c->H = (cfg->arch == MI_ARCH_IMPALA && cfg->out_dim == 0) ? 256 : cfg->out_dim;
     c->NB = cfg->max_batch < cfg->n_envs ? cfg->n_envs : cfg->max_batch;
     c->bf = (cfg->arch == MI_ARCH_IMPALA) && cfg->precision == 1;
+    c->lse = cfg->value_from_logits;
     c->es = c->bf ? 2.0 : 4.0;
     if (cfg->stream) { c->stream = (hipStream_t)cfg->stream; c->own_stream = false; }
     else { HIPC(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
@@ -396,6 +399,7 @@ int mi_create(const mi_config* cfg, mi_ctx** out) {
     }
     HIPC(dalloc(&c->feat, (size_t)NB * c->H)); HIPC(dalloc(&c->dfeat, (size_t)NB * c->H));
     HIPC(dalloc(&c->hout, (size_t)NB * (c->A + 1))); HIPC(dalloc(&c->dY, (size_t)NB * (c->A + 1)));
+    if (c->lse) HIPC(dalloc(&c->d_val, (size_t)NB));
     HIPC(dalloc(&c->d_lp, (size_t)NB * c->A));
     const size_t gws = (size_t)8 << 20;
     HIPC(dalloc(&c->gemm_ws, gws)); c->gemm_ws_floats = gws;
@@ -499,6 +503,7 @@ int mi_destroy(mi_ctx* c) {
     if (c->frames) hipFree(c->frames);
     if (c->stage_frames) hipFree(c->stage_frames);
     hipFree(c->s_act); hipFree(c->s_logp); hipFree(c->s_val);
+    if (c->d_val) hipFree(c->d_val);
     if (c->fc_wp) hipFree(c->fc_wp); if (c->fc_wt) hipFree(c->fc_wt);
     if (c->banks) hipFree(c->banks); if (c->d_bank_desc) hipFree(c->d_bank_desc); if (c->c1_bank) hipFree(c->c1_bank);
     hipFree(c->stats_ring); hipFree(c->fs_ring); hipFree(c->fs_parts); if (c->d_slab_desc) hipFree(c->d_slab_desc); if (c->sal_dc) hipFree(c->sal_dc); if (c->sal_dx) hipFree(c->sal_dx); hipFree(c->d_pack); hipFree(c->d_rd); hipHostFree(c->h_pack); hipHostFree(c->h_rd); hipFree(c->d_done_ctr); if (c->side_stream) hipStreamDestroy(c->side_stream); hipEventDestroy(c->ev_side_fork); hipEventDestroy(c->ev_side_join); hipHostFree(c->h_flag);
@@ -820,6 +825,7 @@ static void linear_wgrad(mi_ctx* c, const float* dY, const float* X, int relu_x,
 }
 
 static void net_heads(mi_ctx* c, int n, int soff = 0) {
+    // (tests/test_gpu_lse_value.py::test_update_sized_heads_and_partial_loss_block picks its 1040 samples to be past this threshold)
     if (c->H == 256 && c->A + 1 <= 16 && n >= 1024) {      // update-sized batches: dedicated kernel (misc.hip heads_fwd_kernel)
         ProfScope ps(c, PC_GEMM, n, 4.0 * ((double)n * c->H + (double)n * (c->A + 1) + (double)c->H * (c->A + 1)), 2.0 * n * c->H * (c->A + 1));
         launch_heads_fwd(c->feat + (size_t)soff * c->H, c->params + c->wh_off, c->params + c->bh_off, c->hout + (size_t)soff * (c->A + 1), n, c->A + 1, CUR(c));
@@ -1143,7 +1149,7 @@ int mi_policy_step(mi_ctx* c, int32_t t, uint64_t seed, const float* u, int64_t*
     net_forward(c, src, E, true);
     const bool last = (t == c->T);
     launch_sample(c->hout, E, c->A, du, seed, (unsigned long long)t * E, last ? nullptr : c->act + (size_t)t * E,
-                  last ? nullptr : c->logp + (size_t)t * E, c->value + (size_t)t * E, c->stream);
+                  last ? nullptr : c->logp + (size_t)t * E, c->value + (size_t)t * E, c->stream, c->lse);
     HIPC(hipGetLastError()); NETCHK(c);
     if (!act_out && !logp_out && !value_out) { if (u) HIPC(hipStreamSynchronize(c->stream)); return 0; }
     if (act_out && !last) HIPC(hipMemcpyAsync(c->h_i, c->act + (size_t)t * E, (size_t)E * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1177,7 +1183,7 @@ int mi_rollout_step(mi_ctx* c, int32_t t, const float* rew_prev, const float* do
     launch_heads_sample(c->feat, c->params + c->wh_off, c->params + c->bh_off, E, c->H, c->A, du, seed, (unsigned long long)t * E,
                         last ? nullptr : c->act + (size_t)t * E, last ? nullptr : c->logp + (size_t)t * E, c->value + (size_t)t * E,
                         c->h_pack, nullptr, have_rd ? c->h_rd : nullptr, have_rd ? c->rew + (size_t)(t - 1) * E : nullptr,
-                        have_rd ? c->done + (size_t)(t - 1) * E : nullptr, c->stream, c->d_done_ctr, c->h_flag, ++c->roll_ticket);
+                        have_rd ? c->done + (size_t)(t - 1) * E : nullptr, c->stream, c->d_done_ctr, c->h_flag, ++c->roll_ticket, c->lse);
     HIPC(hipGetLastError()); NETCHK(c);
     // The last workgroup of the head kernel publishes the ticket after all results (h_pack) are visible to the host and all reads of
     // h_rd / u are done: spinning on it returns ~5 us earlier than hipStreamSynchronize (12.9 -> 8.1 us for launch + wait of a small
@@ -1271,7 +1277,7 @@ static int group_issue(mi_ctx* c, int g, const GroupJob& j) {
     launch_heads_sample(hin, c->params + c->wh_off, c->params + c->bh_off, ng, c->H, c->A, du, j.seed, (unsigned long long)j.t * E + e0,
                         j.last ? nullptr : c->act + o, j.last ? nullptr : c->logp + o, c->value + o, c->h_pack + 3 * e0, nullptr,
                         j.have_rd ? h_rd : nullptr, j.have_rd ? c->rew + o - E : nullptr, j.have_rd ? c->done + o - E : nullptr, st,
-                        c->d_done_ctr + 1 + g, c->h_flag + 1 + g, j.ticket);
+                        c->d_done_ctr + 1 + g, c->h_flag + 1 + g, j.ticket, c->lse);
     HIPC(hipGetLastError());
     if (const char* lf = mi_launch_failed_take()) return fail(-4, lf);      // (this worker thread's launchers)
     return 0;
@@ -1403,7 +1409,7 @@ int mi_predict_staged(mi_ctx* c, const void* obs, size_t bytes, uint64_t seed, u
     if (u) { HIPC(hipMemcpyAsync(c->d_u, u, (size_t)E * 4, hipMemcpyHostToDevice, c->stream)); du = c->d_u; }
     InputSrc src{stage, nullptr, 0};
     net_forward(c, src, E, true);
-    launch_sample(c->hout, E, c->A, du, seed, counter, c->s_act, c->s_logp, c->s_val, c->stream);
+    launch_sample(c->hout, E, c->A, du, seed, counter, c->s_act, c->s_logp, c->s_val, c->stream, c->lse);
     HIPC(hipGetLastError()); NETCHK(c);
     HIPC(hipMemcpyAsync(c->h_i, c->s_act, (size_t)E * 4, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipMemcpyAsync(c->h_f, c->s_logp, (size_t)E * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1438,18 +1444,24 @@ int mi_value_saliency(mi_ctx* c, const void* obs, size_t bytes, uint64_t seed, u
     c->sal_keep_x = rec;
     net_forward(c, src, E, rec, true, true);          // recurrent: h' = GRU(embedder output, h (1 - done)) as a policy step does, heads on h'
     c->sal_keep_x = false;
-    launch_sample(c->hout, E, c->A, du, seed, counter, c->s_act, c->s_logp, c->s_val, c->stream);
+    launch_sample(c->hout, E, c->A, du, seed, counter, c->s_act, c->s_logp, c->s_val, c->stream, c->lse);
     c->sal_src = nullptr;
     if (rec) {
         // value = w_v . h' + b_v: back through the GRU cell to its input x (common/model.py:219-225 under autograd, agents/ppo.py:88-89), then
         // through the embedder's final ReLU (IMPALA) -- d value / d x = dgates W_ih -- and on down the usual backward pass from dfeat
+        // (value_from_logits: value = logsumexp(W_pi h' + b_pi), so the seed into the cell is per row, softmax(logits) W_pi; dfeat carries it)
+        if (c->lse) {
+            launch_lse_hidden_seed(c->hout, c->params + c->wh_off, c->dfeat, E, c->H, c->A, c->stream);
+            launch_gru_value_bwd(c->gru_gi, c->gru_gh, c->h_masked, c->dfeat, c->gru_dg, E, c->H, c->stream, 1);
+        } else
         launch_gru_value_bwd(c->gru_gi, c->gru_gh, c->h_masked, c->params + c->wh_off + (size_t)c->A * c->H, c->gru_dg, E, c->H, c->stream);
         linear_dgrad(c, c->gru_dg, c->gru_wih, impala ? c->gru_x : nullptr, c->dfeat, E, c->H, 3 * c->H);
         c->bwd_from_dfeat = true;
         net_backward(c, src, E);
         c->bwd_from_dfeat = false;
     } else {
-        launch_value_seed(c->dY, E, c->A, c->stream);
+        if (c->lse) launch_lse_value_seed(c->hout, c->dY, E, c->A, c->stream);
+        else launch_value_seed(c->dY, E, c->A, c->stream);
         net_backward(c, src, E);
     }
     ARG(c->sal_src, "backward did not reach the first layer");
@@ -1571,14 +1583,15 @@ static int forward_common(mi_ctx* c, const void* obs, int32_t n, bool recurrent,
     HIPC(hipMemcpyAsync(stage, obs, (size_t)n * c->obs_bytes_per_env, hipMemcpyHostToDevice, c->stream));
     InputSrc src{stage, nullptr, 0};
     net_forward(c, src, n, recurrent);
-    launch_logp_all(c->hout, n, c->A, c->d_lp, nullptr, c->stream);
+    launch_logp_all(c->hout, n, c->A, c->d_lp, c->lse ? c->d_val : nullptr, c->stream, c->lse);
     HIPC(hipGetLastError()); NETCHK(c);
     if (logp_all) HIPC(hipMemcpyAsync(logp_all, c->d_lp, (size_t)n * c->A * 4, hipMemcpyDeviceToHost, c->stream));
     if (feat) HIPC(hipMemcpyAsync(feat, c->feat, (size_t)n * c->H * 4, hipMemcpyDeviceToHost, c->stream));
     std::vector<float> h;
-    if (value) { h.resize((size_t)n * (c->A + 1)); HIPC(hipMemcpyAsync(h.data(), c->hout, h.size() * 4, hipMemcpyDeviceToHost, c->stream)); }
+    if (value && c->lse) HIPC(hipMemcpyAsync(value, c->d_val, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));      // (column A of hout is fc_value's output, not the value)
+    else if (value) { h.resize((size_t)n * (c->A + 1)); HIPC(hipMemcpyAsync(h.data(), c->hout, h.size() * 4, hipMemcpyDeviceToHost, c->stream)); }
     HIPC(hipStreamSynchronize(c->stream));
-    if (value) for (int k = 0; k < n; ++k) value[k] = h[(size_t)k * (c->A + 1) + c->A];
+    if (value && !c->lse) for (int k = 0; k < n; ++k) value[k] = h[(size_t)k * (c->A + 1) + c->A];
     return 0;
 }
 
@@ -1660,6 +1673,7 @@ static int minibatch_impl(mi_ctx* c, const int64_t* idx, int32_t n, const int32_
     a.hout = c->hout; a.idx = c->d_idx; a.act = c->act; a.old_logp = c->logp; a.old_value = c->value; a.ret = c->ret; a.adv = c->adv;
     a.dY = c->dY; a.partial = c->loss_partial; a.stats = c->loss_stats; a.n = n; a.A = c->A;
     a.inv_n_global = 1.0f / (float)n_global;
+    a.value_from_logits = c->lse;
     a.hp = LossHP{hp->eps_clip, hp->value_coef, hp->entropy_coef, hp->x_entropy_coef, hp->entropy_multiplier, hp->fs_coef};
     if (c->multirank == 2)
         // deferred statistics: nothing in the backward pass needs the cross-rank sums when x_entropy_coef == 0 and fs_coef == 0, so this
@@ -1850,6 +1864,7 @@ int mi_set_gru_adam_state(mi_ctx* c, const float* m, const float* v, int64_t n) 
 int mi_minibatch_rec(mi_ctx* c, const int64_t* env_idx, int32_t n_env, const float* h0, int32_t n_global, const mi_hparams* hp) {
     ARG(c && hp && env_idx && h0, "null"); JOIN(c);
     ARG(c->gru_train, "GRU training is off: call mi_gru_train first");
+    ARG(!c->lse, "value_from_logits with a trained GRU (recurrent ppo-pure) is not supported");
     ARG(hp->fs_coef == 0.f, "algo ppo-pure has no feature-sparsity term: fs_coef must be 0");
     ARG(c->multirank == 0 && !c->ar_armed && !c->comm, "GRU training runs on a single rank: multirank modes 1 / 2 and the in-library gradient exchange are refused");
     ARG(n_env >= 1 && n_global >= 1, "n_env / n_global");
@@ -2430,7 +2445,7 @@ int mi_debug_step_latency(mi_ctx* c, int32_t t, int32_t iters, int32_t mode, flo
         c->prof.phase = 0;
         net_forward(c, src, E, true, false);
         launch_heads_sample(c->feat, c->params + c->wh_off, c->params + c->bh_off, E, c->H, c->A, nullptr, 1234ull, (unsigned long long)t * E,
-                            nullptr, nullptr, c->value + (size_t)t * E, c->h_pack, nullptr, nullptr, nullptr, nullptr, c->stream);
+                            nullptr, nullptr, c->value + (size_t)t * E, c->h_pack, nullptr, nullptr, nullptr, nullptr, c->stream, nullptr, nullptr, 0, c->lse);
     };
     const bool prof_on = c->prof.on; c->prof.on = false;       // (no event records inside a capture)
     issue();                                                   // warm: packed banks in place, lazy function attributes set

@@ -576,12 +576,16 @@ void launch_fill(float* p, long long n, float v, hipStream_t st) {
 __device__ __forceinline__ float philox_uniform(unsigned long long seed, unsigned long long ctr);
 struct SampleTerms {
     float lp[MAXA], p[MAXA];
+    float q1[MAXA];           // value_from_logits only: softmax of the raw logits (the FIRST normalisation) = d logsumexp / d logit
     float H, ratio, adv, surr1, surr2, v, oldv, ret, vclip, vs1, vs2;
     int act;
 };
 // (All loops over the actions run to the compile-time MAXA under `k < A`: with a run-time bound the per-thread arrays are indexed
 // dynamically and live in scratch memory -- 180 B per thread, the loss kernel then took 35 us for 8192 samples.)
-__device__ __forceinline__ void log_softmax_twice(const float* z, int A, float* lp, float* p) {
+// LSE (mi_config.value_from_logits; common/policy.py:77-78, v = logits.logsumexp(-1)): also hands out lse = mx + log sum exp(z - mx) of
+// the first pass and q1 = exp(z - lse), its softmax.  Off: lse / q1 are not touched and the code is the two-output form.
+template <bool LSE>
+__device__ __forceinline__ void log_softmax_twice_t(const float* z, int A, float* lp, float* p, float& lse_out, float* q1) {
     float mx = z[0];
 #pragma unroll
     for (int a = 1; a < MAXA; ++a) if (a < A) mx = fmaxf(mx, z[a]);
@@ -591,7 +595,8 @@ __device__ __forceinline__ void log_softmax_twice(const float* z, int A, float* 
     const float lse = mx + logf(s);
     float s2 = 0.f;
 #pragma unroll
-    for (int a = 0; a < MAXA; ++a) if (a < A) { lp[a] = z[a] - lse; s2 += expf(lp[a]); }
+    for (int a = 0; a < MAXA; ++a) if (a < A) { lp[a] = z[a] - lse; const float e1 = expf(lp[a]); s2 += e1; if (LSE) q1[a] = e1; }
+    if (LSE) lse_out = lse;
     const float lse2 = logf(s2);                 // Categorical(logits=log_probs) normalises again (policy.py:86-87)
     float s3 = 0.f;
 #pragma unroll
@@ -599,16 +604,18 @@ __device__ __forceinline__ void log_softmax_twice(const float* z, int A, float* 
 #pragma unroll
     for (int a = 0; a < MAXA; ++a) if (a < A) p[a] /= s3;       // Categorical.probs = softmax(logits)
 }
+template <bool LSE>
 __device__ __forceinline__ void sample_terms(const LossArgs& a, int s, SampleTerms& t) {
     const float* h = a.hout + (long long)s * (a.A + 1);
     float z[MAXA];
 #pragma unroll
     for (int k = 0; k < MAXA; ++k) z[k] = (k < a.A) ? h[k] : 0.f;
-    log_softmax_twice(z, a.A, t.lp, t.p);
+    float lse = 0.f;
+    log_softmax_twice_t<LSE>(z, a.A, t.lp, t.p, lse, t.q1);
     const int gi = a.idx[s];
     t.act = a.act[gi];
     t.adv = a.adv[gi]; t.ret = a.ret[gi]; t.oldv = a.old_value[gi];
-    t.v = h[a.A];
+    t.v = LSE ? lse : h[a.A];       // LSE: column A (fc_value's output) is not part of the model's value
     float H = 0.f, lp_act = 0.f;
 #pragma unroll
     for (int k = 0; k < MAXA; ++k) if (k < a.A) { H -= t.p[k] * t.lp[k]; lp_act = (k == t.act) ? t.lp[k] : lp_act; }
@@ -626,8 +633,18 @@ __device__ __forceinline__ void sample_terms(const LossArgs& a, int s, SampleTer
 constexpr int LOSS_BLK = 64;
 int loss_blocks(int n) { return (n + LOSS_BLK - 1) / LOSS_BLK; }
 
+// LSE: the value-loss gradient enters the logits through d v / d logit_k = q1[k]; the value column of dY is zero, which makes fc_value's
+// weight and bias gradient exact zeros in the heads' backward.
+template <bool LSE>
 __device__ __forceinline__ void loss_bwd_sample(const LossArgs& a, int s, const SampleTerms& t) {
     const float ib = a.inv_n_global;
+    const float dvl = t.v - t.oldv;
+    const float inr = (dvl >= -a.hp.eps_clip && dvl <= a.hp.eps_clip) ? 1.f : 0.f;
+    float gv;
+    if (t.vs1 > t.vs2) gv = 2.f * (t.v - t.ret);
+    else if (t.vs2 > t.vs1) gv = 2.f * (t.vclip - t.ret) * inr;
+    else gv = (t.v - t.ret) + (t.vclip - t.ret) * inr;
+    const float gvc = a.hp.value_coef * 0.5f * ib * gv;
     // d pi_loss / d logp_act  (torch.min routes to surr1 on <=; a tie is the unclipped regime where both
     // branches carry adv/2 each; clamp passes gradient inside [1-eps, 1+eps])
     const float g_lp = -ib * ((t.surr1 <= t.surr2) ? t.adv : 0.f) * t.ratio;
@@ -645,27 +662,23 @@ __device__ __forceinline__ void loss_bwd_sample(const LossArgs& a, int s, const 
         float gk = g_lp * ((k == t.act ? 1.f : 0.f) - t.p[k]);
         gk += cH * (-t.p[k] * (t.lp[k] + t.H));
         if (xe) gk += a.hp.x_entropy_coef * ib * t.p[k] * (lq[k] - plq);
+        if (LSE) gk += gvc * t.q1[k];
         d[k] = gk;
     }
-    const float dvl = t.v - t.oldv;
-    const float inr = (dvl >= -a.hp.eps_clip && dvl <= a.hp.eps_clip) ? 1.f : 0.f;
-    float gv;
-    if (t.vs1 > t.vs2) gv = 2.f * (t.v - t.ret);
-    else if (t.vs2 > t.vs1) gv = 2.f * (t.vclip - t.ret) * inr;
-    else gv = (t.v - t.ret) + (t.vclip - t.ret) * inr;
-    d[a.A] = a.hp.value_coef * 0.5f * ib * gv;
+    d[a.A] = LSE ? 0.f : gvc;
 }
+template <bool LSE>
 __global__ __launch_bounds__(LOSS_BLK) void loss_bwd_kernel(LossArgs a) {
     const int s = blockIdx.x * LOSS_BLK + threadIdx.x;
     if (s >= a.n) return;
     SampleTerms t;
-    sample_terms(a, s, t);
-    loss_bwd_sample(a, s, t);
+    sample_terms<LSE>(a, s, t);
+    loss_bwd_sample<LSE>(a, s, t);
 }
 // one LOSS_BLK-sample block of the loss: sums over the samples s < s_end of this block -> partial row `row` (per value: wave sums,
 // then the waves in order, one barrier per block).  BWD: the loss has no
 // batch-level term (x_entropy_coef == 0), so the gradient of the sample goes out in the same pass.
-template <bool BWD>
+template <bool BWD, bool LSE>
 __device__ __forceinline__ void loss_fwd_block(const LossArgs& a, int s, int s_end, int row) {
     constexpr int NW = LOSS_BLK / 64;
     __shared__ float sw[NW][8 + MAXA];
@@ -675,13 +688,13 @@ __device__ __forceinline__ void loss_fwd_block(const LossArgs& a, int s, int s_e
 #pragma unroll
     for (int k = 0; k < MAXA; ++k) pa[k] = 0.f;
     if (s < s_end) {
-        sample_terms(a, s, t);
+        sample_terms<LSE>(a, s, t);
         pi = fminf(t.surr1, t.surr2);
         vm = fmaxf(t.vs1, t.vs2);
         H = t.H;
 #pragma unroll
         for (int k = 0; k < MAXA; ++k) if (k < a.A) pa[k] = t.p[k];
-        if (BWD) loss_bwd_sample(a, s, t);
+        if (BWD) loss_bwd_sample<LSE>(a, s, t);
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     float r = wave_sum(pi); if (lane == 0) sw[w][0] = r;
@@ -698,8 +711,9 @@ __device__ __forceinline__ void loss_fwd_block(const LossArgs& a, int s, int s_e
         a.partial[(long long)row * (8 + a.A) + k] = t;
     }
 }
+template <bool LSE>
 __global__ __launch_bounds__(LOSS_BLK) void loss_fwd_kernel(LossArgs a) {
-    loss_fwd_block<false>(a, blockIdx.x * LOSS_BLK + threadIdx.x, a.n, blockIdx.x);
+    loss_fwd_block<false, LSE>(a, blockIdx.x * LOSS_BLK + threadIdx.x, a.n, blockIdx.x);
 }
 // segment k owns ceil(len_k / LOSS_BLK) consecutive blocks (no block straddles two minibatches)
 __device__ __forceinline__ void seg_of_block(const SegTab& st, int b, int& k, int& first) {
@@ -710,11 +724,11 @@ __device__ __forceinline__ void seg_of_block(const SegTab& st, int b, int& k, in
         first += nb;
     }
 }
-template <bool BWD>
+template <bool BWD, bool LSE>
 __global__ __launch_bounds__(LOSS_BLK) void loss_fwd_seg_kernel(LossArgs a, SegTab st) {
     int k, first;
     seg_of_block(st, blockIdx.x, k, first);
-    loss_fwd_block<BWD>(a, st.start[k] + (blockIdx.x - first) * LOSS_BLK + threadIdx.x, st.start[k + 1], blockIdx.x);
+    loss_fwd_block<BWD, LSE>(a, st.start[k] + (blockIdx.x - first) * LOSS_BLK + threadIdx.x, st.start[k + 1], blockIdx.x);
 }
 int loss_blocks_seg(const SegTab& st) {
     int nb = 0;
@@ -724,12 +738,16 @@ int loss_blocks_seg(const SegTab& st) {
 void launch_loss_fwd_seg(const LossArgs& a, const SegTab& st, bool with_bwd, hipStream_t stream) {
     const int nb = loss_blocks_seg(st);
     if (nb <= 0) return;
-    if (with_bwd) hipLaunchKernelGGL(loss_fwd_seg_kernel<true>, dim3(nb), dim3(LOSS_BLK), 0, stream, a, st);
-    else hipLaunchKernelGGL(loss_fwd_seg_kernel<false>, dim3(nb), dim3(LOSS_BLK), 0, stream, a, st);
+    if (a.value_from_logits) {
+        if (with_bwd) hipLaunchKernelGGL((loss_fwd_seg_kernel<true, true>), dim3(nb), dim3(LOSS_BLK), 0, stream, a, st);
+        else hipLaunchKernelGGL((loss_fwd_seg_kernel<false, true>), dim3(nb), dim3(LOSS_BLK), 0, stream, a, st);
+    } else if (with_bwd) hipLaunchKernelGGL((loss_fwd_seg_kernel<true, false>), dim3(nb), dim3(LOSS_BLK), 0, stream, a, st);
+    else hipLaunchKernelGGL((loss_fwd_seg_kernel<false, false>), dim3(nb), dim3(LOSS_BLK), 0, stream, a, st);
 }
 void launch_loss_fwd(const LossArgs& a, hipStream_t st) {
     if (a.n <= 0) return;
-    hipLaunchKernelGGL(loss_fwd_kernel, dim3(loss_blocks(a.n)), dim3(LOSS_BLK), 0, st, a);
+    if (a.value_from_logits) hipLaunchKernelGGL(loss_fwd_kernel<true>, dim3(loss_blocks(a.n)), dim3(LOSS_BLK), 0, st, a);
+    else hipLaunchKernelGGL(loss_fwd_kernel<false>, dim3(loss_blocks(a.n)), dim3(LOSS_BLK), 0, st, a);
 }
 
 // phase 1: block partials -> this rank's contribution to the GLOBAL-minibatch means (x inv_n_global)
@@ -807,7 +825,8 @@ void launch_loss_finalize(const LossArgs& a, int nblk, int phase, const float* f
 
 void launch_loss_bwd(const LossArgs& a, hipStream_t st) {
     if (a.n <= 0) return;
-    hipLaunchKernelGGL(loss_bwd_kernel, dim3(loss_blocks(a.n)), dim3(LOSS_BLK), 0, st, a);
+    if (a.value_from_logits) hipLaunchKernelGGL(loss_bwd_kernel<true>, dim3(loss_blocks(a.n)), dim3(LOSS_BLK), 0, st, a);
+    else hipLaunchKernelGGL(loss_bwd_kernel<false>, dim3(loss_blocks(a.n)), dim3(LOSS_BLK), 0, st, a);
 }
 
 // feature-sparsity metric (common/model.py:207): mean_j max_b tanh(|100*relu(h_bj)|)
@@ -1108,6 +1127,7 @@ void launch_advnorm_apply(float* adv, int n, const double* stats3, hipStream_t s
 // ------------------------------------------------------------------------------------------ rollout head: sample
 // agents/ppo.py:77-79: dist.sample(), dist.log_prob(act).  Inverse-CDF over the A probabilities with a
 // uniform from a caller-supplied array (tests) or Philox4x32-10 keyed by (seed, counter + env).
+template <bool LSE>
 __global__ void sample_kernel(const float* hout, int n, int A, const float* u, unsigned long long seed,
                               unsigned long long ctr, int32_t* act, float* logp, float* value) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1115,7 +1135,8 @@ __global__ void sample_kernel(const float* hout, int n, int A, const float* u, u
     const float* h = hout + (long long)e * (A + 1);
     float z[MAXA], lp[MAXA], p[MAXA];
     for (int k = 0; k < A; ++k) z[k] = h[k];
-    log_softmax_twice(z, A, lp, p);
+    float lse = 0.f, q1[MAXA];
+    log_softmax_twice_t<LSE>(z, A, lp, p, lse, q1);
     const float uu = u ? u[e] : philox_uniform(seed, ctr + e);
     float cdf = 0.f;
     int a_sel = 0;
@@ -1123,21 +1144,24 @@ __global__ void sample_kernel(const float* hout, int n, int A, const float* u, u
     if (a_sel > A - 1) a_sel = A - 1;
     if (act) act[e] = a_sel;
     if (logp) logp[e] = lp[a_sel];
-    if (value) value[e] = h[A];
+    if (value) value[e] = LSE ? lse : h[A];
 }
+template <bool LSE>
 __global__ void logp_all_kernel(const float* hout, int n, int A, float* lp_out, float* value_out) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
     const float* h = hout + (long long)e * (A + 1);
     float z[MAXA], lp[MAXA], p[MAXA];
     for (int k = 0; k < A; ++k) z[k] = h[k];
-    log_softmax_twice(z, A, lp, p);
+    float lse = 0.f, q1[MAXA];
+    log_softmax_twice_t<LSE>(z, A, lp, p, lse, q1);
     if (lp_out) for (int k = 0; k < A; ++k) lp_out[(long long)e * A + k] = lp[k];
-    if (value_out) value_out[e] = h[A];
+    if (value_out) value_out[e] = LSE ? lse : h[A];
 }
-void launch_logp_all(const float* hout, int n, int A, float* lp_out, float* value_out, hipStream_t st) {
+void launch_logp_all(const float* hout, int n, int A, float* lp_out, float* value_out, hipStream_t st, int value_from_logits) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(logp_all_kernel, dim3((n + 63) / 64), dim3(64), 0, st, hout, n, A, lp_out, value_out);
+    if (value_from_logits) hipLaunchKernelGGL(logp_all_kernel<true>, dim3((n + 63) / 64), dim3(64), 0, st, hout, n, A, lp_out, value_out);
+    else hipLaunchKernelGGL(logp_all_kernel<false>, dim3((n + 63) / 64), dim3(64), 0, st, hout, n, A, lp_out, value_out);
 }
 __device__ __forceinline__ void philox_round(uint32_t* c, uint32_t* k) {
     const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
@@ -1184,7 +1208,11 @@ void launch_philox_debug(const uint32_t* in6, int n, uint32_t* out4, float* u_ou
 // log_softmax_twice + CDF walk of sample_kernel.
 // WIDE (H > 256: IMPALA output_dim up to 512, any MLP latent_size): features and head rows are staged in K chunks of 256 through the
 // same LDS rows, each dot product carried across the chunks in the same order of operations as the single-chunk loop.
-template <bool WIDE>
+// LSE (mi_config.value_from_logits): the value is mx + log(s1) of the first normalisation below -- the same sums in the same order as
+// log_softmax_twice_t<true>, so GIVEN THE SAME LOGITS it is the number sample_kernel / logp_all_kernel / the loss compute.  This kernel's
+// logits are its own dot products, taken in another order than the GEMM's that feeds those kernels, so across the two paths the values
+// agree to a few ulp, not bit for bit (as the logits do with the flag off).  Column A of hout stays fc_value's output.
+template <bool WIDE, bool LSE>
 __global__ __launch_bounds__(256) void heads_sample_kernel(const float* __restrict__ feat, const float* __restrict__ Wh,
                                                            const float* __restrict__ bh, int n, int H, int A, const float* u,
                                                            unsigned long long seed, unsigned long long ctr, int32_t* act,
@@ -1322,7 +1350,8 @@ __global__ __launch_bounds__(256) void heads_sample_kernel(const float* __restri
         for (int k = 1; k < 16; ++k) if (k < A) mx = fmaxf(mx, v[k]);
     }
     const float s1 = group_sum(lane_on ? expf(z - mx) : 0.f);
-    float lp = z - (mx + logf(s1));
+    const float lse1 = mx + logf(s1);
+    float lp = z - lse1;
     const float s2 = group_sum(lane_on ? expf(lp) : 0.f);
     lp -= logf(s2);                                        // Categorical(logits=log_probs) normalises again (policy.py:86-87)
     const float pr = lane_on ? expf(lp) : 0.f;
@@ -1353,7 +1382,7 @@ __global__ __launch_bounds__(256) void heads_sample_kernel(const float* __restri
         for (int k = 1; k < 16; ++k) lp_pick = (k == a_sel) ? v[k] : lp_pick;
     }
     if (o == 0 && e < n) {
-        const float lp_sel = lp_pick, val = s_z[el * 17 + A];
+        const float lp_sel = lp_pick, val = LSE ? lse1 : s_z[el * 17 + A];
         if (rd) { rew_dst[e] = rwd; done_dst[e] = dn; }        // previous step's reward / done into the (T,E) arrays
         if (act) act[e] = a_sel;
         if (logp) logp[e] = lp_sel;
@@ -1379,19 +1408,21 @@ __global__ __launch_bounds__(256) void heads_sample_kernel(const float* __restri
 void launch_heads_sample(const float* feat, const float* Wh, const float* bh, int n, int H, int A, const float* u,
                          unsigned long long seed, unsigned long long ctr, int32_t* act, float* logp, float* value, float* pack,
                          float* hout, const float* rd, float* rew_dst, float* done_dst, hipStream_t st,
-                         unsigned* done_ctr, unsigned* host_flag, unsigned ticket) {
+                         unsigned* done_ctr, unsigned* host_flag, unsigned ticket, int value_from_logits) {
     if (n <= 0) return;
-    if (H > 256)
-        hipLaunchKernelGGL(heads_sample_kernel<true>, dim3((n + 15) / 16), dim3(256), 0, st, feat, Wh, bh, n, H, A, u, seed, ctr, act, logp, value, pack, hout,
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((n + 15) / 16), dim3(256), 0, st, feat, Wh, bh, n, H, A, u, seed, ctr, act, logp, value, pack, hout,
                            rd, rew_dst, done_dst, done_ctr, host_flag, ticket);
-    else
-        hipLaunchKernelGGL(heads_sample_kernel<false>, dim3((n + 15) / 16), dim3(256), 0, st, feat, Wh, bh, n, H, A, u, seed, ctr, act, logp, value, pack, hout,
-                           rd, rew_dst, done_dst, done_ctr, host_flag, ticket);
+    };
+    if (value_from_logits) { if (H > 256) go(heads_sample_kernel<true, true>); else go(heads_sample_kernel<false, true>); }
+    else if (H > 256) go(heads_sample_kernel<true, false>);
+    else go(heads_sample_kernel<false, false>);
 }
 void launch_sample(const float* hout, int n, int A, const float* u, unsigned long long seed, unsigned long long ctr,
-                   int32_t* act, float* logp, float* value, hipStream_t st) {
+                   int32_t* act, float* logp, float* value, hipStream_t st, int value_from_logits) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(sample_kernel, dim3((n + 63) / 64), dim3(64), 0, st, hout, n, A, u, seed, ctr, act, logp, value);
+    if (value_from_logits) hipLaunchKernelGGL(sample_kernel<true>, dim3((n + 63) / 64), dim3(64), 0, st, hout, n, A, u, seed, ctr, act, logp, value);
+    else hipLaunchKernelGGL(sample_kernel<false>, dim3((n + 63) / 64), dim3(64), 0, st, hout, n, A, u, seed, ctr, act, logp, value);
 }
 
 // ------------------------------------------------------------------------------------------ clip + Adam
@@ -1526,6 +1557,8 @@ __global__ void gru_gates_kernel(const float* gi, const float* gh, const float* 
 // d value / d (GRU input pre-activations): value = w_v . h' + b_v with h' = (1 - z) n + z h (gates as in gru_gates_kernel), so with
 // g = w_v[j]:  dn = g (1 - z), dz = g (h - n);  d pre_n = dn (1 - n^2), d pre_z = dz z (1 - z), d pre_r = d pre_n gh_n r (1 - r).
 // dgates[row] = {d pre_r, d pre_z, d pre_n} (3H): the gradient wrt gi = W_ih x + b_ih; dx = dgates W_ih follows as a GEMM.
+// ROWSEED (value_from_logits): d value / d h' differs from row to row -- wv is [n][H] (lse_hidden_seed_kernel) instead of fc_value's one weight row.
+template <bool ROWSEED>
 __global__ void gru_value_bwd_kernel(const float* gi, const float* gh, const float* hm, const float* wv, float* dgates, int n, int H) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n * H) return;
@@ -1535,16 +1568,17 @@ __global__ void gru_value_bwd_kernel(const float* gi, const float* gh, const flo
     const float r = 1.f / (1.f + expf(-(a[j] + b[j])));
     const float z = 1.f / (1.f + expf(-(a[H + j] + b[H + j])));
     const float nn = tanhf(a[2 * H + j] + r * b[2 * H + j]);
-    const float g = wv[j];
+    const float g = ROWSEED ? wv[e] : wv[j];
     const float dpn = g * (1.f - z) * (1.f - nn * nn);
     const float dpz = g * (hm[e] - nn) * z * (1.f - z);
     const float dpr = dpn * b[2 * H + j] * r * (1.f - r);
     float* d = dgates + (long long)row * 3 * H;
     d[j] = dpr; d[H + j] = dpz; d[2 * H + j] = dpn;
 }
-void launch_gru_value_bwd(const float* gi, const float* gh, const float* hm, const float* wv, float* dgates, int n, int H, hipStream_t st) {
+void launch_gru_value_bwd(const float* gi, const float* gh, const float* hm, const float* wv, float* dgates, int n, int H, hipStream_t st, int row_seed) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(gru_value_bwd_kernel, dim3((n * H + 255) / 256), dim3(256), 0, st, gi, gh, hm, wv, dgates, n, H);
+    if (row_seed) hipLaunchKernelGGL(gru_value_bwd_kernel<true>, dim3((n * H + 255) / 256), dim3(256), 0, st, gi, gh, hm, wv, dgates, n, H);
+    else hipLaunchKernelGGL(gru_value_bwd_kernel<false>, dim3((n * H + 255) / 256), dim3(256), 0, st, gi, gh, hm, wv, dgates, n, H);
 }
 void launch_gru_gates(const float* gi, const float* gh, const float* hm, float* h_out, float* feat_out, int n, int H, hipStream_t st) {
     if (n <= 0) return;
@@ -1635,6 +1669,45 @@ __global__ void value_seed_kernel(float* dY, int n, int A) {
 void launch_value_seed(float* dY, int n, int A, hipStream_t st) {
     if (n <= 0) return;
     hipLaunchKernelGGL(value_seed_kernel, dim3((n * (A + 1) + 255) / 256), dim3(256), 0, st, dY, n, A);
+}
+// value_from_logits: value = logsumexp(logits), so value.backward() seeds the A logit columns of dY with softmax(logits) (the first
+// normalisation, q1 of log_softmax_twice_t) and the value column with 0.  One thread per row.
+__global__ void lse_value_seed_kernel(const float* hout, float* dY, int n, int A) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const float* h = hout + (long long)e * (A + 1);
+    float z[MAXA], lp[MAXA], p[MAXA], q1[MAXA], lse;
+#pragma unroll
+    for (int k = 0; k < MAXA; ++k) z[k] = (k < A) ? h[k] : 0.f;
+    log_softmax_twice_t<true>(z, A, lp, p, lse, q1);
+    float* d = dY + (long long)e * (A + 1);
+#pragma unroll
+    for (int k = 0; k < MAXA; ++k) if (k < A) d[k] = q1[k];
+    d[A] = 0.f;
+}
+void launch_lse_value_seed(const float* hout, float* dY, int n, int A, hipStream_t st) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(lse_value_seed_kernel, dim3((n + 63) / 64), dim3(64), 0, st, hout, dY, n, A);
+}
+// The same seed one layer down, for a recurrent policy (the heads sit on h'): seed[e][j] = d value_e / d h'_{e,j} = sum_k q1_{e,k} W_pi[k][j],
+// no ReLU mask (h' is the GRU's output).  One thread per (row, unit); the row's A logits are re-normalised by each of its threads.
+__global__ void lse_hidden_seed_kernel(const float* hout, const float* Wh, float* seed, int n, int H, int A) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long long)n * H) return;
+    const int row = (int)(e / H), j = (int)(e % H);
+    const float* h = hout + (long long)row * (A + 1);
+    float z[MAXA], lp[MAXA], p[MAXA], q1[MAXA], lse;
+#pragma unroll
+    for (int k = 0; k < MAXA; ++k) z[k] = (k < A) ? h[k] : 0.f;
+    log_softmax_twice_t<true>(z, A, lp, p, lse, q1);
+    float g = 0.f;
+#pragma unroll
+    for (int k = 0; k < MAXA; ++k) if (k < A) g += q1[k] * Wh[(long long)k * H + j];
+    seed[e] = g;
+}
+void launch_lse_hidden_seed(const float* hout, const float* Wh, float* seed, int n, int H, int A, hipStream_t st) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(lse_hidden_seed_kernel, dim3((unsigned)(((long long)n * H + 255) / 256)), dim3(256), 0, st, hout, Wh, seed, n, H, A);
 }
 template <bool BF>
 __global__ __launch_bounds__(256) void conv1_input_grad_kernel(const void* dC, const float* __restrict__ W, float* __restrict__ dX, int n) {

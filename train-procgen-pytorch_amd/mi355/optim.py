@@ -20,6 +20,9 @@ class DeviceAdam:
         # never receives gradients there, so it never gets optimiser state either)
         self._adam = optim.Adam(list(policy.parameters()), lr=lr, eps=eps)
         self.step_count = 0
+        # logsumexp_logits_is_v: fc_value never receives a gradient (policy.py:77-78), so torch's Adam never creates state for it -- like
+        # the frozen GRU it stays in param_groups and out of `state`; the device moments of its slice are and stay zero
+        self._stateless = {"fc_value.weight", "fc_value.bias"} if getattr(policy, "logsumexp_logits_is_v", False) else set()
 
     @property
     def param_groups(self):
@@ -47,6 +50,8 @@ class DeviceAdam:
             m, v = self.engine.get_adam_state()
             m, v = layout.unflatten(shapes, m), layout.unflatten(shapes, v)
             for n, p in zip(self._names, self._params):
+                if n in self._stateless:
+                    continue
                 self._adam.state[p] = {'step': torch.tensor(float(self.step_count)),
                                        'exp_avg': torch.from_numpy(m[n]), 'exp_avg_sq': torch.from_numpy(v[n])}
             if self._gru_trained():
@@ -68,13 +73,20 @@ class DeviceAdam:
         st = self._adam.state
         if len(st) == 0:
             return
-        m = {n: st[p]['exp_avg'].numpy() for n, p in zip(self._names, self._params)}
-        v = {n: st[p]['exp_avg_sq'].numpy() for n, p in zip(self._names, self._params)}
+        import numpy as np
+        zeros = lambda n: np.zeros(shapes[n], np.float32)
+        # fc_value's moments are zero in this mode whatever the file holds: a state written in this mode has no entries for it, and one
+        # written with the fc_value head (the flag off) carries moments that would go on moving the parameter under a zero gradient
+        # (m / (sqrt(v) + eps) != 0).  Such entries are dropped, so that state_dict() gives this mode's layout again.
+        for n, p in zip(self._names, self._params):
+            if n in self._stateless:
+                st.pop(p, None)
+        m = {n: zeros(n) if n in self._stateless else st[p]['exp_avg'].numpy() for n, p in zip(self._names, self._params)}
+        v = {n: zeros(n) if n in self._stateless else st[p]['exp_avg_sq'].numpy() for n, p in zip(self._names, self._params)}
         self.engine.set_adam_state(layout.flatten(shapes, m), layout.flatten(shapes, v))
         if self._gru_trained():
             gp = self.policy.gru_parameters()
             if all(p in st for p in gp):
-                import numpy as np
                 self.engine.set_gru_adam_state(np.concatenate([st[p]['exp_avg'].numpy().ravel() for p in gp]),
                                                np.concatenate([st[p]['exp_avg_sq'].numpy().ravel() for p in gp]))
-        self.step_count = int(float(st[self._params[0]]['step']))
+        self.step_count = int(float(next(st[p]['step'] for p in self._params if p in st)))

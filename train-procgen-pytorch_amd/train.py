@@ -208,7 +208,8 @@ def initialize_model(device, env, hp):
         model = MLPModel(obs_shape[0], hp.get("depth", 4), hp.get("mid_weight", 64), hp.get("latent_size", 256))
     else:
         raise NotImplementedError(f"Architecture:{arch} is not on the accelerated path")
-    policy = CategoricalPolicy(model, hp.get('recurrent', False), env.action_space.n)
+    policy = CategoricalPolicy(model, hp.get('recurrent', False), env.action_space.n,
+                               logsumexp_logits_is_v=hp.get('logsumexp_logits_is_v', False))       # (helper_local.py:445-447)
     policy.device = device
     return model, obs_shape, policy
 
