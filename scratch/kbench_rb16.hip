@@ -1,6 +1,7 @@
-// Micro-bench of the whole backward of the 16-channel residual blocks (resblock_bwd_full_bf16_kernel) outside the engine, with checksums of
-// dx and of the two weight-gradient slab sets (A/B of kernel variants: dx must stay bit-identical, the slabs may move in the last bits):
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DRBFULL_WG_REUSE=0] -I train-procgen-pytorch_amd/csrc scratch/kbench_rb16.hip -o scratch/kb_rb16 ; ./kb_rb16 [n]
+// Micro-bench of the whole backward of the 16-channel residual blocks (resblock_bwd_full16d_bf16_kernel) outside the engine, with checksums of
+// dx and of the two weight-gradient slab sets (A/B of kernel builds: dx must stay bit-identical, the slabs may move in the last bits),
+// optionally with the per-phase shader-clock breakdown of the two wave roles:
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DRBF_TIMING] -I train-procgen-pytorch_amd/csrc scratch/kbench_rb16.hip -o scratch/kb_rb16 ; ./kb_rb16 [n]
 #include "resblock_bf16.hip"
 #include <cstdio>
 #include <cstring>
@@ -42,20 +43,12 @@ int main(int argc, char** argv) {
     double s2 = 0, s1 = 0; for (size_t k = 0; k < (size_t)grid * 2320; ++k) { s2 += hs[k]; s1 += hs[(size_t)grid * 2320 + k]; }
     printf("n=%d grid=%d: %.1f us/launch  dx fnv %016llx  slab sums %.6e %.6e  (%s)\n", n, grid, ms * 1000 / reps, cx, s2, s1, hipGetErrorString(hipGetLastError()));
 #ifdef RBF_TIMING
-    if (RBFULL16_SPECIALISED) {
+    {
         unsigned long long t[8]; hipMemcpyFromSymbol(t, HIP_SYMBOL(g_rbf_timing), sizeof t);
-        const char* nm[4] = {"staging (+wait)", "phase-1 work", "wait at mid barrier", "phase-2 work + top wait"};
+        const char* nm[4] = {"DMA issue", "phase-1 work", "wait at mid barrier", "phase-2 work + end wait"};
         const double items = (double)n * RbFull16S::TPI / grid * reps;
         for (int role = 0; role < 2; ++role)
             for (int k = 0; k < 4; ++k) printf("  %s %-24s %8.0f cycles per item\n", role ? "wgrad" : "conv ", nm[k], (double)t[role * 4 + k] / grid / items);
-    } else
-    {   // slot k = cycles between mark k-1 and mark k of wave 0 (slot 0: weight-gradient phase of the previous item + loop back)
-        unsigned long long t[8]; hipMemcpyFromSymbol(t, HIP_SYMBOL(g_rbf_timing), sizeof t);
-        const char* nm[8] = {"wgrad phase (prev item)", "wait top barrier", "stage tiles to LDS", "wait barrier", "issue next loads", "phase A conv (da)", "wait mid barrier", "phase B conv (dx)"};
-        const double items = (double)n * 4 / grid * reps;
-        double tot = 0; for (int k = 0; k < 8; ++k) tot += (double)t[k];
-        for (int k = 0; k < 8; ++k) printf("  %-26s %8.0f cycles per item (%4.1f %%)\n", nm[k], (double)t[k] / grid / items, 100.0 * t[k] / tot);
-        printf("  total %.0f cycles per item per workgroup\n", tot / grid / items);
     }
 #endif
     return 0;

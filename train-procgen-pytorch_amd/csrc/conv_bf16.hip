@@ -174,12 +174,9 @@ struct BfCfg {
     static constexpr int C8 = CIN / 8;
     static constexpr int NLD = (NPIX * C8 + 255) / 256;
     static constexpr size_t LDS_BYTES = (size_t)(IN_ELEMS + W_ELEMS) * 2;
-#ifndef BF_WPE_32_16
-#define BF_WPE_32_16 1
-#endif
     // waves per SIMD the register allocation must leave room for.  The 32-channel 16x16 tiles fit 3 workgroups per CU by LDS
     // (50.6 KB) but compile to 196 registers = 2 waves per SIMD; forcing 3 spills 76 bytes and measured slower (12.3 vs 10.2 ms)
-    static constexpr int WPE = (CIN == 32 && COUT == 32 && HW == 16 && NIMG == 1) ? BF_WPE_32_16 : 1;
+    static constexpr int WPE = 1;
     static_assert(NMT % 4 == 0, "M tiles must split over 4 waves");
 };
 
@@ -756,9 +753,6 @@ __global__ __launch_bounds__(512, 2) void block3_conv_bwd_bf16_kernel(ConvArgs a
         }
     }
 }
-#ifndef B3BWD_FUSED
-#define B3BWD_FUSED 1              // 0: block3.conv's two gradients stay two generic launches
-#endif
 static int b3bwd_grid(int n) { const int w = (n + B3Bwd::NIMG - 1) / B3Bwd::NIMG; return w > 256 ? 256 : w; }
 static void launch_block3_conv_bwd(const ConvArgs& a, hipStream_t st) {
     static std::once_flag attr;
@@ -1445,16 +1439,11 @@ void launch_conv1_pool_fwd_bf16(const ConvArgs& a, const unsigned short* lut16, 
     hipLaunchKernelGGL(conv1_pool_fwd_bf16_kernel, dim3(grid), dim3(256), 0, st, a, lut16, (unsigned short*)p_out, p_arg);
 }
 
-// POOLED: a.dout is the gradient of the POOLED map (32x32x16) and a.pool_arg its arg-max bytes; the conv-output
-// gradient tile is rebuilt in LDS from the 3 pooled rows that touch the 4 conv rows of the item (max-pool backward
-// fused into the staging: no 64x64x16 gradient tensor in HBM).
-template <bool POOLED>
+// block1.conv weight gradient from the conv-output gradient a.dout (64x64x16); from the POOLED gradient: conv1_wgrad_onehot_bf16_kernel.
 __global__ __launch_bounds__(256) void conv1_wgrad_bf16_kernel(WgradArgs a, const unsigned short* lut16) {
     extern __shared__ __attribute__((aligned(16))) unsigned short smem_h[];
     unsigned short* s_in = smem_h;                                   // [396][4]: 3 channels + 1.0
     unsigned short* s_do = smem_h + ((C1W::NPIX * 4 + 7) / 8) * 8;    // [256][16]
-    unsigned short* s_pd = s_do + C1W::NT * 16;                       // POOLED: [3][32][16] pooled gradient
-    uint8_t* s_pa = (uint8_t*)(s_pd + 3 * 32 * 16);                   // POOLED: [3][32][16] arg-max bytes
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, kq = lane >> 4, rq = (lane & 15) >> 2, cp = lane & 3;
     const unsigned short* g_do = (const unsigned short*)a.dout;
 #ifdef WG_TIMING
@@ -1466,20 +1455,13 @@ __global__ __launch_bounds__(256) void conv1_wgrad_bf16_kernel(WgradArgs a, cons
     // Two staging register sets: the loads of item k+2 are issued while item k is processed.  One item lasts ~2.5 us, about one
     // loaded-HBM round trip, so with a single set every item waited for its own data (phases "store" + "issue" = 33 % of the clocks).
     constexpr int NDO = C1W::NT * 2 / 256;                            // NT px x 2 chunks of 8 channels
-    struct Stage { uint32_t regs[C1W::NLD]; uint4 rdo[NDO]; uint2 rpa; };
+    struct Stage { uint32_t regs[C1W::NLD]; uint4 rdo[NDO]; };
     Stage S0, S1;
     auto load_do = [&](Stage& S, int img, int ty0) {
-        if (POOLED) {                                               // 3 pooled rows x 32 x 2 halves = 192 (uint4, uint2) pairs; unconditional,
-            const int pr = tid >> 6, oy = ty0 / 2 + (pr < 2 ? pr : 2);   // clamped: rows past the map are replaced when the registers are stored
-            const size_t o = (((size_t)img * 32 + (oy < 32 ? oy : 31)) * 32) * 16 + (size_t)(tid & 63) * 8;
-            S.rdo[0] = *(const uint4*)(g_do + o);
-            S.rpa = *(const uint2*)(a.pool_arg + o);
-        } else {
 #pragma unroll
-            for (int k = 0; k < NDO; ++k) {
-                const int e = tid + k * 256, pl = e >> 1, c8 = e & 1;
-                S.rdo[k] = *(const uint4*)(g_do + (((long long)img * C1W::HW + ty0 + pl / C1W::TW) * C1W::HW + pl % C1W::TW) * 16 + c8 * 8);
-            }
+        for (int k = 0; k < NDO; ++k) {
+            const int e = tid + k * 256, pl = e >> 1, c8 = e & 1;
+            S.rdo[k] = *(const uint4*)(g_do + (((long long)img * C1W::HW + ty0 + pl / C1W::TW) * C1W::HW + pl % C1W::TW) * 16 + c8 * 8);
         }
     };
     auto item = [&](int w) { return w < nwork ? w : nwork - 1; };          // past the end: the last item again (loads stay unconditional)
@@ -1497,15 +1479,8 @@ __global__ __launch_bounds__(256) void conv1_wgrad_bf16_kernel(WgradArgs a, cons
         __syncthreads();
         TCK(1);
         c1_store<C1W, true>(S.regs, s_in, (work % C1W::TPI) * C1W::TH);
-        if (POOLED) {
-            if (tid < 192) {
-                const bool in = (work % C1W::TPI) * C1W::TH / 2 + (tid >> 6) < 32;      // the third pooled row of an image's last item does not exist
-                *(uint4*)(s_pd + tid * 8) = in ? S.rdo[0] : (uint4){0u, 0u, 0u, 0u}; *(uint2*)(s_pa + tid * 8) = in ? S.rpa : (uint2){0xffffffffu, 0xffffffffu};
-            }
-        } else {
 #pragma unroll
-            for (int k = 0; k < NDO; ++k) { const int e = tid + k * 256; *(uint4*)(s_do + (e >> 1) * 16 + (e & 1) * 8) = S.rdo[k]; }
-        }
+        for (int k = 0; k < NDO; ++k) { const int e = tid + k * 256; *(uint4*)(s_do + (e >> 1) * 16 + (e & 1) * 8) = S.rdo[k]; }
         TCK(2);
         __syncthreads();
         {
@@ -1515,46 +1490,6 @@ __global__ __launch_bounds__(256) void conv1_wgrad_bf16_kernel(WgradArgs a, cons
             c1_load<C1W>(S.regs, (const uint8_t*)a.in, frame, ty0); load_do(S, img, ty0);   // next step needs this index but not these pixels
         }
         TCK(3);
-        if (POOLED) {       // max-pool backward into the LDS tile.  A thread owns a 2x2 block of conv pixels x 4 channels: the
-            // 4 windows (oy, ox) in {a, a+1} x {b, b+1} that touch the block are read once each and their 9 (window, pixel)
-            // incidences -- one per pool position -- are resolved with compile-time (ky, kx); windows are added in
-            // (oy, ox) order, the order of the stand-alone max-pool backward kernel.
-            const int cq = tid & 3, bx = (tid >> 2) & 31, by = tid >> 7;
-            float sm[4][4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) sm[q][c] = 0.f;
-#pragma unroll
-            for (int wy = 0; wy < 2; ++wy)
-#pragma unroll
-                for (int wx = 0; wx < 2; ++wx) {
-                    const int o = ((by + wy) * 32 + bx + wx) * 16 + cq * 4;
-                    const uint2 d = *(const uint2*)(s_pd + o);
-                    unsigned ag = *(const unsigned*)(s_pa + o);
-                    if (wx == 1 && bx == 31) ag = 0xffffffffu;                 // window column 32 does not exist
-                    const float v[4] = {__uint_as_float(d.x << 16), __uint_as_float(d.x & 0xffff0000u), __uint_as_float(d.y << 16), __uint_as_float(d.y & 0xffff0000u)};
-#pragma unroll
-                    for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                        for (int dx = 0; dx < 2; ++dx) {
-                            const int ky = dy + 1 - 2 * wy, kx = dx + 1 - 2 * wx;
-                            if (ky < 0 || kx < 0) continue;
-                            const unsigned pos = (unsigned)(ky * 3 + kx);
-#pragma unroll
-                            for (int c = 0; c < 4; ++c)
-                                sm[dy * 2 + dx][c] += (((ag >> (8 * c)) & 0xffu) == pos) ? v[c] : 0.f;
-                        }
-                }
-#pragma unroll
-            for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                for (int dx = 0; dx < 2; ++dx) {
-                    const float* q = sm[dy * 2 + dx];
-                    *(uint2*)(s_do + ((2 * by + dy) * 64 + 2 * bx + dx) * 16 + cq * 4) =
-                        (uint2){mi_pk_bf16(q[0], q[1]), mi_pk_bf16(q[2], q[3])};
-                }
-        }
         TCK(4);
         TCK(5);
         __syncthreads();
@@ -1606,19 +1541,20 @@ __global__ __launch_bounds__(256) void conv1_wgrad_bf16_kernel(WgradArgs a, cons
     float* slab = a.partial + (long long)blockIdx.x * 448;
     for (int e = tid; e < 448; e += 256) slab[e] = red[e];
 }
-// ---- block1.conv weight gradient from the POOLED gradient in ONE-HOT form (round 3; replaces the gather of conv1_wgrad_bf16_kernel<true>)
+// ---- block1.conv weight gradient from the POOLED gradient in ONE-HOT form
 // dW[co][tap][ci] = sum_p dC[p][co] x[p + tap][ci], and the max-pool backward is dC[p][co] = sum of g[w][co] over the windows w whose
 // arg-max is p.  Substituted:  dW = sum_{w, pos} T[w][pos][co] x[pixel(w, pos) + tap][ci]  with  T[w][pos][co] = (arg[w][co] == pos) ?
 // g[w][co] : 0  -- the pool backward becomes a one-hot EXPANSION of the contraction index (9 K-rows per window: 9216 per image instead
 // of 4096 pixels) whose operand addresses are regular: pixel(w, pos) = (2 oy - 1 + ky, 2 ox - 1 + kx) does not depend on the data.  No
-// gathered dC tile, no compare / select / add per (window position, channel): the old kernel spent ~75 vector instructions per conv
-// pixel there and was VALU-issue-bound at 2.6 TB/s with 8 % of the matrix pipe busy.  Numerically the products g * x are summed in fp32
-// directly (the old form rounded the <= 4 coinciding contributions of a pixel to one bf16 first): closer to the fp32 reference.
+// gathered dC tile, no compare / select / add per (window position, channel): a kernel that rebuilt dC in LDS spent ~75 vector
+// instructions per conv pixel there and was VALU-issue-bound at 2.6 TB/s with 8 % of the matrix pipe busy.  Numerically the products
+// g * x are summed in fp32 directly (a gathered dC rounds the <= 4 coinciding contributions of a pixel to one bf16 first): closer to
+// the fp32 reference.
 //   * item = 4 pooled rows of one image (8 items per image); wave r owns pooled row r: 8 K-steps of 4 windows x positions 0..7 and one
 //     K-step of 32 windows x position 8;
 //   * positions 0..7 -- the A operand (16 channels x 32 K-rows) is built in REGISTERS: lane (co, kq) reads g and arg of window 4 s + kq
 //     (two small LDS reads) and places g in the slot arg of its 8; position 8 -- a second one-hot image T8[w][co], written once per item;
-//   * B operand = frame pixels through ds_read_b64_tr_b16 as in the old kernel: lane (rq, cp) of quarter kq supplies the 8-byte LDS row of
+//   * B operand = frame pixels through ds_read_b64_tr_b16 as in conv1_wgrad_bf16_kernel: lane (rq, cp) of quarter kq supplies the 8-byte LDS row of
 //     pixel(window, position rq | 4 + rq) + tap(4 m + cp); the 16 columns of MFMA m are 4 taps x (3 channels + the 1.0 that sums the bias);
 //   * two LDS tile sets and two staging register sets: item k + 1 is stored while item k is multiplied, loads run two items ahead,
 //     one barrier per item.
@@ -1648,7 +1584,7 @@ __global__ __launch_bounds__(256) void conv1_wgrad_onehot_bf16_kernel(WgradArgs 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, kq = lane >> 4, rq = i >> 2, cp = i & 3;
     const unsigned short* g_dp = (const unsigned short*)a.dout;
     const int nwork = a.n * C1H::TPI, G = gridDim.x;
-    if ((int)blockIdx.x >= nwork) {                             // (the slab count is the old kernel's: min(1024, 16 n) >= 8 n)
+    if ((int)blockIdx.x >= nwork) {                             // (the slab count is c1_grid(n), shared with conv1_wgrad_bf16_kernel: min(1024, 16 n) >= 8 n)
         float* slab = a.partial + (long long)blockIdx.x * 448;
         for (int e = tid; e < 448; e += 256) slab[e] = 0.f;
         return;
@@ -1809,15 +1745,11 @@ __global__ __launch_bounds__(256) void conv1_wgrad_onehot_bf16_kernel(WgradArgs 
     float* slab = a.partial + (long long)blockIdx.x * 448;
     for (int e = tid; e < 448; e += 256) slab[e] = red[e];
 }
-#ifndef C1_WG_ONEHOT
-#define C1_WG_ONEHOT 1             // 0: the gathering kernel conv1_wgrad_bf16_kernel<true>
-#endif
 #ifndef C1_WG_PAD
 #define C1_WG_PAD (36 * 1024)      // requested LDS: at most 4 workgroups of the 1024 land on one CU (an even spread; the tiles need 12-16 KB)
 #endif
 constexpr size_t C1_WG_TILES = (size_t)(((C1W::NPIX * 4 + 7) / 8) * 8 + C1W::NT * 16) * 2;
-constexpr size_t C1_WG_LDS = C1_WG_TILES + 3 * 32 * 16 * 3 > C1_WG_PAD ? C1_WG_TILES : C1_WG_PAD - 3 * 32 * 16 * 3;
-constexpr size_t C1_WGP_LDS = C1_WG_LDS + 3 * 32 * 16 * 3;
+constexpr size_t C1_WG_LDS = C1_WG_TILES + 3 * 32 * 16 * 3 > C1_WG_PAD ? C1_WG_TILES : C1_WG_PAD - 3 * 32 * 16 * 3;      // (the pad less 4.5 KB: the request the spread was measured with)
 static int c1_grid(int n) { const int w = n * C1W::TPI; return w > 1024 ? 1024 : w; }
 void launch_conv1_fwd_bf16(const ConvArgs& a, const unsigned short* lut16, hipStream_t st) {
     const int w = a.n * C1::TPI, grid = w > 1024 ? 1024 : w;
@@ -1827,15 +1759,13 @@ void launch_conv1_fwd_bf16(const ConvArgs& a, const unsigned short* lut16, hipSt
 void launch_conv1_wgrad_bf16(const WgradArgs& a, const unsigned short* lut16, hipStream_t st) {
     static std::once_flag attr;
     std::call_once(attr, [] {
-        hipFuncSetAttribute((const void*)conv1_wgrad_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C1_WG_LDS);
-        hipFuncSetAttribute((const void*)conv1_wgrad_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C1_WGP_LDS);
+        hipFuncSetAttribute((const void*)conv1_wgrad_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C1_WG_LDS);
         hipFuncSetAttribute((const void*)conv1_wgrad_onehot_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * C1H::SET_BYTES);
     });
     const int grid = c1_grid(a.n);
     if (grid < 1) return;
-    if (a.pool_arg && C1_WG_ONEHOT) hipLaunchKernelGGL(conv1_wgrad_onehot_bf16_kernel, dim3(grid), dim3(256), 2 * C1H::SET_BYTES, st, a);
-    else if (a.pool_arg) hipLaunchKernelGGL(conv1_wgrad_bf16_kernel<true>, dim3(grid), dim3(256), C1_WGP_LDS, st, a, lut16);
-    else hipLaunchKernelGGL(conv1_wgrad_bf16_kernel<false>, dim3(grid), dim3(256), C1_WG_LDS, st, a, lut16);
+    if (a.pool_arg) hipLaunchKernelGGL(conv1_wgrad_onehot_bf16_kernel, dim3(grid), dim3(256), 2 * C1H::SET_BYTES, st, a);
+    else hipLaunchKernelGGL(conv1_wgrad_bf16_kernel, dim3(grid), dim3(256), C1_WG_LDS, st, a, lut16);
 }
 
 // ------------------------------------------------------------------------------------------ launchers
@@ -1892,4 +1822,4 @@ void launch_conv_dgrad_bf16(ConvShape s, const ConvArgs& a, hipStream_t st) {
     }
 }
 
-int conv_bwd_fused_grid(ConvShape s, int n) { return s == CS_16_32_32 ? b2bwd_grid(n) : (s == CS_32_32_16 && B3BWD_FUSED) ? b3bwd_grid(n) : -1; }
+int conv_bwd_fused_grid(ConvShape s, int n) { return s == CS_16_32_32 ? b2bwd_grid(n) : s == CS_32_32_16 ? b3bwd_grid(n) : -1; }

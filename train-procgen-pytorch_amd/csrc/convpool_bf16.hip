@@ -29,9 +29,6 @@ struct CpCfg {
 #ifndef CP_MTC
 #define CP_MTC 3
 #endif
-#ifndef CP_ROLL
-#define CP_ROLL 1         // 0: the item kernel at every batch size (A/B timing)
-#endif
     static constexpr int MTC = MT < CP_MTC ? MT : CP_MTC;            // M tiles whose accumulators live together
     static constexpr int NSRC = PH * HW * C8, NLD = (NSRC + 255) / 256;
     static constexpr int IPI = HO / 4;                               // items per image (4 pooled rows each)
@@ -296,7 +293,7 @@ using CP_32_32_16 = CpCfg<32, 32, 16>;
 
 template <class C>
 static void launch_cp_t(const ConvArgs& a, void* p_out, uint8_t* p_arg, hipStream_t st) {
-    if (a.n >= 1024 && CP_ROLL) {                           // update-sized: whole images per workgroup, rolling conv rows
+    if (a.n >= 1024) {                           // update-sized: whole images per workgroup, rolling conv rows
         using R = CpRoll<C>;
         static std::once_flag attr_r;          // (launchers run on up to 4 group worker threads)
         std::call_once(attr_r, [] { hipFuncSetAttribute((const void*)conv_pool_fwd_roll_bf16_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R::LDS_BYTES); });

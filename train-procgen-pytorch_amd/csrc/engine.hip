@@ -940,9 +940,6 @@ static void net_forward(mi_ctx* c, const InputSrc& src, int n, bool recurrent = 
     if (with_heads) net_heads(c, n, soff);
 }
 
-#ifndef SIDE_EXT_EVENT
-#define SIDE_EXT_EVENT 1
-#endif
 // backward from dY (n x (A+1)); gradients accumulate into c->grads
 static void net_backward(mi_ctx* c, const InputSrc& src, int n) {
     const bool impala = c->cfg.arch == MI_ARCH_IMPALA;
@@ -952,7 +949,7 @@ static void net_backward(mi_ctx* c, const InputSrc& src, int n) {
         ProfScope ps(c, PC_GEMM, n, 4.0 * ((double)n * (c->A + 1) + 2.0 * n * c->H + (double)c->H * (c->A + 1)), 4.0 * n * c->H * (c->A + 1));
         launch_heads_bwd(c->dY, c->feat, c->params + c->wh_off, impala ? 1 : 0, c->dfeat, c->grads + c->wh_off, c->grads + c->bh_off, c->gemm_ws,
                          n, c->H, c->A + 1, CUR(c), !(c->side.armed && !tl_stream),      // (side stream armed: it also sums the slabs ...
-                         (c->side.armed && !tl_stream && SIDE_EXT_EVENT) ? c->ev_side_fork : nullptr);      //  ... and forks on this launch's completion)
+                         (c->side.armed && !tl_stream) ? c->ev_side_fork : nullptr);      //  ... and forks on this launch's completion)
     } else {
         linear_wgrad(c, c->dY, c->feat, 0, c->grads + c->wh_off, c->grads + c->bh_off, n, c->H, c->A + 1);
         linear_dgrad(c, c->dY, c->params + c->wh_off, impala ? c->feat : nullptr, c->dfeat, n, c->H, c->A + 1);
@@ -983,8 +980,7 @@ static void net_backward(mi_ctx* c, const InputSrc& src, int n) {
         // the first env group's stream when there is one (idle during an update, joined by JOIN(); one hardware queue less in use), else an own stream
         hipStream_t ss = (c->n_groups > 0 && c->gs[0]) ? c->gs[0] : c->side_stream;
         if (!ss) { hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking); ss = c->side_stream; }
-        if (!SIDE_EXT_EVENT) hipEventRecord(c->ev_side_fork, c->stream);          // (else: heads_bwd_kernel's own completion, launch_heads_bwd above)
-        hipStreamWaitEvent(ss, c->ev_side_fork, 0);
+        hipStreamWaitEvent(ss, c->ev_side_fork, 0);          // (recorded at heads_bwd_kernel's own completion: launch_heads_bwd above)
         if (c->idx_ev_deferred >= 0) { hipEventRecord(c->idx_ev[c->idx_ev_deferred], ss); c->idx_ev_deferred = -1; }      // (minibatch_impl: the index slot's "read" marker)
         tl_stream = ss;
         launch_heads_bwd_reduce(c->gemm_ws, c->grads + c->wh_off, c->grads + c->bh_off, n, c->H, c->A + 1, ss);      // (before fc_tn reuses the slabs)
@@ -1024,7 +1020,7 @@ static void net_backward(mi_ctx* c, const InputSrc& src, int n) {
         // fused data gradients where they measured faster than two dgrad launches (16 channels @32x32: 14.5 vs 15.9 ms per
         // iteration; 32 @8x8: equal); at 32 channels @16x16 the two separate launches win (8.3 vs 10.2 ms)
         if (c->bf && (L[1].shape == CS_32_32_16 || L[1].shape == CS_32_32_8)) {
-            // 32 channels @16x16: whole backward of each residual block in one launch (resblock_bwd_full32_bf16_kernel)
+            // 32 channels @16x16: whole backward of each residual block in one launch (resblock_bwd_full32s_bf16_kernel; @8x8: resblock_bwd_full32q_bf16_kernel)
             const double px = (double)n * L[1].hw * L[1].hw, ch = L[1].cout;
             auto rb_full32 = [&](const ConvLayer& l1, const ConvLayer& l2, const float* dy, const float* a_fwd, const float* x_fwd, float* dx) {
                 const int grid = resblock_bwd_full32_grid(l1.shape, n);
@@ -1047,7 +1043,7 @@ static void net_backward(mi_ctx* c, const InputSrc& src, int n) {
                 launch_resblock_bwd_bf16(l1.shape, dy, a_fwd, x_fwd, da, dx, n, c->banks + l2.bank_d, c->banks + l1.bank_d, CUR(c));
             };
             if (L[1].shape == CS_16_16_32) {
-                // 16 channels @32x32: data gradients AND both weight gradients in one launch (resblock_bwd_full_bf16_kernel);
+                // 16 channels @32x32: data gradients AND both weight gradients in one launch (resblock_bwd_full16d_bf16_kernel);
                 // the gradient of conv1's output never reaches HBM
                 auto rb_full = [&](const ConvLayer& l1, const ConvLayer& l2, const float* dy, const float* a_fwd, const float* x_fwd, float* dx, hipEvent_t done_ev = nullptr) {
                     const int grid = resblock_bwd_full_grid(n);
@@ -1061,7 +1057,7 @@ static void net_backward(mi_ctx* c, const InputSrc& src, int n) {
                 };
                 rb_full(L[3], L[4], Gout, k.A2, k.P1, Gb);      // res2: P2 = conv2(relu(A2)) + P1 ; A2 = conv1(relu(P1))
                 // (block 1's res1 is the last launch in front of the second fork: the fork event is this launch's own completion)
-                fork2_on_launch = b == 0 && SIDE_EXT_EVENT && c->side_on && !tl_stream && n >= 1024 && c->slab_desc_cached_n == n && launch_resblock_bwd_full_event_ok();
+                fork2_on_launch = b == 0 && c->side_on && !tl_stream && n >= 1024 && c->slab_desc_cached_n == n;
                 rb_full(L[1], L[2], Gb, k.A1, k.P0, Gout, fork2_on_launch ? c->ev_side_fork : nullptr);      // res1: P1 = conv2(relu(A1)) + P0 ; A1 = conv1(relu(P0))
             } else {
             // res2: P2 = conv2(relu(A2)) + P1 ; A2 = conv1(relu(P1))

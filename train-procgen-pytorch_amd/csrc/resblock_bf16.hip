@@ -463,16 +463,20 @@ __global__ __launch_bounds__(C::NT) void resblock_pair_bf16_kernel(ResblockPairA
     }
 }
 
-// ---- 32 channels @16x16, update-sized batches: the two residual blocks as two wave ROLES, pipelined over images (round 3).
-// resblock_pair_bf16_kernel keeps its four filter banks in LDS (78 KB) and, with two pixel tiles per wave, reads a bank fragment from
-// LDS for every two MFMAs: 1 KB of LDS traffic per MFMA, the LDS pipe 0.66 busy, the matrix pipe 0.40 (187 us per 8192 images).  Here
-// waves 0-3 run res1 of image k + 1 while waves 4-7 run res2 of image k, each role with ITS two banks in registers (36 fragments, loaded
-// once per launch): no bank reads at all, four pixel tiles per wave and conv, and the LDS holds five 16x16x32 tiles instead -- res1's
-// input, relu(res1.conv1), res1's output twice (the hand-over between the roles, double-buffered), relu(res2.conv1).  Two barriers per
-// image (after the staging, between the two convs), shared by the roles.  Arithmetic per output element as before (same banks, same K
-// order, same rounding points): the four stored tensors are bit-identical.
+// ---- 32 channels @16x16, update-sized batches: resblock_pair32r_bf16_kernel, the two residual blocks as two wave ROLES pipelined over
+// images.  512 threads, one workgroup per CU.  Waves 0-3 (role A) run res1 of image k + 1 while waves 4-7 (role B) run res2 of image k.
+// Registers: each role holds ITS two filter banks (36 fragments, loaded once per launch) and its two bias quads per output block: no bank
+// is read from LDS (with the four banks in LDS, 78 KB, and two pixel tiles per wave, resblock_pair_bf16_kernel reads 1 KB of LDS per
+// MFMA: LDS pipe 0.66 busy, matrix pipe 0.40, 187 us per 8192 images).  Role A also holds the next image's input, loaded one step ahead.
+// LDS: five haloed 16x16x32 tiles -- s_x (res1's raw input: ReLU on the operand reads, the skip connection reads it as is),
+// s_a1 (relu(res1.conv1)), s_h[2] (res1's raw output: the hand-over from role A to role B, double-buffered), s_a2 (relu(res2.conv1)).
+// Per step both roles run conv1 (+ bias) -> a (HBM) and relu(a) -> LDS, then conv2 (+ bias) + skip -> y (HBM; role A also into
+// s_h[step & 1]), four pixel tiles per wave and conv, two at a time (four independent accumulator chains).
+// Barriers: three per step, shared by the roles (previous step's tiles free, staging done, conv1's output complete).
+// Arithmetic per output element as in resblock_pair_bf16_kernel (same banks, same K order, same rounding points): the four stored
+// tensors are bit-identical between the two kernels.
 template <int HW_, int NIMG_>
-struct RbPair32R {                                       // HW 16: one image per step; HW 8: two images per step (8 pixel tiles: two per wave and conv)
+struct RbPair32R {                                       // NIMG images of HW x HW per step (run: 16x16, one image)
     static constexpr int C = 32, HW = HW_, NIMG = NIMG_, P = HW + 2, S = RB_S32, IMG_ELEMS = P * P * S, T_ELEMS = NIMG * IMG_ELEMS, WS = 9 * 32 + 16;
     static constexpr int NPX = NIMG * HW * HW, NMT = NPX / 16, NWORD = NPX * 4 / 256;       // pixels, pixel tiles, staged 16-byte words per thread of role A
     static constexpr size_t LDS_BYTES = (size_t)5 * T_ELEMS * 2;
@@ -626,9 +630,6 @@ __global__ __launch_bounds__(512, 2) void resblock_pair32r_bf16_kernel(ResblockP
         }
     }
 }
-#ifndef RB32_PAIR_ROLES
-#define RB32_PAIR_ROLES 1          // bit 0: 32 channels @16x16 (n >= 1024), bit 1: @8x8 (n > 1024; two images per step: 55.4 against 56.1 us, not taken) run resblock_pair32r_bf16_kernel instead of resblock_pair_bf16_kernel
-#endif
 template <class C>
 static void launch_rbp32r(const ResblockPairArgs& a, hipStream_t st) {
     static std::once_flag attr;
@@ -638,7 +639,6 @@ static void launch_rbp32r(const ResblockPairArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(resblock_pair32r_bf16_kernel<C>, dim3(grid), dim3(512), C::LDS_BYTES, st, a);
 }
 using RBR_32_16 = RbPair32R<16, 1>;
-using RBR_32_8 = RbPair32R<8, 2>;
 
 template <class C>
 static void launch_rbp_t(const ResblockPairArgs& a, hipStream_t st) {
@@ -654,16 +654,17 @@ static void launch_rbp_t(const ResblockPairArgs& a, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------ whole backward of a residual block
-// Data gradients AND both weight gradients of a residual block in one launch (16-channel blocks @32x32, the largest
-// share of the update's HBM traffic).  Separately, the four kernels move 9.75 tensor passes per block (fused data
-// gradients 5.25 + two weight-gradient kernels 2.25 each); here the tile of every operand is staged once:
-//   reads  dy (12 rows per 8), conv1 output a and block input x (10 rows per 8, ReLU applied while staging)
+// Data gradients AND both weight gradients of a residual block in one launch.  Separately, the four kernels move 9.75
+// tensor passes per block (fused data gradients 5.25 + two weight-gradient kernels 2.25 each); here the tile of every
+// operand is staged once:
+//   reads  dy, conv1 output a and block input x (with the halo rows of a row tile)
 //   writes dx only -- the gradient of conv1's output lives in LDS (second transposed conv AND conv1's weight gradient
 //   read it there) and goes to HBM only if the caller asks for it.
 // Weight gradients as in conv3x3_wgrad_bf16_kernel: M = 16 output channels, N = 16 input channels, K = 32 pixels, both
 // operands through ds_read_b64_tr_b16 from the [pixel][channel] tiles, accumulators kept across the persistent loop,
-// waves summed through LDS in fixed order, one slab per workgroup and layer; bias gradients = MFMA against ones.
-// ReLU masks come from the staged relu(a) / relu(x) tiles (> 0 there <=> > 0 before the ReLU).
+// one slab per workgroup and layer; bias gradients = MFMA against ones.
+// One kernel per shape: resblock_bwd_full16d_bf16_kernel (16 channels @32x32, the largest share of the update's HBM
+// traffic), resblock_bwd_full32s_bf16_kernel (32 @16x16), resblock_bwd_full32q_bf16_kernel (32 @8x8).
 typedef short rb_s16x4 __attribute__((ext_vector_type(4)));
 typedef rb_s16x4 __attribute__((address_space(3))) * rb_lds_s16x4_ptr;
 
@@ -675,691 +676,47 @@ struct RbFullArgs {
     int n;
 };
 
-#ifndef RBFULL_WG_REUSE
-#define RBFULL_WG_REUSE 1          // weight-gradient operand rows shared between a wave's two consecutive pixel rows (see the kernel)
-#endif
-#ifndef RBFULL_SPREAD_LOADS
-#define RBFULL_SPREAD_LOADS 1
-#endif
-#ifndef RBFULL_CFG
-#define RBFULL_CFG 8, 256          // tile rows, threads per workgroup: every wave holds both layers' 20 weight-gradient tiles, 250 registers, 2 waves per SIMD.
-#endif                             // Measured alternatives (scratch/kbench_rb16.hip, us per 8192-sample launch on random data, this config 349-365):
-                                   //  8 x 512 = two workgroups of 8 waves per CU = 4 waves per SIMD at <= 128 registers, weight-gradient accumulators split by
-                                   //  LAYER over the wave halves (waves 0-3 conv2's, 4-7 conv1's), four staging words per thread in one index space: needs 160
-                                   //  registers, so 19 spill at 128 -- 378-384; 16 x 512, 92 KB, one workgroup per CU: 14.8 vs 13.8 ms per iteration (round 1)
-template <int TH_, int NT_>
-struct RbFullT {                                 // C = 16, HW = 32
-    static constexpr int C = 16, HW = 32, TH = TH_, NT = NT_, NW = NT_ / 64, S = 16, P = HW + 2, TPI = HW / TH;
-    static constexpr int XR = TH + 4, YR = TH + 2;
-    static constexpr int X_ELEMS = XR * P * S, Y_ELEMS = YR * P * S;
-    static constexpr int NK = 5, WS = NK * 32 + 16, W_ELEMS = C * WS;
-    static constexpr int NMT1 = YR * HW / 16, NMT2 = TH * HW / 16, MT1 = (NMT1 + NW - 1) / NW, MT2 = NMT2 / NW;     // TH 8 x 4 waves: 20 / 16 tiles = 5 / 4 per wave
-    static_assert(NMT2 % NW == 0, "second conv: whole tiles per wave");
-    static constexpr int NX = XR * HW * 2, NA = YR * HW * 2;                                          // 16-byte words staged per tensor
-    static constexpr int KX = (NX + NT - 1) / NT, KA = (NA + NT - 1) / NT;
-    static constexpr int NSTEP = TH * HW / 32;                                                         // 8 pixel steps of 32
-    static constexpr int WLEN = C * 9 * C, SLAB = WLEN + C;
-    static constexpr size_t TILE_BYTES = (size_t)(X_ELEMS + 3 * Y_ELEMS + 2 * W_ELEMS) * 2, RED_BYTES = (size_t)(2 * WLEN + 2 * NW * C) * 4;
-    static constexpr size_t LDS_BYTES = TILE_BYTES > RED_BYTES ? TILE_BYTES : RED_BYTES;
-};
-using RbFull = RbFullT<RBFULL_CFG>;
-
-#ifdef RBF_TIMING      // scratch/kbench_rb16.hip: per-phase shader-clock totals of wave 0, summed over workgroups
-__device__ unsigned long long g_rbf_timing[8];
-#define RBF_TCK(k) do { if (tid == 0) { const long long now_ = clock64(); tacc_[k] += now_ - tlast_; tlast_ = now_; } } while (0)
-#else
-#define RBF_TCK(k) do { } while (0)
-#endif
-__global__ __launch_bounds__(RbFull::NT, RbFull::NT == 512 ? 4 : 2) void resblock_bwd_full_bf16_kernel(RbFullArgs a) {      // 512 threads: 4 waves per SIMD, <= 128 registers
-    using C = RbFull;
-    extern __shared__ __attribute__((aligned(16))) unsigned short smem_h[];
-    unsigned short* s_x = smem_h;                         // dy rows ty0-2 .. ty0+TH+1
-    unsigned short* s_y = s_x + C::X_ELEMS;               // d(conv1 output) rows ty0-1 .. ty0+TH
-    unsigned short* s_a = s_y + C::Y_ELEMS;               // relu(conv1 output), same rows
-    unsigned short* s_p = s_a + C::Y_ELEMS;               // relu(block input), same rows
-    unsigned short* s_w1 = s_p + C::Y_ELEMS;              // transposed bank of conv2 (first conv of this pass)
-    unsigned short* s_w2 = s_w1 + C::W_ELEMS;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, kq = lane >> 4, rq = (lane & 15) >> 2, cp = lane & 3;
-    for (int e = tid; e < C::W_ELEMS / 8; e += C::NT) { ((uint4*)s_w1)[e] = ((const uint4*)a.bank2_t)[e]; ((uint4*)s_w2)[e] = ((const uint4*)a.bank1_t)[e]; }
-    for (int e = tid; e < (C::X_ELEMS + 3 * C::Y_ELEMS) / 8; e += C::NT) ((uint4*)smem_h)[e] = (uint4){0u, 0u, 0u, 0u};   // column halos stay zero
-    int koff[C::NK];
-#pragma unroll
-    for (int m = 0; m < C::NK; ++m) {
-        int tap = 2 * m + (kq >> 1); const int chunk = kq & 1; if (tap > 8) tap = 8;
-        koff[m] = ((tap / 3) * C::P + (tap % 3)) * C::S + chunk * 8;
-    }
-    constexpr bool SPLIT = C::NW == 8;               // weight gradients: waves 0-3 own conv2's tiles (acc2), waves 4-7 conv1's (held in acc2 as well)
-    constexpr int NACC1 = 9;                         // (SPLIT: acc1 / accb1 are never used and vanish)
-    f32x4 acc2[9], acc1[NACC1], accb2 = {0.f, 0.f, 0.f, 0.f}, accb1 = {0.f, 0.f, 0.f, 0.f};     // weight-gradient tiles of conv2 / conv1, bias rows
-#pragma unroll
-    for (int t = 0; t < 9; ++t) acc2[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < NACC1; ++t) acc1[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const bf16x8 ones = __builtin_bit_cast(bf16x8, (uint4){0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u});
-
-    const int nwork = a.n * C::TPI;
-#ifdef RBF_TIMING
-    long long tacc_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast_ = clock64();
-#endif
-    // 512 threads: the three tiles of an item are 768 + 640 + 640 = 2048 16-byte words = exactly four per thread in ONE index space (a
-    // thread's word k is e = tid + 512 k: dy for e < 768, then relu(a), then relu(x)): 16 staging registers instead of 24 with a per-tensor
-    // split that leaves the second word of every tensor half empty -- the kernel has 128 registers per thread.
-    constexpr bool UNI = C::NT == 512;
-    static_assert(!UNI || C::NX + 2 * C::NA == 4 * C::NT, "unified staging: four words per thread");
-    uint4 ru[UNI ? 4 : 1];
-    auto uni_word = [&](int e, int& t, int& le) { t = e < C::NX ? 0 : (e < C::NX + C::NA ? 1 : 2); le = e - (t == 0 ? 0 : (t == 1 ? C::NX : C::NX + C::NA)); };
-    uint4 rx[UNI ? 1 : C::KX], ra[UNI ? 1 : C::KA], rp[UNI ? 1 : C::KA];
-    // Next item's tiles into registers while this one is computed.  Every load is UNCONDITIONAL from a row clamped into the image and a
-    // word index clamped into the tile (rows outside the image / threads past the tile are replaced by zeros when the registers are
-    // stored): `v = 0; if (row in image) v = load` merges the loaded registers with older values and the compiler then waits for the
-    // loads right where they are issued -- the item paid a full HBM round trip there (1180 of 9200 cycles per item, scratch/kbench_rb16.hip).
-    auto load = [&](int work, int part = 7) {            // part bits: 1 = dy words, 2 = relu(a) words, 4 = relu(x) words
-        const long long img = work / C::TPI; const int ty0 = (work % C::TPI) * C::TH;
-        if constexpr (UNI) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                int t, le; uni_word(tid + k * C::NT, t, le);
-                const int c8 = le & 1, px = (le >> 1) % C::HW; int gy = ty0 - (t == 0 ? 2 : 1) + le / (2 * C::HW);
-                gy = gy < 0 ? 0 : (gy > C::HW - 1 ? C::HW - 1 : gy);
-                const unsigned short* src = t == 0 ? a.dy : (t == 1 ? a.a_fwd : a.x_fwd);
-                ru[k] = *(const uint4*)(src + ((img * C::HW + gy) * C::HW + px) * C::C + c8 * 8);
-            }
-            return;
-        }
-        if (part & 1) {
-#pragma unroll
-        for (int k = 0; k < C::KX; ++k) {
-            int e = tid + k * C::NT; e = e < C::NX ? e : C::NX - 1;
-            const int c8 = e & 1, px = (e >> 1) % C::HW; int gy = ty0 - 2 + e / (2 * C::HW);
-            gy = gy < 0 ? 0 : (gy > C::HW - 1 ? C::HW - 1 : gy);
-            rx[k] = *(const uint4*)(a.dy + ((img * C::HW + gy) * C::HW + px) * C::C + c8 * 8);
-        }
-        }
-#pragma unroll
-        for (int k = 0; k < C::KA; ++k) {
-            int e = tid + k * C::NT; e = e < C::NA ? e : C::NA - 1;
-            const int c8 = e & 1, px = (e >> 1) % C::HW; int gy = ty0 - 1 + e / (2 * C::HW);
-            gy = gy < 0 ? 0 : (gy > C::HW - 1 ? C::HW - 1 : gy);
-            const long long o = ((img * C::HW + gy) * C::HW + px) * C::C + c8 * 8;
-            if (part & 2) ra[k] = *(const uint4*)(a.a_fwd + o);
-            if (part & 4) rp[k] = *(const uint4*)(a.x_fwd + o);
-        }
-    };
-    auto item = [&](int w) { return w < nwork ? w : nwork - 1; };            // past the end: the last item again (loads stay unconditional)
-    if ((int)blockIdx.x < nwork) load(blockIdx.x);
-    for (int work = blockIdx.x; work < nwork; work += gridDim.x) {
-        const long long img = work / C::TPI; const int ty0 = (work % C::TPI) * C::TH;
-        RBF_TCK(0);
-        __syncthreads();
-        RBF_TCK(1);
-        if constexpr (UNI) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                int t, le; uni_word(tid + k * C::NT, t, le);
-                const int ry = le / (2 * C::HW), gy = ty0 - (t == 0 ? 2 : 1) + ry;
-                const bool in = gy >= 0 && gy < C::HW;
-                unsigned short* dst = (t == 0 ? s_x : (t == 1 ? s_a : s_p)) + (ry * C::P + (le >> 1) % C::HW + 1) * C::S + (le & 1) * 8;
-                const uint4 v = ru[k];
-                const uint4 r = t == 0 ? v : (uint4){rb_relu2(v.x), rb_relu2(v.y), rb_relu2(v.z), rb_relu2(v.w)};
-                *(uint4*)dst = in ? r : (uint4){0u, 0u, 0u, 0u};
-            }
-        } else {
-#pragma unroll
-        for (int k = 0; k < C::KX; ++k) {
-            const int e = tid + k * C::NT, gy = ty0 - 2 + e / (2 * C::HW);
-            const bool in = gy >= 0 && gy < C::HW;
-            if (e < C::NX) *(uint4*)(s_x + ((e / (2 * C::HW)) * C::P + (e >> 1) % C::HW + 1) * C::S + (e & 1) * 8) = in ? rx[k] : (uint4){0u, 0u, 0u, 0u};
-        }
-#pragma unroll
-        for (int k = 0; k < C::KA; ++k) {
-            const int e = tid + k * C::NT, gy = ty0 - 1 + e / (2 * C::HW);
-            const bool in = gy >= 0 && gy < C::HW;
-            if (e < C::NA) {
-                const int o = ((e / (2 * C::HW)) * C::P + (e >> 1) % C::HW + 1) * C::S + (e & 1) * 8;
-                *(uint4*)(s_a + o) = in ? (uint4){rb_relu2(ra[k].x), rb_relu2(ra[k].y), rb_relu2(ra[k].z), rb_relu2(ra[k].w)} : (uint4){0u, 0u, 0u, 0u};
-                *(uint4*)(s_p + o) = in ? (uint4){rb_relu2(rp[k].x), rb_relu2(rp[k].y), rb_relu2(rp[k].z), rb_relu2(rp[k].w)} : (uint4){0u, 0u, 0u, 0u};
-            }
-        }
-        }
-        RBF_TCK(2);
-        __syncthreads();
-        RBF_TCK(3);
-#if RBFULL_SPREAD_LOADS
-        // the next item's 9 loads per thread are ISSUED in three pieces, in front of each compute phase: in one piece their issue alone took
-        // ~1000 of an item's ~9200 cycles per workgroup (36 KB through a 64 B/clk path shared with the CU's other workgroup) with nothing else running
-        const int wnext = item(work + gridDim.x);
-        load(wnext, 1);
-#else
-        load(item(work + gridDim.x));
-#endif
-        RBF_TCK(4);
-
-        // ---- da = convT2(dy) * (a > 0) on rows ty0-1 .. ty0+TH -> s_y (rows outside the image: relu(a) is 0 there, so da is 0)
-        {
-            int abase[C::MT1], ybase[C::MT1];
-#pragma unroll
-            for (int mt = 0; mt < C::MT1; ++mt) {
-                int t = wave + C::NW * mt; t = t < C::NMT1 ? t : C::NMT1 - 1;          // (a clamped duplicate rewrites the same values)
-                const int pl = t * 16 + i, px = pl % C::HW, ry = pl / C::HW;
-                abase[mt] = (ry * C::P + px) * C::S;
-                ybase[mt] = (ry * C::P + px + 1) * C::S + kq * 4;
-            }
-            f32x4 acc[C::MT1][1];
-            {
-#pragma unroll
-                for (int mt = 0; mt < C::MT1; ++mt) acc[mt][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                const int bbase = i * C::WS + kq * 8;
-#pragma unroll
-                for (int m = 0; m < C::NK; ++m) {
-                    const bf16x8 bv = *(const bf16x8*)(s_w1 + bbase + m * 32);
-#pragma unroll
-                    for (int mt = 0; mt < C::MT1; ++mt) acc[mt][0] = MFMA_BF16(bv, *(const bf16x8*)(s_x + abase[mt] + koff[m]), acc[mt][0]);
-#if RBFULL_SPREAD_LOADS == 2
-                    if (m == 1) load(wnext, 2);
-#endif
-                    if constexpr (SPLIT) __builtin_amdgcn_sched_barrier(0);      // (128 registers: no operand reads hoisted across K steps; 4 waves per SIMD cover the LDS latency)
-                }
-            }
-#pragma unroll
-            for (int mt = 0; mt < C::MT1; ++mt) {
-                const uint2 mk = *(const uint2*)(s_a + ybase[mt]);
-                float v[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = rb_lane(mk, r) > 0.f ? acc[mt][0][r] : 0.f;
-                const uint2 raw = rb_pack(v);
-                *(uint2*)(s_y + ybase[mt]) = raw;
-                if (a.da_out) {
-                    int t = wave + C::NW * mt; t = t < C::NMT1 ? t : C::NMT1 - 1;
-                    const int pl = t * 16 + i, px = pl % C::HW, ry = pl / C::HW, gy = ty0 - 1 + ry;
-                    if (ry >= 1 && ry <= C::TH) *(uint2*)(a.da_out + ((img * C::HW + gy) * C::HW + px) * C::C + kq * 4) = raw;
-                }
-            }
-        }
-        RBF_TCK(5);
-        __syncthreads();
-        RBF_TCK(6);
-#if RBFULL_SPREAD_LOADS == 2
-        load(wnext, 4);
-#elif RBFULL_SPREAD_LOADS
-        load(wnext, 2);
-#endif
-        // ---- dx = convT1(da) * (x > 0) + dy on rows ty0 .. ty0+TH-1 -> HBM
-        {
-            int abase[C::MT2];
-#pragma unroll
-            for (int mt = 0; mt < C::MT2; ++mt) { const int pl = (wave + C::NW * mt) * 16 + i; abase[mt] = ((pl / C::HW) * C::P + pl % C::HW) * C::S; }
-            f32x4 acc[C::MT2];
-#pragma unroll
-            for (int mt = 0; mt < C::MT2; ++mt) acc[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            const int bbase = i * C::WS + kq * 8;
-#pragma unroll
-            for (int m = 0; m < C::NK; ++m) {
-                const bf16x8 bv = *(const bf16x8*)(s_w2 + bbase + m * 32);
-#pragma unroll
-                for (int mt = 0; mt < C::MT2; ++mt) acc[mt] = MFMA_BF16(bv, *(const bf16x8*)(s_y + abase[mt] + koff[m]), acc[mt]);
-                if constexpr (SPLIT) __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int mt = 0; mt < C::MT2; ++mt) {
-                const int pl = (wave + C::NW * mt) * 16 + i, px = pl % C::HW, oy = pl / C::HW;
-                const uint2 mk = *(const uint2*)(s_p + ((oy + 1) * C::P + px + 1) * C::S + kq * 4);
-                const uint2 sk = *(const uint2*)(s_x + ((oy + 2) * C::P + px + 1) * C::S + kq * 4);
-                float v[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = (rb_lane(mk, r) > 0.f ? acc[mt][r] : 0.f) + rb_lane(sk, r);
-                *(uint2*)(a.dx_out + ((img * C::HW + ty0 + oy) * C::HW + px) * C::C + kq * 4) = rb_pack(v);
-            }
-        }
-        RBF_TCK(7);
-#if RBFULL_SPREAD_LOADS == 1
-        load(wnext, 4);
-#endif
-        // ---- weight gradients: conv2 from (dy, relu(a)), conv1 from (da, relu(x)); pixel steps of 32 dealt to the waves
-#if RBFULL_WG_REUSE
-        // A pixel step is one image row (HW = 32), and the tap (ky, kx) operand of row r is row r + ky of the staged relu(a) / relu(x)
-        // tile shifted by kx: a wave that owns CONSECUTIVE rows r0, r0 + 1 needs tile rows r0 .. r0 + 3 only once each -- 12 operand
-        // fragments per layer for its 18 (row, tap) products instead of 18 (56 transposing LDS reads per wave and item instead of 80;
-        // the kernel is LDS-pipe / latency bound).  Every accumulator still receives its rows in ascending order.
-        static_assert(C::HW == 32 && (C::NSTEP == 2 * C::NW || (SPLIT && C::NSTEP == C::NW)), "one row per pixel step, two consecutive rows per wave (pair)");
-        if constexpr (SPLIT) {
-            // one code path for both halves (two paths made the compiler keep two accumulator sets): role 0 = conv2 from (dy, relu(a)),
-            // role 1 = conv1 from (da, relu(x)); the operand tiles differ by base pointer and by the row offset of the gradient tile
-            const int role = wave >> 2, r0 = 2 * (wave & 3);
-            const unsigned short* s_d = role ? s_y : s_x;
-            const unsigned short* s_b = role ? s_p : s_a;
-            const int drow = role ? 1 : 2;
-            int ocol[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) ocol[h] = (16 * (kq >> 1) + 8 * h + 4 * (kq & 1) + rq) * C::S + 4 * cp;
-            auto tr = [&](const unsigned short* base, int off) {
-                const rb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(base + ocol[0] + off));
-                const rb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(base + ocol[1] + off));
-                return (bf16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-            };
-            bf16x8 dd[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) dd[j] = tr(s_d, ((r0 + j + drow) * C::P + 1) * C::S);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) accb2 = MFMA_BF16(dd[j], ones, accb2);
-#pragma unroll
-            for (int R = 0; R < 4; ++R)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const bf16x8 fb = tr(s_b, ((r0 + R) * C::P + kx) * C::S);
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const int ky = R - j;
-                        if (ky < 0 || ky > 2) continue;
-                        acc2[ky * 3 + kx] = MFMA_BF16(dd[j], fb, acc2[ky * 3 + kx]);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);            // (128 registers: at most one operand fragment ahead of its products)
-                }
-        } else {
-            const int r0 = 2 * wave;
-            int ocol[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) ocol[h] = (16 * (kq >> 1) + 8 * h + 4 * (kq & 1) + rq) * C::S + 4 * cp;
-            auto tr = [&](const unsigned short* base, int off) {
-                const rb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(base + ocol[0] + off));
-                const rb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(base + ocol[1] + off));
-                return (bf16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-            };
-            bf16x8 d2[2], d1[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                d2[j] = tr(s_x, ((r0 + j + 2) * C::P + 1) * C::S);      // dy at the pixel   (s_x row 0 = ty0-2, col 0 = -1)
-                d1[j] = tr(s_y, ((r0 + j + 1) * C::P + 1) * C::S);      // da at the pixel   (s_y row 0 = ty0-1)
-            }
-#pragma unroll
-            for (int j = 0; j < 2; ++j) { accb2 = MFMA_BF16(d2[j], ones, accb2); accb1 = MFMA_BF16(d1[j], ones, accb1); }
-#pragma unroll
-            for (int R = 0; R < 4; ++R)                                  // tile row r0 + R of s_a / s_p (row 0 = ty0-1, col 0 = -1)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const int off = ((r0 + R) * C::P + kx) * C::S;
-                    const bf16x8 fa = tr(s_a, off), fp = tr(s_p, off);
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const int ky = R - j;
-                        if (ky < 0 || ky > 2) continue;
-                        acc2[ky * 3 + kx] = MFMA_BF16(d2[j], fa, acc2[ky * 3 + kx]);
-                        acc1[ky * 3 + kx] = MFMA_BF16(d1[j], fp, acc1[ky * 3 + kx]);
-                    }
-                }
-        }
-#else
-        for (int t = wave; t < C::NSTEP; t += C::NW) {
-            int orow[2];                                   // this lane's two source pixels (interior coordinates), MFMA k permutation as in conv_bf16.hip
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int pl = 32 * t + 16 * (kq >> 1) + 8 * h + 4 * (kq & 1) + rq;
-                orow[h] = ((pl / C::HW) * C::P + pl % C::HW) * C::S + 4 * cp;
-            }
-            auto tr = [&](const unsigned short* base, int off) {
-                const rb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(base + orow[0] + off));
-                const rb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(base + orow[1] + off));
-                return (bf16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-            };
-            const bf16x8 d2 = tr(s_x, (2 * C::P + 1) * C::S);      // dy at the pixel   (s_x row 0 = ty0-2, col 0 = -1)
-            const bf16x8 d1 = tr(s_y, (1 * C::P + 1) * C::S);      // da at the pixel   (s_y row 0 = ty0-1)
-            accb2 = MFMA_BF16(d2, ones, accb2);
-            accb1 = MFMA_BF16(d1, ones, accb1);
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                const int toff = ((tap / 3) * C::P + (tap % 3)) * C::S;      // s_a / s_p row 0 = ty0-1, col 0 = -1: tap (0,0) is the pixel's upper-left neighbour
-                acc2[tap] = MFMA_BF16(d2, tr(s_a, toff), acc2[tap]);
-                acc1[tap] = MFMA_BF16(d1, tr(s_p, toff), acc1[tap]);
-            }
-        }
-#endif
-    }
-#ifdef RBF_TIMING
-    if (tid == 0) for (int k = 0; k < 8; ++k) atomicAdd(&g_rbf_timing[k], (unsigned long long)tacc_[k]);
-#endif
-    // ---- waves summed through LDS in fixed order; one slab per workgroup and layer
-    __syncthreads();
-    float* red = (float*)smem_h;                              // [2][WLEN] then [2][NW][16] bias partials
-    float* redb = red + 2 * C::WLEN;
-    if constexpr (SPLIT) {
-        // waves 0-3 hold conv2's tiles, waves 4-7 conv1's (both in acc2 / accb2): the two halves sum side by side, each in wave order
-        const int role = wave >> 2, wl = wave & 3;
-        for (int w = 0; w < 4; ++w) {
-            if (wl == w) {
-#pragma unroll
-                for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int o = role * C::WLEN + ((kq * 4 + r) * 9 + tap) * C::C + i;
-                        red[o] = (w == 0) ? acc2[tap][r] : red[o] + acc2[tap][r];
-                    }
-            }
-            __syncthreads();
-        }
-        if (i == 0) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) redb[(role * 4 + wl) * 16 + kq * 4 + r] = accb2[r];
-        }
-        __syncthreads();
-        float* sl2 = a.slab2 + (long long)blockIdx.x * C::SLAB;
-        float* sl1 = a.slab1 + (long long)blockIdx.x * C::SLAB;
-        for (int e = tid; e < C::WLEN; e += C::NT) { sl2[e] = red[e]; sl1[e] = red[C::WLEN + e]; }
-        if (tid < 16) {
-            float t2 = 0.f, t1 = 0.f;
-            for (int w = 0; w < 4; ++w) { t2 += redb[w * 16 + tid]; t1 += redb[(4 + w) * 16 + tid]; }
-            sl2[C::WLEN + tid] = t2; sl1[C::WLEN + tid] = t1;
-        }
-    } else {
-    for (int w = 0; w < C::NW; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int o = ((kq * 4 + r) * 9 + tap) * C::C + i;
-                    red[o] = (w == 0) ? acc2[tap][r] : red[o] + acc2[tap][r];
-                    red[C::WLEN + o] = (w == 0) ? acc1[tap][r] : red[C::WLEN + o] + acc1[tap][r];
-                }
-        }
-        __syncthreads();
-    }
-    if (i == 0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { redb[wave * 16 + kq * 4 + r] = accb2[r]; redb[C::NW * 16 + wave * 16 + kq * 4 + r] = accb1[r]; }
-    }
-    __syncthreads();
-    float* sl2 = a.slab2 + (long long)blockIdx.x * C::SLAB;
-    float* sl1 = a.slab1 + (long long)blockIdx.x * C::SLAB;
-    for (int e = tid; e < C::WLEN; e += C::NT) { sl2[e] = red[e]; sl1[e] = red[C::WLEN + e]; }
-    if (tid < 16) {
-        float t2 = 0.f, t1 = 0.f;
-        for (int w = 0; w < C::NW; ++w) { t2 += redb[w * 16 + tid]; t1 += redb[C::NW * 16 + w * 16 + tid]; }
-        sl2[C::WLEN + tid] = t2; sl1[C::WLEN + tid] = t1;
-    }
-    }
-}
-// ---- wave-specialised variant of the kernel above (16 channels @32x32, 512 threads, ONE workgroup per CU).
-// scratch/kbench_rb16.hip phase clocks of the kernel above: conv phases A + B = 54 % of an item's cycles with the matrix pipe 28 % and the
-// LDS pipe 48 % busy -- every wave walks load-issue -> LDS stores -> conv A -> conv B -> weight gradients one after the other, two
-// waves per SIMD, each phase waiting on its own LDS / MFMA latencies.  Here, as in resblock_bwd_full32s_bf16_kernel, the eight waves take two
-// ROLES and each SIMD hosts one wave of each, so the matrix work of one role overlaps the LDS work of the other:
-//   waves 0-3  the two transposed convs, BOTH filter banks in registers (2 x 5 fragments = 40 VGPRs, loaded once per launch: no weight
-//              reads from LDS, no bank copies in LDS); a wave's operand reads of a whole phase go out before its first MFMA;
-//   waves 4-7  global loads + LDS staging of the tiles (four 16-byte words per thread and tensor row group, one index space), conv2's
-//              weight gradient while the conv waves produce da, conv1's while they produce dx -- two CONSECUTIVE pixel rows per wave and
-//              quarter tile, operand rows shared between them.
-// Arithmetic per output element is unchanged (same K order): dx / da are bit-identical to the kernel above; weight-gradient slabs sum
-// the same products (rows dealt to other waves).
-template <int TH_>
-struct RbFull16ST {
-    static constexpr int C = 16, HW = 32, TH = TH_, NT = 512, S = 16, P = HW + 2, TPI = HW / TH;
+// Tile geometry of the 16-channel kernel: items of TH = 16 rows of a 32x32 image.
+struct RbFull16S {
+    static constexpr int C = 16, HW = 32, TH = 16, NT = 512, S = 16, P = HW + 2, TPI = HW / TH;
     static constexpr int XR = TH + 4, YR = TH + 2;
     static constexpr int X_ELEMS = XR * P * S, Y_ELEMS = YR * P * S;
     static constexpr int NK = 5, WS = NK * 32 + 16;
     static constexpr int NMT1 = YR * HW / 16, NMT2 = TH * HW / 16, MT1 = (NMT1 + 3) / 4, MT2 = NMT2 / 4;       // tiles per conv wave
-    static constexpr int NX = XR * HW * 2, NA = YR * HW * 2, NWORD = NX + 2 * NA, KW = (NWORD + 255) / 256;    // 16-byte words; per staging thread
     static constexpr int NR = TH / 4;                                                                       // pixel rows per weight-gradient wave
     static constexpr int WLEN = C * 9 * C, SLAB = WLEN + C;
     static constexpr size_t TILE_BYTES = (size_t)(X_ELEMS + 3 * Y_ELEMS) * 2, RED_BYTES = (size_t)(2 * WLEN + 2 * 4 * C) * 4;
-    static constexpr size_t LDS_BYTES = TILE_BYTES > RED_BYTES ? TILE_BYTES : RED_BYTES;
     static_assert(NMT2 % 4 == 0 && TH % 4 == 0, "whole tiles / rows per wave");
 };
-#ifndef RBFULL16_SPECIALISED
-#define RBFULL16_SPECIALISED 2     // (see the end of this section)
-#endif
-#ifndef RBFULL16S_TH
-#define RBFULL16S_TH (RBFULL16_SPECIALISED == 2 ? 16 : 8)      // tile rows of the two-role kernels: 16 with the LDS-DMA fill (two items per image: rows
-#endif                                                         // re-read for the halo 1.17x instead of 1.33x; 2 x 60 KB of DMA-filled tiles + 19 KB)
-#ifndef RBFULL16S_CG
-#define RBFULL16S_CG 2
-#endif
-using RbFull16S = RbFull16ST<RBFULL16S_TH>;
-#ifdef RBF_TIMING
+#ifdef RBF_TIMING      // scratch/kbench_rb16.hip: per-phase shader-clock totals of wave 0 (conv role, slots 0-3) and wave 4 (weight-gradient role, 4-7), summed over workgroups
+__device__ unsigned long long g_rbf_timing[8];
 #define S16_TCK(k) do { if ((tid & 255) == 0) { const long long now_ = clock64(); tacc_[k] += now_ - tlast_; tlast_ = now_; } } while (0)
 #else
 #define S16_TCK(k) do { } while (0)
 #endif
-#if RBFULL16_SPECIALISED == 1
-
-__global__ __launch_bounds__(512, 2) void resblock_bwd_full16s_bf16_kernel(RbFullArgs a) {
-    using C = RbFull16S;
-    extern __shared__ __attribute__((aligned(16))) unsigned short smem_h[];
-    unsigned short* s_x = smem_h;                         // dy rows ty0-2 .. ty0+TH+1
-    unsigned short* s_y = s_x + C::X_ELEMS;               // d(conv1 output) rows ty0-1 .. ty0+TH
-    unsigned short* s_a = s_y + C::Y_ELEMS;               // relu(conv1 output), same rows
-    unsigned short* s_p = s_a + C::Y_ELEMS;               // relu(block input), same rows
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, kq = lane >> 4, rq = (lane & 15) >> 2, cp = lane & 3;
-    const int wv = __builtin_amdgcn_readfirstlane(wave);
-    const bool conv_role = wv < 4;
-    const int rw = wv & 3;
-#ifdef RBF_TIMING
-    long long tacc_[4] = {0, 0, 0, 0}, tlast_ = clock64();
-#endif
-    for (int e = tid; e < (C::X_ELEMS + 3 * C::Y_ELEMS) / 8; e += C::NT) ((uint4*)smem_h)[e] = (uint4){0u, 0u, 0u, 0u};   // column halos stay zero
-    // ONE register array for both roles (two sets: the kernel's allocation is the union of what its waves may keep live).
-    // conv role: st[m] = fragment of K step m of conv2's transposed bank, st[5 + m] of conv1's.
-    // weight-gradient role: st[tap] / st[10 + tap] accumulator tiles of conv2 / conv1, st[9] / st[19] their bias rows, st[20 ..] the prefetch words.
-    constexpr int NST = 20 + C::KW;
-    f32x4 st[NST];
-    if (conv_role) {
-#pragma unroll
-        for (int m = 0; m < C::NK; ++m) {
-            st[m] = __builtin_bit_cast(f32x4, *(const uint4*)(a.bank2_t + i * C::WS + m * 32 + kq * 8));
-            st[5 + m] = __builtin_bit_cast(f32x4, *(const uint4*)(a.bank1_t + i * C::WS + m * 32 + kq * 8));
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < NST; ++q) st[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);                   // vmcnt(0): the bank fragments are in (see resblock_bwd_full32s_bf16_kernel)
-    const bf16x8 ones = __builtin_bit_cast(bf16x8, (uint4){0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u});
-    int koff[C::NK];
-#pragma unroll
-    for (int m = 0; m < C::NK; ++m) {
-        int tap = 2 * m + (kq >> 1); const int chunk = kq & 1; if (tap > 8) tap = 8;
-        koff[m] = ((tap / 3) * C::P + (tap % 3)) * C::S + chunk * 8;
-    }
-    constexpr int CG = RBFULL16S_CG;                       // conv tiles whose operand reads are in flight together
-    const int nwork = a.n * C::TPI;
-    const int t2 = tid - 256;                              // staging thread index (weight-gradient waves)
-    auto word = [&](int e, int& t, int& le) { t = e < C::NX ? 0 : (e < C::NX + C::NA ? 1 : 2); le = e - (t == 0 ? 0 : (t == 1 ? C::NX : C::NX + C::NA)); };
-    auto load = [&](int work) {                            // unconditional, clamped (replaced by zeros at the store where outside the image)
-        const long long img = work / C::TPI; const int ty0 = (work % C::TPI) * C::TH;
-#pragma unroll
-        for (int k = 0; k < C::KW; ++k) {
-            int e = t2 + k * 256; e = e < C::NWORD ? e : C::NWORD - 1;
-            int t, le; word(e, t, le);
-            const int c8 = le & 1, px = (le >> 1) % C::HW; int gy = ty0 - (t == 0 ? 2 : 1) + le / (2 * C::HW);
-            gy = gy < 0 ? 0 : (gy > C::HW - 1 ? C::HW - 1 : gy);
-            const unsigned short* src = t == 0 ? a.dy : (t == 1 ? a.a_fwd : a.x_fwd);
-            st[20 + k] = __builtin_bit_cast(f32x4, *(const uint4*)(src + ((img * C::HW + gy) * C::HW + px) * C::C + c8 * 8));
-        }
-    };
-    auto item = [&](int w) { return w < nwork ? w : nwork - 1; };
-    // weight gradient of one layer over this wave's NR consecutive pixel rows: d = output-gradient tile (row offset d_row), b = input tile
-    auto wgrad = [&](const unsigned short* s_d, int d_row, const unsigned short* s_b, const int a0) {
-        const int r0 = C::NR * rw;
-        int ocol[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) ocol[h] = (16 * (kq >> 1) + 8 * h + 4 * (kq & 1) + rq) * C::S + 4 * cp;
-        auto tr = [&](const unsigned short* base, int off) {
-            const rb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(base + ocol[0] + off));
-            const rb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(base + ocol[1] + off));
-            return (bf16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        };
-        bf16x8 dd[C::NR];
-#pragma unroll
-        for (int j = 0; j < C::NR; ++j) dd[j] = tr(s_d, ((r0 + j + d_row) * C::P + 1) * C::S);
-#pragma unroll
-        for (int j = 0; j < C::NR; ++j) st[a0 + 9] = MFMA_BF16(dd[j], ones, st[a0 + 9]);
-#pragma unroll
-        for (int R = 0; R < C::NR + 2; ++R) {                // tile row r0 + R of the input tile (row 0 = ty0-1, col 0 = -1)
-            bf16x8 fb[3];
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) fb[kx] = tr(s_b, ((r0 + R) * C::P + kx) * C::S);
-#pragma unroll
-            for (int j = 0; j < C::NR; ++j) {
-                const int ky = R - j;
-                if (ky < 0 || ky > 2) continue;
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) st[a0 + ky * 3 + kx] = MFMA_BF16(dd[j], fb[kx], st[a0 + ky * 3 + kx]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-
-    if (!conv_role && (int)blockIdx.x < nwork) load(blockIdx.x);
-    for (int work = blockIdx.x; work < nwork; work += gridDim.x) {
-        const long long img = work / C::TPI; const int ty0 = (work % C::TPI) * C::TH;
-        __syncthreads();
-        S16_TCK(3);                                         // phase-2 work + wait at the top barrier
-        if (!conv_role) {
-#pragma unroll
-            for (int k = 0; k < C::KW; ++k) {
-                const int e = t2 + k * 256;
-                int t, le; word(e < C::NWORD ? e : C::NWORD - 1, t, le);
-                const int ry = le / (2 * C::HW), gy = ty0 - (t == 0 ? 2 : 1) + ry;
-                const bool in = gy >= 0 && gy < C::HW;
-                unsigned short* dst = (t == 0 ? s_x : (t == 1 ? s_a : s_p)) + (ry * C::P + (le >> 1) % C::HW + 1) * C::S + (le & 1) * 8;
-                const uint4 v = __builtin_bit_cast(uint4, st[20 + k]);
-                const uint4 r = t == 0 ? v : (uint4){rb_relu2(v.x), rb_relu2(v.y), rb_relu2(v.z), rb_relu2(v.w)};
-                if (e < C::NWORD) *(uint4*)dst = in ? r : (uint4){0u, 0u, 0u, 0u};
-            }
-        }
-        __syncthreads();
-        S16_TCK(0);                                         // staging (+ the conv waves' wait for it)
-        if (!conv_role) load(item(work + gridDim.x));
-
-        if (conv_role) {
-            // ---- da = convT2(dy) * (a > 0) on rows ty0-1 .. ty0+TH -> s_y: tiles rw, rw+4, ... in groups of CG: a group's operand reads go
-            // out together, then its MFMAs (K-step-major: the accumulator chains of the group interleave)
-#pragma unroll
-            for (int g0 = 0; g0 < C::MT1; g0 += CG) {
-                bf16x8 av[CG][C::NK];
-                uint2 mk[CG];
-                int yb[CG];
-#pragma unroll
-                for (int q = 0; q < CG; ++q) {
-                    const int mt = g0 + q < C::MT1 ? g0 + q : C::MT1 - 1;
-                    int t = rw + 4 * mt; t = t < C::NMT1 ? t : C::NMT1 - 1;            // (a clamped duplicate rewrites the same values)
-                    const int pl = t * 16 + i, px = pl % C::HW, ry = pl / C::HW;
-                    const unsigned short* src = s_x + (ry * C::P + px) * C::S;
-                    yb[q] = (ry * C::P + px + 1) * C::S + kq * 4;
-#pragma unroll
-                    for (int m = 0; m < C::NK; ++m) av[q][m] = *(const bf16x8*)(src + koff[m]);
-                    mk[q] = *(const uint2*)(s_a + yb[q]);
-                }
-                f32x4 acc[CG];
-#pragma unroll
-                for (int q = 0; q < CG; ++q) acc[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int m = 0; m < C::NK; ++m)
-#pragma unroll
-                    for (int q = 0; q < CG; ++q) acc[q] = MFMA_BF16(__builtin_bit_cast(bf16x8, st[m]), av[q][m], acc[q]);
-#pragma unroll
-                for (int q = 0; q < CG; ++q) {
-                    float v[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = rb_lane(mk[q], r) > 0.f ? acc[q][r] : 0.f;
-                    const uint2 raw = rb_pack(v);
-                    *(uint2*)(s_y + yb[q]) = raw;
-                    if (a.da_out) {
-                        const int mt = g0 + q < C::MT1 ? g0 + q : C::MT1 - 1;
-                        int t = rw + 4 * mt; t = t < C::NMT1 ? t : C::NMT1 - 1;
-                        const int pl = t * 16 + i, px = pl % C::HW, ry = pl / C::HW, gy = ty0 - 1 + ry;
-                        if (ry >= 1 && ry <= C::TH) *(uint2*)(a.da_out + ((img * C::HW + gy) * C::HW + px) * C::C + kq * 4) = raw;
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);            // (register budget: the next group's reads stay behind this group's epilogue)
-            }
-        } else {
-            wgrad(s_x, 2, s_a, 0);                           // conv2's weight / bias gradient from (dy, relu(a)): nothing the conv waves are producing
-        }
-        S16_TCK(1);                                         // phase-1 work
-        __syncthreads();
-        S16_TCK(2);                                         // wait for the other role
-        if (conv_role) {
-            // ---- dx = convT1(da) * (x > 0) + dy on rows ty0 .. ty0+TH-1 -> HBM
-            static_assert(C::MT2 % CG == 0, "whole groups");
-#pragma unroll
-            for (int g0 = 0; g0 < C::MT2; g0 += CG) {
-                bf16x8 av[CG][C::NK];
-                uint2 mk[CG], sk[CG];
-#pragma unroll
-                for (int q = 0; q < CG; ++q) {
-                    const int pl = (rw + 4 * (g0 + q)) * 16 + i, px = pl % C::HW, oy = pl / C::HW;
-                    const unsigned short* src = s_y + (oy * C::P + px) * C::S;
-#pragma unroll
-                    for (int m = 0; m < C::NK; ++m) av[q][m] = *(const bf16x8*)(src + koff[m]);
-                    mk[q] = *(const uint2*)(s_p + ((oy + 1) * C::P + px + 1) * C::S + kq * 4);
-                    sk[q] = *(const uint2*)(s_x + ((oy + 2) * C::P + px + 1) * C::S + kq * 4);
-                }
-                f32x4 acc[CG];
-#pragma unroll
-                for (int q = 0; q < CG; ++q) acc[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int m = 0; m < C::NK; ++m)
-#pragma unroll
-                    for (int q = 0; q < CG; ++q) acc[q] = MFMA_BF16(__builtin_bit_cast(bf16x8, st[5 + m]), av[q][m], acc[q]);
-#pragma unroll
-                for (int q = 0; q < CG; ++q) {
-                    const int pl = (rw + 4 * (g0 + q)) * 16 + i, px = pl % C::HW, oy = pl / C::HW;
-                    float v[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = (rb_lane(mk[q], r) > 0.f ? acc[q][r] : 0.f) + rb_lane(sk[q], r);
-                    *(uint2*)(a.dx_out + ((img * C::HW + ty0 + oy) * C::HW + px) * C::C + kq * 4) = rb_pack(v);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else {
-            wgrad(s_y, 1, s_p, 10);                          // conv1's weight / bias gradient from (da, relu(x))
-        }
-    }
-#ifdef RBF_TIMING
-    if ((tid & 255) == 0) for (int q = 0; q < 4; ++q) atomicAdd(&g_rbf_timing[(tid >> 8) * 4 + q], (unsigned long long)tacc_[q]);
-#endif
-    // ---- the four weight-gradient waves summed through LDS in wave order; one slab per workgroup and layer
-    __syncthreads();
-    float* red = (float*)smem_h;                              // [2][WLEN] then [2][4][16] bias partials
-    float* redb = red + 2 * C::WLEN;
-    for (int w = 0; w < 4; ++w) {
-        if (!conv_role && rw == w) {
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int o = ((kq * 4 + r) * 9 + tap) * C::C + i;
-                    red[o] = (w == 0) ? st[tap][r] : red[o] + st[tap][r];
-                    red[C::WLEN + o] = (w == 0) ? st[10 + tap][r] : red[C::WLEN + o] + st[10 + tap][r];
-                }
-        }
-        __syncthreads();
-    }
-    if (!conv_role && i == 0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { redb[rw * 16 + kq * 4 + r] = st[9][r]; redb[4 * 16 + rw * 16 + kq * 4 + r] = st[19][r]; }
-    }
-    __syncthreads();
-    float* sl2 = a.slab2 + (long long)blockIdx.x * C::SLAB;
-    float* sl1 = a.slab1 + (long long)blockIdx.x * C::SLAB;
-    for (int e = tid; e < C::WLEN; e += C::NT) { sl2[e] = red[e]; sl1[e] = red[C::WLEN + e]; }
-    if (tid < 16) {
-        float t2s = 0.f, t1s = 0.f;
-        for (int w = 0; w < 4; ++w) { t2s += redb[w * 16 + tid]; t1s += redb[4 * 16 + w * 16 + tid]; }
-        sl2[C::WLEN + tid] = t2s; sl1[C::WLEN + tid] = t1s;
-    }
-}
-#endif      // RBFULL16_SPECIALISED == 1
-// ---- the same two roles with the tiles filled by LDS-DMA into TWO tile buffers (RBFULL16_SPECIALISED == 2, the default).
-// Phase clocks of the kernel above (scratch/kbench_rb16.hip): 28 % of an item is "staging" -- the weight-gradient waves wait for their
-// prefetched words, apply the ReLU and write 8 x 16 bytes per thread to LDS while the conv waves idle.  A row of a tile is 32 pixels x 32
-// bytes = 1 KB, contiguous in HBM (NHWC) and in LDS: exactly ONE global_load_lds_dwordx4 wave-instruction (lane = 16-byte word of the
-// row), no registers, no LDS store instructions.  So: two tile buffers (16-row tiles: 2 x 79 KB = 161 KB, one workgroup per CU); at the top of
-// item k the weight-gradient waves issue the row DMAs (56 per 16-row item) of item k + 1 into the other buffer (a whole item of flight time), drain them (vmcnt(0)) just before the item's last barrier.
-// What changes for the consumers: relu(a) / relu(x) are no longer applied while staging -- the tiles hold RAW a and x; the ReLU masks
-// read them as before (> 0 is the same truth), the weight-gradient operand fragments take the ReLU in registers (one v_pk_max_i16 per
-// dword: max(x, 0) on bf16 bits = the staged relu, -0 -> +0 included).  Rows outside the image (first / last item of an image) are
-// zero-filled with one 16-byte LDS store per lane by the wave that would have issued their DMA.  Two barriers per item instead of three,
-// both raw (s_waitcnt lgkmcnt(0) + s_barrier): a __syncthreads() would also wait for the conv waves' dx stores.
+// ---- 16 channels @32x32: resblock_bwd_full16d_bf16_kernel.  512 threads, ONE workgroup per CU, an item = 16 rows of an image (two items
+// per image: 20 rows of dy and 18 rows each of a and x per 16 rows of output, halo rows re-read 1.17x).
+// LDS: TWO tile buffers (2 x 79 KB) of four haloed tiles each -- s_x (dy, rows ty0-2 .. ty0+17), s_y (d(conv1 output), rows ty0-1 ..
+// ty0+16), s_a (conv1 output) and s_p (block input), same rows as s_y; 32-byte pixels, one zero column each side (zeroed once per launch).
+// Item k is computed in buffer k % 2 while the rows of item k + 1 land in the other one.
+// Filling: a row of a tile is 32 pixels x 32 bytes = 1 KB, contiguous in HBM (NHWC) and in LDS: exactly ONE global_load_lds_dwordx4
+// wave-instruction (lane = 16-byte word of the row), no registers, no LDS store instructions.  The tiles therefore hold RAW a and x: the
+// ReLU masks test them as they are (> 0 is the same truth before and after a ReLU) and the weight-gradient operand fragments take the
+// ReLU in registers (one v_pk_max_i16 per dword: max(x, 0) on bf16 bits, -0 -> +0 included).  A row outside the image (first / last
+// item of an image) is filled by a DMA from a row of zeros, so every wave issues the same number of DMAs per item and every wait for
+// them is a counted immediate.
+// The eight waves take two ROLES and each SIMD hosts one wave of each, so the matrix work of one overlaps the LDS work of the other:
+//   waves 0-3  the two transposed convs, BOTH filter banks in registers (2 x 5 fragments = 40 VGPRs, loaded once per launch: no weight
+//              reads from LDS, no bank copies in LDS): phase 1 da = convT2(dy) * (a > 0) -> s_y (and HBM if asked), phase 2
+//              dx = convT1(da) * (x > 0) + dy -> HBM; pixel tiles in groups of RBFULL16D_CG, a group's operand reads out before its first MFMA;
+//   waves 4-7  the weight gradients -- conv2's from (dy, relu(a)) in phase 1, which needs nothing the conv waves are producing, conv1's
+//              from (da, relu(x)) in phase 2 -- four CONSECUTIVE pixel rows per wave with the operand rows shared between them, both
+//              layers' 9 tiles + bias row kept in registers across the persistent loop; and the next item's row DMAs (14 per wave),
+//              issued between their MFMA groups.
+// Barriers: two per item -- after phase 1 (da complete) and after phase 2 (everyone is done with this buffer and the next item's rows,
+// drained with vmcnt(0) by the waves that issued them, have landed) -- both raw (s_waitcnt lgkmcnt(0) + s_barrier): a __syncthreads()
+// would also wait for the conv waves' dx stores.  After the last item the four weight-gradient waves sum their accumulators through LDS
+// in wave order: one slab per workgroup and layer.
 // The DMAs are issued from inline asm (the compiler, seeing an LDS write it cannot place, would wait for a builtin's load before the next
 // LDS read of the issuing wave): M0 is set in the same statement, the waits are explicit, and the kernel drains its last prefetch before exit.
 __device__ __forceinline__ void rb_glds16(const void* gsrc, unsigned lds_dst) {
@@ -1376,14 +733,8 @@ __device__ unsigned short g_rb_zero_row[64 * 512];     // 64 x 1 KB of zeros: th
 #ifndef RBFULL16D_CG
 #define RBFULL16D_CG 5
 #endif
-#ifndef RBFULL16D_INTERLEAVE
-#define RBFULL16D_INTERLEAVE 1
-#endif
 #ifndef RBFULL16D_N1
 #define RBFULL16D_N1 10             // rows (of a weight-gradient wave's 14) issued during phase 1; the rest during phase 2 (engine, us per launch: all up front 268, 14: 256, 10: 249)
-#endif
-#ifndef RBFULL16D_NC
-#define RBFULL16D_NC 0             // tile rows (of 32) whose DMA each conv wave issues (measured: 0 best -- 338 us; 2 / 3 / 4: 374-387 / 376-380 / 365-371)
 #endif
 __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFullArgs a) {
     using C = RbFull16S;
@@ -1399,7 +750,9 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
     constexpr int NBUF = RBFULL16D_NBUF;                    // tile buffers: item k computes in buffer k % NBUF while the rows of items k+1 .. k+NBUF-1 are in flight / landed
     for (int e = tid; e < NBUF * TILE / 8; e += C::NT) ((uint4*)smem_h)[e] = (uint4){0u, 0u, 0u, 0u};   // column halos of all buffers stay zero
     constexpr int NST = 20;
-    f32x4 st[NST];                                          // conv role: st[m] / st[5 + m] bank fragments; weight-gradient role: accumulators (as above)
+    f32x4 st[NST];                                          // ONE register array for both roles (a kernel's registers are allocated for the union of what its
+                                                            // waves keep live).  conv role: st[m] = bank fragment of K step m of conv2's transposed bank, st[5 + m]
+                                                            // of conv1's; weight-gradient role: st[tap] / st[10 + tap] accumulator tiles of conv2 / conv1, st[9] / st[19] their bias rows
     if (conv_role) {
 #pragma unroll
         for (int m = 0; m < C::NK; ++m) {
@@ -1424,15 +777,14 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
     const int nwork = a.n * C::TPI;
     const unsigned lds0 = (unsigned)(unsigned long long)(void*)smem_h;          // LDS byte address of the tile buffers (low half of the flat address)
     auto item = [&](int w) { return w < nwork ? w : nwork - 1; };
-    // the 32 tile rows of item `work` -> buffer b, rows rw, rw + 4, ... by this (weight-gradient) wave: a DMA per row inside the image, zeros otherwise
-    // (issuing one row costs its wave ~150 cycles -- 1 KB through the CU's load path -- so the rows are dealt to BOTH roles: NC per conv
-    //  wave, the rest to the weight-gradient waves, whose phases are the shorter ones)
-    constexpr int NROW = C::XR + 2 * C::YR, NC = RBFULL16D_NC, NWR = (NROW - 4 * NC + 3) / 4;
+    // the 56 tile rows of item `work` -> buffer b, rows rw, rw + 4, ... by this (weight-gradient) wave: a DMA per row inside the image, zeros otherwise
+    // (issuing one row costs its wave ~150 cycles -- 1 KB through the CU's load path; the weight-gradient waves' phases are the shorter ones)
+    constexpr int NROW = C::XR + 2 * C::YR, NWR = (NROW + 3) / 4;
     // row jj (of this wave's share) of item `work` -> buffer b
     auto fill_row = [&](int work, int b, int jj) {
         const long long img = work / C::TPI; const int ty0 = (work % C::TPI) * C::TH;
-        if (jj >= (conv_role ? NC : NWR)) return;           // (wave-uniform)
-        const int j = conv_role ? 4 * NWR + rw + 4 * jj : rw + 4 * jj;
+        if (conv_role || jj >= NWR) return;                 // (wave-uniform) the conv waves issue no DMAs: 0 best -- 338 us; 2 / 3 / 4 rows each: 365-387
+        const int j = rw + 4 * jj;
         if (j >= NROW) return;
         const int t = j < C::XR ? 0 : (j < C::XR + C::YR ? 1 : 2), ry = j - (t == 0 ? 0 : (t == 1 ? C::XR : C::XR + C::YR));
         const int gy = ty0 - (t == 0 ? 2 : 1) + ry;
@@ -1446,16 +798,16 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
     };
     auto fill = [&](int work, int b) {
 #pragma unroll
-        for (int jj = 0; jj < (NC > NWR ? NC : NWR); ++jj) fill_row(work, b, jj);
+        for (int jj = 0; jj < NWR; ++jj) fill_row(work, b, jj);
     };
     auto relu8 = [](bf16x8 v) {
         const uint4 u = __builtin_bit_cast(uint4, v);
         return __builtin_bit_cast(bf16x8, (uint4){rb_relu2(u.x), rb_relu2(u.y), rb_relu2(u.z), rb_relu2(u.w)});
     };
     // weight gradient of one layer over this wave's NR consecutive pixel rows: d = output-gradient tile (row offset d_row), b = RAW input tile
-    // RBFULL16D_INTERLEAVE: conv2's weight gradient (phase 1) issues the NEXT item's row DMAs between its MFMA groups, a few per pixel row --
-    // issued back to back at the top of the item they cost the wave ~190 cycles each (the CU's load path drains at its share of HBM and the
-    // wave waits for queue space), 2600 cycles per item in front of phase 1 while the conv waves waited at the mid barrier.
+    // Conv2's weight gradient (phase 1) issues the NEXT item's row DMAs between its MFMA groups, a few per pixel row -- issued back to
+    // back at the top of the item they cost the wave ~190 cycles each (the CU's load path drains at its share of HBM and the wave waits
+    // for queue space), 2600 cycles per item in front of phase 1 while the conv waves waited at the mid barrier.
     // The first N1 rows go out during phase 1, the rest during phase 2 (whose weight-gradient work is the shorter role's).
     constexpr int N1 = RBFULL16D_N1 < NWR ? RBFULL16D_N1 : NWR;
     auto wgrad = [&](const unsigned short* s_d, int d_row, const unsigned short* s_b, const int a0, int fill_work, int fill_b, const int f_lo, const int f_hi) {
@@ -1479,11 +831,9 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
             bf16x8 fb[3];
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) fb[kx] = relu8(tr(s_b, ((r0 + R) * C::P + kx) * C::S));
-            if (RBFULL16D_INTERLEAVE) {
 #pragma unroll
-                for (int f = 0; f < 4; ++f)
-                    if (f < FPR && f_lo + R * FPR + f < f_hi) fill_row(fill_work, fill_b, f_lo + R * FPR + f);
-            }
+            for (int f = 0; f < 4; ++f)
+                if (f < FPR && f_lo + R * FPR + f < f_hi) fill_row(fill_work, fill_b, f_lo + R * FPR + f);
 #pragma unroll
             for (int j = 0; j < C::NR; ++j) {
                 const int ky = R - j;
@@ -1496,9 +846,9 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
 
     rb_raw_barrier();                                       // the zero fill is in
 #pragma unroll
-    for (int d = 0; d < NBUF - 1; ++d) fill(item(blockIdx.x + d * gridDim.x), d);
+    for (int d = 0; d < NBUF - 1; ++d) fill(item(blockIdx.x + d * gridDim.x), d);           // (the weight-gradient waves; the conv waves issue none)
     // rows of the first item landed: all but the (NBUF - 2) x rows-per-wave youngest DMAs of this wave
-    if (conv_role) rb_wait_vm<(NBUF - 2) * NC>(); else rb_wait_vm<(NBUF - 2) * NWR>();
+    if (conv_role) rb_wait_vm<0>(); else rb_wait_vm<(NBUF - 2) * NWR>();
     rb_raw_barrier();
     // The item loop is instantiated once per wave role (a generic lambda called with true_type / false_type): with one loop body for both
     // roles the compiler kept the role-union register array st[] consistent at the back-edge with a copy of all 80 dwords (60 v_mov per
@@ -1521,7 +871,9 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
         unsigned short* s_a = s_y + C::Y_ELEMS;
         unsigned short* s_p = s_a + C::Y_ELEMS;
         S16_TCK(3);                                         // (phase-2 work + wait at the end barrier of the previous item)
-        if (!RBFULL16D_INTERLEAVE || conv_role) fill(item(work + (NBUF - 1) * gridDim.x), (b + NBUF - 1) % NBUF);      // that buffer's readers (item k - 1) finished before the barrier that ended the previous item
+        // Issues nothing: fill_row returns at once for a conv wave.  The call stays because the compiler allocates the kernel's registers
+        // differently without it (2810 instead of 2813 instructions, never measured); taking it out is a change to measure on its own.
+        if (conv_role) fill(item(work + (NBUF - 1) * gridDim.x), (b + NBUF - 1) % NBUF);
         S16_TCK(0);                                         // DMA issue
         if (conv_role) {
             // ---- da = convT2(dy) * (a > 0) on rows ty0-1 .. ty0+TH -> s_y
@@ -1597,8 +949,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            // this wave's row DMAs are older than its MT2 dx stores and the counter retires in order: all but the MT2 youngest done = rows landed
-            rb_wait_vm<(NBUF - 2) * NC + C::MT2>();
+            rb_wait_vm<C::MT2>();                            // (no DMAs of its own: at most this item's MT2 dx stores stay in flight across the barrier)
         } else {
             wgrad(s_y, 1, s_p, 10, item(work + (NBUF - 1) * gridDim.x), (b + NBUF - 1) % NBUF, N1, NWR);      // conv1's weight / bias gradient from (da, relu(x)) + the remaining rows
             rb_wait_vm<(NBUF - 2) * NWR>();                  // the NEXT item's rows have landed: all but the rows of the items after it
@@ -1642,288 +993,65 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
         sl2[C::WLEN + tid] = t2s; sl1[C::WLEN + tid] = t1s;
     }
 }
-// Which whole-backward kernel the 16-channel blocks run (RBFULL16_SPECIALISED): 0 = resblock_bwd_full_bf16_kernel (256 threads, two
-// workgroups per CU), 1 = the wave-specialised one (register staging), 2 = wave-specialised + LDS-DMA into RBFULL16D_NBUF tile buffers
-// (DEFAULT, with 16-row tiles).  Measured (round 3, us per 8192-sample launch): micro-bench on random data 0: 348-371, 1: 368-376,
-// 2 with 8-row tiles: 330-363 (2 or 3 buffers alike), 2 with 16-row tiles: 346-347 where 0 ran 362-371; in the engine (HIP events, A/B of
-// library builds on one box, three rounds) 0: 272-278, 2 / 8 rows: 265-267, 2 / 16 rows: 258-263.  dx is bit-identical in all of them.
-// All variants end up bound by the same thing -- how fast a CU gets an item's bytes through its load path (a row's DMA costs its wave
-// ~150 cycles of issue: the queue drains at the CU's share of HBM) -- which is why fewer BYTES (16-row tiles: 36 instead of 41 KB per 8
-// rows) bought more than any re-arrangement of the work.
-// (Also tried on variant 2: two more waves, 640 threads, that only issue the row DMAs and wait for them -- the kernel then has to fit
-//  168 registers, spills 28-43 whatever the conv group size, and runs 560 us; issuing the rows from a run-time loop instead of the
-//  unrolled one: 415 against 335.)
-#ifndef RBFULL16S_BPC
-#define RBFULL16S_BPC 1            // workgroups per CU of the specialised kernel
-#endif
-int resblock_bwd_full_grid(int n) {
-    if (RBFULL16_SPECIALISED) { const int w = n * RbFull16S::TPI; return w > 256 * RBFULL16S_BPC ? 256 * RBFULL16S_BPC : w; }
-    int bpc = (int)((160 * 1024) / RbFull::LDS_BYTES);
-    bpc = bpc < 1 ? 1 : (bpc > 4 ? 4 : bpc);
-    const int w = n * RbFull::TPI;
-    return w > 256 * bpc ? 256 * bpc : w;
-}
+// Measured (us per 8192-sample launch, HIP events in the engine): 258-263; the history of the variants it replaced is in DESIGN.md section 7.
+// What bounds it is how fast a CU gets an item's bytes through its load path (a row's DMA costs its wave ~150 cycles of issue: the queue
+// drains at the CU's share of HBM) -- which is why fewer BYTES (16-row tiles: 36 instead of 41 KB per 8 rows) bought more than any
+// re-arrangement of the work.
+// (Also tried: two more waves, 640 threads, that only issue the row DMAs and wait for them -- the kernel then has to fit 168 registers,
+//  spills 28-43 whatever the conv group size, and runs 560 us; issuing the rows from a run-time loop instead of the unrolled one: 415 against 335.)
+int resblock_bwd_full_grid(int n) { const int w = n * RbFull16S::TPI; return w > 256 ? 256 : w; }      // one workgroup per CU
 // 16-channel residual blocks @32x32 only (CS_16_16_32).  slab2 / slab1: [grid][2320] floats each (grid = resblock_bwd_full_grid(n)).
-bool launch_resblock_bwd_full_event_ok() { return RBFULL16_SPECIALISED == 2; }
 void launch_resblock_bwd_full_bf16(const void* dy, const void* a_fwd, const void* x_fwd, void* dx_out, void* da_out, int n,
                                    const unsigned short* bank2_t, const unsigned short* bank1_t, float* slab2, float* slab1, hipStream_t st, hipEvent_t done_ev) {
-    static std::once_flag attr;          // (launchers run on up to 4 group worker threads)
-    std::call_once(attr, [] { hipFuncSetAttribute((const void*)resblock_bwd_full_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RbFull::LDS_BYTES); });
     const int grid = resblock_bwd_full_grid(n);
     if (grid < 1) return;
     RbFullArgs a{(const unsigned short*)dy, (const unsigned short*)a_fwd, (const unsigned short*)x_fwd, (unsigned short*)dx_out, (unsigned short*)da_out,
                  bank2_t, bank1_t, slab2, slab1, n};
-    if (RBFULL16_SPECIALISED) {
-        static std::once_flag attr_s;
-        // one workgroup per CU: request more LDS than the tiles need so that a second workgroup never lands on the same CU (RBFULL16S_BPC == 1)
-        constexpr size_t LDS_S = RBFULL16S_BPC == 1 ? (RbFull16S::LDS_BYTES > 84 * 1024 ? RbFull16S::LDS_BYTES : 84 * 1024) : RbFull16S::LDS_BYTES;
-#if RBFULL16_SPECIALISED == 1
-        std::call_once(attr_s, [] { hipFuncSetAttribute((const void*)resblock_bwd_full16s_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_S); });
-#endif
-        if (RBFULL16_SPECIALISED == 2) {
-            static std::once_flag attr_d;
-            constexpr size_t LDS_D = RBFULL16D_NBUF * RbFull16S::TILE_BYTES > RbFull16S::RED_BYTES ? RBFULL16D_NBUF * RbFull16S::TILE_BYTES : RbFull16S::RED_BYTES;
-            static_assert(LDS_D > 80 * 1024 && LDS_D <= 160 * 1024, "one workgroup per CU");
-            std::call_once(attr_d, [] { hipFuncSetAttribute((const void*)resblock_bwd_full16d_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_D); });
-            // done_ev: this launch's completion as an event (the dispatch packet's own signal: no marker packet behind the kernel)
-            if (done_ev) hipExtLaunchKernelGGL(resblock_bwd_full16d_bf16_kernel, dim3(grid), dim3(512), (unsigned)LDS_D, st, nullptr, done_ev, 0, a);
-            else
-            hipLaunchKernelGGL(resblock_bwd_full16d_bf16_kernel, dim3(grid), dim3(512), LDS_D, st, a);
-            return;
-        }
-#if RBFULL16_SPECIALISED == 1
-        hipLaunchKernelGGL(resblock_bwd_full16s_bf16_kernel, dim3(grid), dim3(512), LDS_S, st, a);
-#endif
-        return;
-    }
-    hipLaunchKernelGGL(resblock_bwd_full_bf16_kernel, dim3(grid), dim3(RbFull::NT), RbFull::LDS_BYTES, st, a);
+    // both tile buffers: more than half a CU's LDS, so a second workgroup never lands on the same CU
+    constexpr size_t LDS_D = RBFULL16D_NBUF * RbFull16S::TILE_BYTES > RbFull16S::RED_BYTES ? RBFULL16D_NBUF * RbFull16S::TILE_BYTES : RbFull16S::RED_BYTES;
+    static_assert(LDS_D > 80 * 1024 && LDS_D <= 160 * 1024, "one workgroup per CU");
+    static std::once_flag attr;          // (launchers run on up to 4 group worker threads)
+    std::call_once(attr, [] { hipFuncSetAttribute((const void*)resblock_bwd_full16d_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_D); });
+    // done_ev: this launch's completion as an event (the dispatch packet's own signal: no marker packet behind the kernel)
+    if (done_ev) hipExtLaunchKernelGGL(resblock_bwd_full16d_bf16_kernel, dim3(grid), dim3(512), (unsigned)LDS_D, st, nullptr, done_ev, 0, a);
+    else hipLaunchKernelGGL(resblock_bwd_full16d_bf16_kernel, dim3(grid), dim3(512), LDS_D, st, a);
 }
 
-// ------------------------------------------------------------------------------------------ whole backward, 32-channel blocks @16x16
-// Same scheme as resblock_bwd_full_bf16_kernel with the sizes forcing two changes: tiles (72.6 KB) + the two transposed
-// filter banks (39 KB) leave room for ONE workgroup per CU, so the workgroup is 512 threads (8 waves = 2 per SIMD, what two
-// 256-thread workgroups would give); and the 2 x 36 weight-gradient accumulator tiles are dealt to the waves by (tap, input
-// block) column as in the column-split stand-alone kernel: every wave walks all 4 pixel steps with its 2-3 columns of both
-// layers and owns its slab entries outright (no cross-wave reduction).  (A 256-thread variant with the banks streamed from
-// L2 instead of LDS measured 410 us per launch: every K step waited ~0.5 us for its filter fragment.)
-template <int HW_, int NT_, int TH_ = 8>
-struct RbFull32T {                               // HW 16: 8-row tiles, 512 threads; HW 8: whole image, 256 threads (79 KB: two per CU)
-    static constexpr int C = 32, HW = HW_, TH = TH_, S = RB_S32, P = HW + 2, TPI = HW / TH, NT = NT_, NW = NT_ / 64;
+// ------------------------------------------------------------------------------------------ whole backward, 32-channel blocks
+// Tile geometry of the 16x16 kernel: items of TH rows of a HW x HW image, staged with two halo rows (dy) / one (everything else).
+template <int HW_, int NT_, int TH_>
+struct RbFull32T {
+    static constexpr int C = 32, HW = HW_, TH = TH_, S = RB_S32, P = HW + 2, TPI = HW / TH, NT = NT_;
     static constexpr int XR = TH + 4, YR = TH + 2;
     static constexpr int X_ELEMS = XR * P * S, Y_ELEMS = YR * P * S;
-    static constexpr int NK = 9, WS = NK * 32 + 16, W_ELEMS = C * WS;
-    static constexpr int NMT1 = YR * HW / 16, NMT2 = TH * HW / 16;                                            // HW 16: 10 / 8 tiles over 8 waves; HW 8: 5 / 4 over 4 waves
-    static_assert(TH != 8 || (NMT2 == NW && NMT1 <= 2 * NW), "one conv2 tile and at most two conv1 tiles per wave");
+    static constexpr int NK = 9, WS = NK * 32 + 16;                                                            // packed bank: row stride of an output channel
+    static constexpr int NMT1 = YR * HW / 16, NMT2 = TH * HW / 16;                                            // pixel tiles of the two convs
     static constexpr int NX = XR * HW * 4, NA = YR * HW * 4;                                                  // 16-byte words staged per tensor
-    static constexpr int KX = (NX + NT - 1) / NT, KA = (NA + NT - 1) / NT;
-    static constexpr int NSTEP = TH * HW / 32;                                                                 // 4 pixel steps of 32
-    static constexpr int NQ = 18, QMAX = (NQ + NW - 1) / NW;                                                   // (tap, input block) columns; per wave
+    static constexpr int NSTEP = TH * HW / 32;                                                                 // pixel steps of 32
+    static constexpr int NQ = 18;                                                                              // (tap, input block) columns
     static constexpr int WLEN = C * 9 * C, SLAB = WLEN + C;
-    static constexpr size_t LDS_BYTES = (size_t)(X_ELEMS + 3 * Y_ELEMS + 2 * W_ELEMS) * 2;
 };
-using RbFull32 = RbFull32T<16, 512>;
 #ifndef RB32S_TH
-#define RB32S_TH 16          // rows per item of the wave-specialised kernel: 16 = whole image (128 KB of LDS now that no bank sits there): no halo rows re-read or
+#define RB32S_TH 16          // rows per item of resblock_bwd_full32s_bf16_kernel: 16 = whole image (128 KB of LDS, no bank sits there): no halo rows re-read or
 #endif                       // recomputed, three barriers per image instead of six.  It needs the weight-gradient step loops unrolled by 4, not 8 (spills: 1007 us);
                              // micro-bench per 8192 images: 8-row items 220-222 us, 16-row items 203 (step loops rolled / by 2: 206-212)
 using RbFull32W = RbFull32T<16, 512, RB32S_TH>;
-using RbFull32S = RbFull32T<8, 256>;
-
-template <class C>
-__global__ __launch_bounds__(C::NT, C::NT == 256 ? 2 : 1) void resblock_bwd_full32_bf16_kernel(RbFullArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned short smem_h[];
-    unsigned short* s_x = smem_h;                         // dy rows ty0-2 .. ty0+TH+1
-    unsigned short* s_y = s_x + C::X_ELEMS;               // d(conv1 output) rows ty0-1 .. ty0+TH
-    unsigned short* s_a = s_y + C::Y_ELEMS;               // relu(conv1 output), same rows
-    unsigned short* s_p = s_a + C::Y_ELEMS;               // relu(block input), same rows
-    unsigned short* s_w1 = s_p + C::Y_ELEMS;              // transposed bank of conv2 (first conv of this pass)
-    unsigned short* s_w2 = s_w1 + C::W_ELEMS;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, kq = lane >> 4, rq = (lane & 15) >> 2, cp = lane & 3;
-    const int wv = __builtin_amdgcn_readfirstlane(wave);
-    const int qcnt = (C::NQ - wv + C::NW - 1) / C::NW;    // columns q = wv + NW*qq, qq < qcnt (8 waves: 3, 3, 2, 2, 2, 2, 2, 2)
-    for (int e = tid; e < C::W_ELEMS / 8; e += C::NT) { ((uint4*)s_w1)[e] = ((const uint4*)a.bank2_t)[e]; ((uint4*)s_w2)[e] = ((const uint4*)a.bank1_t)[e]; }
-    for (int e = tid; e < (C::X_ELEMS + 3 * C::Y_ELEMS) / 8; e += C::NT) ((uint4*)smem_h)[e] = (uint4){0u, 0u, 0u, 0u};   // column halos stay zero
-    int koff[C::NK];
-#pragma unroll
-    for (int m = 0; m < C::NK; ++m) koff[m] = ((m / 3) * C::P + (m % 3)) * C::S + kq * 8;     // 32 channels: one tap per K step, lane quarter = 8-channel chunk
-    f32x4 acc2[C::QMAX][2], acc1[C::QMAX][2], accb[2];                                        // weight-gradient tiles [column][output block]; bias rows (waves 6, 7)
-#pragma unroll
-    for (int q = 0; q < C::QMAX; ++q)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) { acc2[q][cb] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc1[q][cb] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-    accb[0] = accb[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const bf16x8 ones = __builtin_bit_cast(bf16x8, (uint4){0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u});
-    const int bbase = i * C::WS + kq * 8;
-
-    const int nwork = a.n * C::TPI;
-    uint4 rx[C::KX], ra[C::KA], rp[C::KA];
-    auto load = [&](int work) {
-        const long long img = work / C::TPI; const int ty0 = (work % C::TPI) * C::TH;
-#pragma unroll
-        for (int k = 0; k < C::KX; ++k) {
-            const int e = tid + k * C::NT;
-            uint4 v = {0u, 0u, 0u, 0u};
-            if (e < C::NX) { const int c8 = e & 3, px = (e >> 2) % C::HW, gy = ty0 - 2 + e / (4 * C::HW);
-                             if (gy >= 0 && gy < C::HW) v = *(const uint4*)(a.dy + ((img * C::HW + gy) * C::HW + px) * C::C + c8 * 8); }
-            rx[k] = v;
-        }
-#pragma unroll
-        for (int k = 0; k < C::KA; ++k) {
-            const int e = tid + k * C::NT;
-            uint4 va = {0u, 0u, 0u, 0u}, vp = {0u, 0u, 0u, 0u};
-            if (e < C::NA) { const int c8 = e & 3, px = (e >> 2) % C::HW, gy = ty0 - 1 + e / (4 * C::HW);
-                             if (gy >= 0 && gy < C::HW) { const long long o = ((img * C::HW + gy) * C::HW + px) * C::C + c8 * 8;
-                                                          va = *(const uint4*)(a.a_fwd + o); vp = *(const uint4*)(a.x_fwd + o); } }
-            ra[k] = va; rp[k] = vp;
-        }
-    };
-    if ((int)blockIdx.x < nwork) load(blockIdx.x);
-    for (int work = blockIdx.x; work < nwork; work += gridDim.x) {
-        const long long img = work / C::TPI; const int ty0 = (work % C::TPI) * C::TH;
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < C::KX; ++k) {
-            const int e = tid + k * C::NT;
-            if (e < C::NX) *(uint4*)(s_x + ((e / (4 * C::HW)) * C::P + (e >> 2) % C::HW + 1) * C::S + (e & 3) * 8) = rx[k];
-        }
-#pragma unroll
-        for (int k = 0; k < C::KA; ++k) {
-            const int e = tid + k * C::NT;
-            if (e < C::NA) {
-                const int o = ((e / (4 * C::HW)) * C::P + (e >> 2) % C::HW + 1) * C::S + (e & 3) * 8;
-                *(uint4*)(s_a + o) = (uint4){rb_relu2(ra[k].x), rb_relu2(ra[k].y), rb_relu2(ra[k].z), rb_relu2(ra[k].w)};
-                *(uint4*)(s_p + o) = (uint4){rb_relu2(rp[k].x), rb_relu2(rp[k].y), rb_relu2(rp[k].z), rb_relu2(rp[k].w)};
-            }
-        }
-        __syncthreads();
-        if (work + (int)gridDim.x < nwork) load(work + gridDim.x);
-
-        // ---- da = convT2(dy) * (a > 0) on rows ty0-1 .. ty0+TH -> s_y (rows outside the image: relu(a) is 0 there, so da is 0)
-        {
-            const int nmt = (C::NMT1 - wv + C::NW - 1) / C::NW;          // 8 waves: 2, 2, 1, 1, 1, 1, 1, 1
-            int abase[2], ybase[2];
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                int t = wave + C::NW * mt; t = t < C::NMT1 ? t : C::NMT1 - 1;
-                const int pl = t * 16 + i, px = pl % C::HW, ry = pl / C::HW;
-                abase[mt] = (ry * C::P + px) * C::S;
-                ybase[mt] = (ry * C::P + px + 1) * C::S + kq * 4;
-            }
-            f32x4 acc[2][2];
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) { acc[mt][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[mt][1] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-            for (int m = 0; m < C::NK; ++m) {
-                const bf16x8 b0 = *(const bf16x8*)(s_w1 + bbase + m * 32), b1 = *(const bf16x8*)(s_w1 + bbase + 16 * C::WS + m * 32);
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-                    if (mt < nmt) {
-                        const bf16x8 av = *(const bf16x8*)(s_x + abase[mt] + koff[m]);
-                        acc[mt][0] = MFMA_BF16(b0, av, acc[mt][0]);
-                        acc[mt][1] = MFMA_BF16(b1, av, acc[mt][1]);
-                    }
-            }
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-                if (mt < nmt) {
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb) {
-                        const uint2 mk = *(const uint2*)(s_a + ybase[mt] + nb * 16);
-                        float v[4];
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = rb_lane(mk, r) > 0.f ? acc[mt][nb][r] : 0.f;
-                        const uint2 raw = rb_pack(v);
-                        *(uint2*)(s_y + ybase[mt] + nb * 16) = raw;
-                        if (a.da_out) {
-                            const int pl = (wave + C::NW * mt) * 16 + i, px = pl % C::HW, ry = pl / C::HW, gy = ty0 - 1 + ry;
-                            if (ry >= 1 && ry <= C::TH) *(uint2*)(a.da_out + ((img * C::HW + gy) * C::HW + px) * C::C + nb * 16 + kq * 4) = raw;
-                        }
-                    }
-                }
-        }
-        __syncthreads();
-        // ---- dx = convT1(da) * (x > 0) + dy on rows ty0 .. ty0+TH-1 -> HBM: one 16-pixel tile per wave
-        {
-            const int pl = wave * 16 + i, px = pl % C::HW, oy = pl / C::HW;
-            const int abase = (oy * C::P + px) * C::S;
-            f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-            for (int m = 0; m < C::NK; ++m) {
-                const bf16x8 av = *(const bf16x8*)(s_y + abase + koff[m]);
-                acc[0] = MFMA_BF16(*(const bf16x8*)(s_w2 + bbase + m * 32), av, acc[0]);
-                acc[1] = MFMA_BF16(*(const bf16x8*)(s_w2 + bbase + 16 * C::WS + m * 32), av, acc[1]);
-            }
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb) {
-                const uint2 mk = *(const uint2*)(s_p + ((oy + 1) * C::P + px + 1) * C::S + nb * 16 + kq * 4);
-                const uint2 sk = *(const uint2*)(s_x + ((oy + 2) * C::P + px + 1) * C::S + nb * 16 + kq * 4);
-                float v[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = (rb_lane(mk, r) > 0.f ? acc[nb][r] : 0.f) + rb_lane(sk, r);
-                *(uint2*)(a.dx_out + ((img * C::HW + ty0 + oy) * C::HW + px) * C::C + nb * 16 + kq * 4) = rb_pack(v);
-            }
-        }
-        // ---- weight gradients: conv2 from (dy, relu(a)), conv1 from (da, relu(x)); every wave walks all pixel steps for its columns
-#pragma unroll
-        for (int t = 0; t < C::NSTEP; ++t) {
-            int orow[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int pl = 32 * t + 16 * (kq >> 1) + 8 * h + 4 * (kq & 1) + rq;
-                orow[h] = ((pl / C::HW) * C::P + pl % C::HW) * C::S + 4 * cp;
-            }
-            auto tr = [&](const unsigned short* base, int off) {
-                const rb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(base + orow[0] + off));
-                const rb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(base + orow[1] + off));
-                return (bf16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-            };
-            bf16x8 d2[2], d1[2];
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb) { d2[cb] = tr(s_x, (2 * C::P + 1) * C::S + cb * 16); d1[cb] = tr(s_y, (C::P + 1) * C::S + cb * 16); }
-            if (wv == C::NW - 2) { accb[0] = MFMA_BF16(d2[0], ones, accb[0]); accb[1] = MFMA_BF16(d2[1], ones, accb[1]); }      // bias of conv2
-            if (wv == C::NW - 1) { accb[0] = MFMA_BF16(d1[0], ones, accb[0]); accb[1] = MFMA_BF16(d1[1], ones, accb[1]); }      // bias of conv1
-#pragma unroll
-            for (int qq = 0; qq < C::QMAX; ++qq)
-                if (qq < qcnt) {                                   // wave-uniform: EXEC stays full for the transpose reads
-                    const int q = wv + C::NW * qq, tap = q >> 1, ib = q & 1;
-                    const int toff = ((tap / 3) * C::P + (tap % 3)) * C::S + ib * 16;
-                    const bf16x8 b2 = tr(s_a, toff), b1 = tr(s_p, toff);
-#pragma unroll
-                    for (int cb = 0; cb < 2; ++cb) { acc2[qq][cb] = MFMA_BF16(d2[cb], b2, acc2[qq][cb]); acc1[qq][cb] = MFMA_BF16(d1[cb], b1, acc1[qq][cb]); }
-                }
-        }
-    }
-    // ---- every wave owns its columns: straight to the slabs
-    float* sl2 = a.slab2 + (long long)blockIdx.x * C::SLAB;
-    float* sl1 = a.slab1 + (long long)blockIdx.x * C::SLAB;
-#pragma unroll
-    for (int qq = 0; qq < C::QMAX; ++qq)
-        if (qq < qcnt) {
-            const int q = wv + C::NW * qq, tap = q >> 1, ib = q & 1;
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int o = ((cb * 16 + kq * 4 + r) * 9 + tap) * C::C + ib * 16 + i;
-                    sl2[o] = acc2[qq][cb][r]; sl1[o] = acc1[qq][cb][r];
-                }
-        }
-    if (i == 0 && wv >= C::NW - 2) {
-        float* sl = wv == C::NW - 2 ? sl2 : sl1;
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sl[C::WLEN + cb * 16 + kq * 4 + r] = accb[cb][r];
-    }
-}
-// ---- wave-specialised variant (HW = 16, 512 threads).  The kernel above is LDS-bandwidth-bound in its conv phases: with one or two
-// 16-pixel tiles per wave every wave re-reads the whole filter bank (18 x 1 KB per conv and wave: 288 of the 738 KB an item reads),
-// i.e. ~1.5 operand reads per MFMA, 6 LDS cycles against 16 MFMA cycles with eight waves on one LDS pipe.  Here the eight waves take
-// two ROLES: waves 0-3 (one per SIMD) run the two transposed convs with BOTH filter banks in registers (2 x 18 fragments = 144 VGPRs,
-// loaded once per launch: no weight reads at all), waves 4-7 run the weight gradients (conv2's while the conv waves produce da,
-// conv1's while they produce dx); each SIMD hosts one wave of each role, so matrix work of one overlaps the LDS work of the other.
-// Per item: LDS reads 738 -> 370 KB, same MFMA count, same three barriers.  Arithmetic per output element and per slab entry is
-// unchanged (same K order, same pixel-step order): results are bit-identical to the kernel above.
+// ---- 32 channels @16x16: resblock_bwd_full32s_bf16_kernel.  512 threads, one workgroup per CU, an item = RB32S_TH rows of an image
+// (16 = the whole image: no halo rows re-read or recomputed).
+// LDS (128 KB with whole images): four haloed tiles -- s_x (dy, item rows -2 .. TH+1), s_y (d(conv1 output), rows -1 .. TH), s_a
+// (relu(conv1 output)) and s_p (relu(block input)), same rows as s_y --, pixels RB_S32 elements apart.  No filter bank sits in LDS.
+// The eight waves take two ROLES and each SIMD hosts one wave of each, so the matrix work of one overlaps the LDS work of the other:
+//   waves 0-3  the two transposed convs with BOTH filter banks in registers (2 x 18 fragments = 144 VGPRs, loaded once per launch: no
+//              weight reads at all); pixel tiles rw, rw + 4, ... one at a time, a tile's nine operand reads in flight in batches of
+//              5 + 4 ahead of its 18 MFMAs: phase 1 da = convT2(dy) * (a > 0) -> s_y (and HBM if asked), phase 2
+//              dx = convT1(da) * (x > 0) + dy -> HBM;
+//   waves 4-7  stage the item (global -> registers one item ahead -> LDS, ReLU of a and x applied on the way) and run the weight
+//              gradients as in conv3x3_wgrad_bf16_kernel's column split: the 18 (tap, input block) columns are dealt to the four waves
+//              (5, 5, 4, 4), every wave walks all 32-pixel steps of the item with its columns of BOTH layers (20 accumulator tiles + 2
+//              bias rows, kept across the persistent loop) -- conv2's from (dy, relu(a)) in phase 1, which needs nothing the conv
+//              waves are producing, conv1's from (da, relu(x)) in phase 2 -- and owns its slab entries outright (no cross-wave sum).
+// Barriers: three per item (previous item's reads done, staging done, da complete).  An item reads 370 KB from LDS.  Every sum runs in a
+// fixed order (K order of the convs, pixel-step order of the weight gradients).
 #ifdef WG_TIMING      // scratch/kbench_rb.hip: per-phase shader-clock totals of wave 0 (conv role, slots 0-3) and wave 4 (weight-gradient role, 4-7)
 __device__ unsigned long long g_rb_timing[8];
 #define RTCK(k) do { if ((tid & 255) == 0) { const long long now_ = clock64(); tacc_[k] += now_ - tlast_; tlast_ = now_; } } while (0)
@@ -2176,7 +1304,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32s_bf16_kernel(RbFul
 #ifdef WG_TIMING
     if ((tid & 255) == 0) for (int q = 0; q < 4; ++q) atomicAdd(&g_rb_timing[(tid >> 8) * 4 + q], (unsigned long long)tacc_[q]);
 #endif
-    // ---- the weight-gradient waves own their columns: straight to the slabs (layout as the kernel above)
+    // ---- the weight-gradient waves own their columns: straight to the slabs ([output channel][tap][input channel], then the 32 bias sums)
     if (!conv_role) {
         float* sl2 = a.slab2 + (long long)blockIdx.x * C::SLAB;
         float* sl1 = a.slab1 + (long long)blockIdx.x * C::SLAB;
@@ -2202,15 +1330,20 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32s_bf16_kernel(RbFul
     }
 }
 
-// ---- 8x8 images, FOUR per item, wave-specialised (round 3).  The kernel above handles ONE 8x8 image per item: 256 threads, one pixel tile
-// per wave and conv -- every tile re-reads its conv's whole filter bank from LDS (18 KB of bank for 9 KB of pixels), three barriers per
-// image, and the launch ran 67-73 us for 17 MB of tensors at 12 % matrix-pipe activity.  Here an item is four images (256 pixels, the
-// pixel count of a 16x16 image) in the two-role scheme of resblock_bwd_full32s_bf16_kernel: conv waves 0-3 hold both transposed banks in
-// registers and take four pixel tiles per conv, weight-gradient waves 4-7 stage the tiles (every staged row is inside its image: plain
-// unconditional loads) and walk the item's eight 32-pixel steps with their columns.  LDS: per image four 10-row tiles (dy with its
-// zero rows -1 and 8 -- da is only needed on the image's own rows --, d(conv1 output), relu(conv1 output), relu(block input)), 153.6 KB.
-// Arithmetic per output element unchanged (same banks, same K order): dx is bit-identical to the kernel above; the slabs sum the same
-// products in another order of partial sums.
+// ---- 32 channels @8x8: resblock_bwd_full32q_bf16_kernel.  512 threads, one workgroup per CU, an item = FOUR images (256 pixels, the pixel
+// count of a 16x16 image; one image per item left every pixel tile re-reading its conv's whole bank for 9 KB of pixels at 12 % matrix-pipe activity).
+// LDS (153.6 KB): four tiles -- s_x (dy), s_y (d(conv1 output)), s_a (relu(conv1 output)), s_p (relu(block input)) -- each holding rows -1 .. 8
+// of the item's four images, one zero column each side, pixels RB_S32 elements apart.  Rows -1 and 8 and the column halos are zeroed once
+// per launch and never written again (da is only needed on the images' own rows), so every staged row is inside its image: plain
+// unconditional loads, and an image past the end of the batch is replaced by zeros at the LDS store.
+// Registers: one array st[36] for both roles (see resblock_bwd_full32s_bf16_kernel, whose two roles this kernel shares):
+//   waves 0-3  both transposed filter banks (2 x 18 fragments, loaded once per launch); four pixel tiles per conv, one at a time:
+//              phase 1 da = convT2(dy) * (a > 0) -> s_y (and HBM if asked), phase 2 dx = convT1(da) * (x > 0) + dy -> HBM;
+//   waves 4-7  stage the item (global -> registers one item ahead -> LDS with the ReLU of a and x applied, 3 x 4 words per thread) and
+//              run the weight gradients over the item's eight 32-pixel steps -- conv2's from (dy, relu(a)) in phase 1, conv1's from
+//              (da, relu(x)) in phase 2 --, each wave with its 4-5 of the 18 (tap, input block) columns in 20 accumulator tiles + 2 bias rows.
+// Barriers: three per item (previous item's reads done, staging done, da complete).  The weight-gradient waves own their columns and
+// write their accumulators straight to the workgroup's two slabs.
 struct RbFull32Q {
     static constexpr int C = 32, HW = 8, NIMG = 4, S = RB_S32, P = HW + 2, R = HW + 2;          // rows -1 .. 8 of every tile
     static constexpr int IMG_ELEMS = R * P * S, T_ELEMS = NIMG * IMG_ELEMS;                     // one image's / the item's share of a tile
@@ -2449,9 +1582,6 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32q_bf16_kernel(RbFul
         }
     }
 }
-#ifndef RB32_QUAD8
-#define RB32_QUAD8 1               // 8x8 blocks: 1 = resblock_bwd_full32q_bf16_kernel (four images per item), 0 = one image per item (kernel above)
-#endif
 static int rb_full32q_grid(int n) { const int w = (n + RbFull32Q::NIMG - 1) / RbFull32Q::NIMG; return w > 256 ? 256 : w; }
 static void launch_rb_full32q(const RbFullArgs& a, hipStream_t st) {
     static std::once_flag attr;
@@ -2461,29 +1591,6 @@ static void launch_rb_full32q(const RbFullArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(resblock_bwd_full32q_bf16_kernel, dim3(grid), dim3(512), RbFull32Q::LDS_BYTES, st, a);
 }
 
-template <class C>
-static int rb_full32_grid_t(int n) {
-    int bpc = (int)((160 * 1024) / C::LDS_BYTES);
-    bpc = bpc < 1 ? 1 : (bpc > 4 ? 4 : bpc);
-    const int w = n * C::TPI;
-    return w > 256 * bpc ? 256 * bpc : w;
-}
-#ifndef RB32_SPECIALISED
-#define RB32_SPECIALISED 1
-#endif
-static int rb_full32s_grid(int n);
-int resblock_bwd_full32_grid(ConvShape s, int n) { return s == CS_32_32_16 ? (RB32_SPECIALISED ? rb_full32s_grid(n) : rb_full32_grid_t<RbFull32>(n)) : s == CS_32_32_8 ? (RB32_QUAD8 ? rb_full32q_grid(n) : rb_full32_grid_t<RbFull32S>(n)) : -1; }
-template <class C>
-static void launch_rb_full32_t(const RbFullArgs& a, hipStream_t st) {
-    static std::once_flag attr;          // (launchers run on up to 4 group worker threads)
-    std::call_once(attr, [] { hipFuncSetAttribute((const void*)resblock_bwd_full32_bf16_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES); });
-    const int grid = rb_full32_grid_t<C>(a.n);
-    if (grid < 1) return;
-    hipLaunchKernelGGL(resblock_bwd_full32_bf16_kernel<C>, dim3(grid), dim3(C::NT), C::LDS_BYTES, st, a);
-}
-#ifndef RB32_SPECIALISED
-#define RB32_SPECIALISED 1
-#endif
 static int rb_full32s_grid(int n) { const int w = n * RbFull32W::TPI; return w > 256 ? 256 : w; }      // one 512-thread workgroup per CU
 static void launch_rb_full32s(const RbFullArgs& a, hipStream_t st) {
     using C = RbFull32W;
@@ -2494,13 +1601,14 @@ static void launch_rb_full32s(const RbFullArgs& a, hipStream_t st) {
     if (grid < 1) return;
     hipLaunchKernelGGL(resblock_bwd_full32s_bf16_kernel<C>, dim3(grid), dim3(512), LDS, st, a);
 }
+int resblock_bwd_full32_grid(ConvShape s, int n) { return s == CS_32_32_16 ? rb_full32s_grid(n) : s == CS_32_32_8 ? rb_full32q_grid(n) : -1; }
 // 32-channel residual blocks @16x16 (CS_32_32_16) and @8x8 (CS_32_32_8).  slab2 / slab1: [grid][9248] floats each.
 void launch_resblock_bwd_full32_bf16(ConvShape s, const void* dy, const void* a_fwd, const void* x_fwd, void* dx_out, void* da_out, int n,
                                      const unsigned short* bank2_t, const unsigned short* bank1_t, float* slab2, float* slab1, hipStream_t st) {
     RbFullArgs a{(const unsigned short*)dy, (const unsigned short*)a_fwd, (const unsigned short*)x_fwd, (unsigned short*)dx_out, (unsigned short*)da_out,
                  bank2_t, bank1_t, slab2, slab1, n};
-    if (s == CS_32_32_16) { if (RB32_SPECIALISED) launch_rb_full32s(a, st); else launch_rb_full32_t<RbFull32>(a, st); }
-    else if (s == CS_32_32_8) { if (RB32_QUAD8) launch_rb_full32q(a, st); else launch_rb_full32_t<RbFull32S>(a, st); }
+    if (s == CS_32_32_16) launch_rb_full32s(a, st);
+    else if (s == CS_32_32_8) launch_rb_full32q(a, st);
 }
 
 // res1 + res2 of a block forward in one launch.  b / bank: res1.conv1, res1.conv2, res2.conv1, res2.conv2 (forward banks).
@@ -2510,8 +1618,8 @@ void launch_resblock_pair_bf16(ConvShape s, const void* x, const float* const* b
                        (unsigned short*)y2_out, n, {bank[0], bank[1], bank[2], bank[3]}};
     switch (s) {
         case CS_16_16_32: launch_rbp_t<RB_16_32>(a, st); break;
-        case CS_32_32_16: if (RB32_PAIR_ROLES && n >= 1024) launch_rbp32r<RBR_32_16>(a, st); else launch_rbp_t<RB_32_16>(a, st); break;
-        case CS_32_32_8:  if (n <= 1024) launch_rbp_t<RB_32_8S>(a, st); else if (RB32_PAIR_ROLES & 2) launch_rbp32r<RBR_32_8>(a, st); else launch_rbp_t<RB_32_8P>(a, st); break;
+        case CS_32_32_16: if (n >= 1024) launch_rbp32r<RBR_32_16>(a, st); else launch_rbp_t<RB_32_16>(a, st); break;
+        case CS_32_32_8:  if (n <= 1024) launch_rbp_t<RB_32_8S>(a, st); else launch_rbp_t<RB_32_8P>(a, st); break;
         default: break;
     }
 }
