@@ -33,7 +33,7 @@ def _ident(t):
 
 
 def frames_to_bf16_obs(frames_u8):
-    """uint8 NHWC -> NCHW float holding bf16(k/255): the uint8 -> bf16 table of block1.conv's staging (engine.hip lut16:
+    """uint8 NHWC -> NCHW float holding bf16(k/255): the uint8 -> bf16 table of block1.conv's staging (engine.hip mi_create, lut16:
     (float)((double)k / 255.0) rounded to nearest even)."""
     return _r16(O.frames_to_obs(frames_u8))
 
@@ -67,7 +67,7 @@ def impala_forward(p, frames_u8, rounding=True, dtype=torch.float32):
 def impala_backward(p, cache, dfeat_post, feat, rounding=True, dtype=torch.float32, fs_coef=0.0):
     """Backward of the bf16 engine from d loss / d feat (after the fc ReLU).  Rounding points:
       * d feat (pre-ReLU, fp32) is rounded to bf16 only by the matrix-core fc kernels, which run for n >= 1024 (fc_bf16.hip
-        fc_tn_kernel / fc_nt_kernel<true>); smaller batches take the fp32 GEMM with the fp32 fc.weight (engine.hip net_backward);
+        fc_tn_kernel / fc_nt_kernel<true>); smaller batches take the fp32 GEMM with the fp32 fc.weight (engine.hip backward_impala_bf16);
         fc.bias's gradient is the column sum of the unrounded d feat in both cases;
       * every activation gradient written to HBM or handed on through LDS is bf16: d flat, the gradient of a residual conv1's
         output (da), of a block's input (dx), of the pre-pool conv output rebuilt from the pooled gradient (dc; not block1's, see below);

@@ -199,7 +199,7 @@ def test_fused_residual_block_bf16(eng, ch, hw, n):
 @pytest.mark.parametrize("ch,hw", [(16, 32), (32, 16), (32, 8)])
 @pytest.mark.parametrize("n", [1, 3, 6])
 def test_residual_pair_kernel_equals_two_single_launches(eng, ch, hw, n):
-    """net_forward runs res1 + res2 of a block in ONE launch (res1's output reaches res2 through LDS and registers).  Same
+    """forward_impala_bf16 (net_forward) runs res1 + res2 of a block in ONE launch (res1's output reaches res2 through LDS and registers).  Same
     arithmetic as two launches of the single-block kernel, so with the same weights for both blocks: bit-identical."""
     g = torch.Generator().manual_seed(300 + ch + hw)
     w1, w2 = torch.randn(ch, ch, 3, 3, generator=g) * 0.1, torch.randn(ch, ch, 3, 3, generator=g) * 0.1
@@ -240,7 +240,7 @@ def _whole_backward_inputs(ch, hw, n):
 @pytest.mark.parametrize("ch,hw", [(16, 32), (32, 16), (32, 8)])
 @pytest.mark.parametrize("n", [1, 6] + UPDATE_N)
 def test_residual_pair_with_distinct_weights(eng, ch, hw, n):
-    """The pair launch as net_forward runs it in training mode (op_resblock mode 4): four distinct convs and biases, all four outputs
+    """The pair launch as forward_impala_bf16 (net_forward) runs it in training mode (op_resblock mode 4): four distinct convs and biases, all four outputs
     A1, P1, A2, P2 stored.  Per image against torch at the kernel's rounding points (filters, A1, P1 and A2 in bf16).  n <= 6: bit for
     bit two single-block launches (mode 0).  n >= 1024 (pair32r at 32@16; at 32@8 RB_32_8S with 4 images per workgroup at n = 1024,
     the 4-image RB_32_8P above): every image equal, bit for bit, to the same images in launches of <= 12 -- a kernel that fed res2
@@ -550,7 +550,7 @@ def test_fc_bf16_matrix_core_path_matches_small_batch_path(T, B):
 def test_side_stream_minibatch_equals_the_single_stream_pass(deferred):
     """Update-sized bf16 minibatches without batch-level loss terms fork a side stream behind heads_bwd: the feature-sparsity metric,
     the loss records and embedder.fc's weight / bias gradients run beside the rest of the backward pass and are joined in front of the
-    slab sums (engine.hip net_backward).  Same kernels on the same data in the same per-buffer order: loss records, gradients and the
+    slab sums (engine.hip backward_impala_bf16: fork_stats_and_fc, fork_slab_sums).  Same kernels on the same data in the same per-buffer order: loss records, gradients and the
     parameters after three optimizer steps (two of them with accumulated half-minibatches: two forks before one optimizer step) are
     BIT-identical to the single-stream pass (mi_debug_flags bit 4).  deferred: the multi-rank schedule without batch-level loss terms
     (mi_set_multirank mode 2: partial sums into the statistics ring, records derived once per optimize() by mi_loss_log_finalize) --

@@ -1,0 +1,522 @@
+// Op-level and debug entry points of the C ABI (include/mi355ppo.h): single kernels and small launch sequences on caller data, for
+// tests and micro-benchmarks.  The production launch path (engine.hip) never goes through here.
+#include "engine_ctx.h"
+
+static int shape_of(int cin, int cout, int hw, ConvShape* s) {
+    for (int k = 0; k < CS_COUNT; ++k) {
+        int a, b, h; conv_shape_dims((ConvShape)k, &a, &b, &h);
+        if (a == cin && b == cout && h == hw) { *s = (ConvShape)k; return 0; }
+    }
+    return fail(-1, "unsupported conv shape");
+}
+
+// host-side activation conversion for the op-level entry points of a bf16 context (round to nearest even; mi_create builds its uint8 -> bf16 table with it)
+std::vector<uint16_t> host_to_bf16(const float* x, size_t n) {
+    std::vector<uint16_t> o(n);
+    for (size_t k = 0; k < n; ++k) { uint32_t u; memcpy(&u, x + k, 4); o[k] = (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); }
+    return o;
+}
+static void host_from_bf16(const uint16_t* h, float* x, size_t n) {
+    for (size_t k = 0; k < n; ++k) { const uint32_t u = ((uint32_t)h[k]) << 16; memcpy(x + k, &u, 4); }
+}
+// Device memory of one op-level call.  Every buffer is freed on every return path.  Outputs the kernels write are poisoned with
+// 0xFF bytes (NaN in bf16 and fp32), so an element a kernel skips reads back as NaN; the targets the slab reduction adds into keep
+// a zero fill.  A canary band follows each output (and covers the weight-gradient slab rows past a launch's grid); check() compares
+// the bands after the launch and names the tensor a kernel wrote past.  The bands sit after the tensors only: bases keep hipMalloc's
+// alignment.  The production launch path never goes through here.
+struct OpMem {
+    static constexpr size_t GUARD = 64 * 1024;
+    static constexpr int CANARY = 0xA5;
+    struct Band { std::string name; unsigned char* p; size_t bytes; bool rezero; };
+    const char* hook; hipStream_t st;
+    std::vector<void*> owned;
+    std::vector<Band> bands;
+    OpMem(const char* h, hipStream_t s) : hook(h), st(s) {}
+    ~OpMem() { for (void* p : owned) hipFree(p); }
+    OpMem(const OpMem&) = delete;
+    OpMem& operator=(const OpMem&) = delete;
+    template <typename T>
+    hipError_t alloc(T** p, size_t bytes) {          // an input: the +256 bytes cover the kernels' vector over-reads
+        void* q = nullptr;
+        hipError_t e = hipMalloc(&q, bytes + 256);
+        if (e != hipSuccess) return e;
+        owned.push_back(q); *p = (T*)q;
+        return hipMemsetAsync(q, 0, bytes + 256, st);
+    }
+    template <typename T>
+    hipError_t out(T** p, size_t bytes, const char* name, int fill = 0xFF) {
+        void* q = nullptr;
+        hipError_t e = hipMalloc(&q, bytes + GUARD);
+        if (e != hipSuccess) return e;
+        owned.push_back(q); *p = (T*)q;
+        if ((e = hipMemsetAsync(q, fill, bytes, st)) != hipSuccess) return e;
+        return band((unsigned char*)q + bytes, GUARD, name, false);
+    }
+    // the rows [grid, 1024) of a weight-gradient slab region; zero-filled again after the check
+    hipError_t slab_rows(float* slabs, int grid, int row_len, const char* name) {
+        const size_t lo = (size_t)grid * row_len, hi = (size_t)1024 * row_len;
+        return grid < 1024 ? band((unsigned char*)(slabs + lo), (hi - lo) * 4, name, true) : hipSuccess;
+    }
+    hipError_t band(unsigned char* p, size_t bytes, const std::string& name, bool rezero) {
+        bands.push_back(Band{name, p, bytes, rezero});
+        return hipMemsetAsync(p, CANARY, bytes, st);
+    }
+    int check() {           // after the stream synchronisation
+        std::vector<unsigned char> h;
+        std::string bad;
+        for (const Band& b : bands) {
+            h.resize(b.bytes);
+            HIPC(hipMemcpy(h.data(), b.p, b.bytes, hipMemcpyDeviceToHost));
+            static const std::vector<unsigned char> want(1 << 20, (unsigned char)CANARY);
+            for (size_t o = 0; o < b.bytes && bad.empty(); o += want.size()) {
+                const size_t k = std::min(want.size(), b.bytes - o);
+                if (memcmp(h.data() + o, want.data(), k) == 0) continue;
+                size_t i = o;
+                while (h[i] == (unsigned char)CANARY) ++i;
+                bad = std::string(hook) + ": a kernel wrote past the end of " + b.name + " (guard byte " + std::to_string(i) + ")";
+            }
+            if (b.rezero) HIPC(hipMemsetAsync(b.p, 0, b.bytes, st));
+        }
+        bands.clear();
+        HIPC(hipStreamSynchronize(st));
+        return bad.empty() ? 0 : fail(-4, bad);
+    }
+};
+
+// the end of an op-level call: launch errors, the stream wait, the canary bands
+static int op_finish(mi_ctx* c, OpMem& m) {
+    HIPC(hipGetLastError()); NETCHK(c);
+    HIPC(hipStreamSynchronize(c->stream));
+    return m.check();
+}
+// upload an activation tensor in the context's storage type
+static int upload_act(mi_ctx* c, OpMem& m, const float* host, size_t n, void** dev) {
+    HIPC(m.alloc(dev, n * 4));
+    HIPC(hipStreamSynchronize(c->stream));          // (the fill runs on the context's stream, the copy on the null stream)
+    if (c->bf) { auto h = host_to_bf16(host, n); HIPC(hipMemcpy(*dev, h.data(), n * 2, hipMemcpyHostToDevice)); }
+    else HIPC(hipMemcpy(*dev, host, n * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+static int download_act(mi_ctx* c, const void* dev, float* host, size_t n) {
+    if (c->bf) { std::vector<uint16_t> h(n); HIPC(hipMemcpy(h.data(), dev, n * 2, hipMemcpyDeviceToHost)); host_from_bf16(h.data(), host, n); }
+    else HIPC(hipMemcpy(host, dev, n * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+static int upload(OpMem& m, const void* host, size_t bytes, void** dev) {
+    HIPC(m.alloc(dev, bytes));
+    HIPC(hipStreamSynchronize(m.st));
+    HIPC(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int mi_op_conv3x3(mi_ctx* c, int32_t mode, int32_t cin, int32_t cout, int32_t hw, int32_t n, const void* in, int32_t in_is_u8,
+                  int32_t relu_in, const float* w_ref, const float* bias, const float* res, const float* mask, const float* dout,
+                  float* out, float* dbias_out) {
+    ARG(c && w_ref && out && n >= 1, "null"); JOIN(c);
+    ConvShape s;
+    if (shape_of(cin, cout, hw, &s)) return -1;
+    ARG((s == CS_3_16_64) == (in_is_u8 != 0) || mode == 1, "block1.conv takes uint8 frames");
+    const std::string hook = "mi_op_conv3x3 mode " + std::to_string(mode);
+    OpMem m(hook.c_str(), c->stream);
+    const size_t px = (size_t)n * hw * hw, es = c->bf ? 2 : 4;
+    TensorDesc td{"w", 0, 0, (int64_t)cout * cin * 9, K_CONVW, cout, cin};
+    std::vector<float> wdev(td.n);
+    to_device_layout(td, w_ref, wdev.data());
+    float *dw = nullptr, *db = nullptr;
+    void *din = nullptr, *dres = nullptr, *dmask = nullptr, *ddout = nullptr, *dout_buf = nullptr;
+    if (int r = upload(m, wdev.data(), td.n * 4, (void**)&dw)) return r;
+    if (bias) { if (int r = upload(m, bias, cout * 4, (void**)&db)) return r; }
+    const int out_ch = (mode == 1) ? cin : cout;
+    if (mode != 1) {
+        if (in_is_u8) { if (int r = upload(m, in, px * 3, &din)) return r; }
+        else if (int r = upload_act(c, m, (const float*)in, px * cin, &din)) return r;
+    }
+    // the weight gradient: slabs [grid][td.n + cout] summed into g (the reduction adds: zero fill)
+    auto wgrad_out = [&](float** g, int grid) -> int {
+        HIPC(m.out(g, (td.n + cout) * 4, "the weight / bias gradient", 0));
+        HIPC(m.slab_rows(c->slabs, grid, (int)td.n + cout, "the weight-gradient slab rows past the grid"));
+        return 0;
+    };
+    auto read_wgrad = [&](const float* g) -> int {
+        std::vector<float> hg(td.n + cout);
+        HIPC(hipMemcpy(hg.data(), g, hg.size() * 4, hipMemcpyDeviceToHost));
+        to_ref_layout(td, hg.data(), out);
+        if (dbias_out) memcpy(dbias_out, hg.data() + td.n, cout * 4);
+        return 0;
+    };
+    if (mode >= 3) {        // a block's first conv fused with the block's max pool (bf16): 3 = forward -> pooled map,
+                            // 4 = weight gradient, 5 = data gradient -- both from the POOLED gradient + the forward's arg-max bytes
+        ARG(c->bf && (s == CS_3_16_64 || s == CS_16_32_32 || s == CS_32_32_16), "fused conv+pool modes: block1/2/3.conv in bf16 precision only");
+        ARG(mode <= 7 && !(mode >= 5 && s == CS_3_16_64) && in, "mode");
+        ARG(mode == 3 || mode == 5 || c->slabs, "modes 4 / 6: weight gradients need an IMPALA context");
+        ARG(mode < 6 || conv_bwd_fused_grid(s, n) > 0, "modes 6 / 7: block2.conv / block3.conv");
+        ARG(mode == 3 || dout, "dout");
+        const size_t pp = (size_t)n * (hw / 2) * (hw / 2) * cout;
+        void *dp = nullptr, *dgi = nullptr; uint8_t* di = nullptr; unsigned short* dbank = nullptr; BankDesc* ddesc = nullptr;
+        HIPC(m.out(&dp, pp * 2, "the pooled map")); HIPC(m.out(&di, pp, "the arg-max bytes", 0));
+        ConvArgs a{};
+        a.in = din; a.w = dw; a.bias = db; a.n = n; a.bf16 = 1; a.lut16 = c->lut16;
+        if (s == CS_3_16_64) launch_conv1_pool_fwd_bf16(a, c->lut16, dp, di, c->stream);
+        else {
+            const long long bf_len = (long long)cout * bank_ws(cin), bd_len = (long long)cin * bank_ws(cout);
+            BankDesc d[2] = {{0, 0, cout, cin, cout, cin, 0, bank_ws(cin), cin == 32 ? 9 : 5}, {0, bf_len, cin, cout, cout, cin, 1, bank_ws(cout), cout == 32 ? 9 : 5}};
+            HIPC(m.alloc(&dbank, (size_t)(bf_len + bd_len) * 2));
+            if (int r = upload(m, d, sizeof d, (void**)&ddesc)) return r;
+            launch_pack_banks(dw, dbank, ddesc, 2, c->stream);
+            a.wbank = dbank;
+            ARG(launch_conv_pool_fwd_bf16(s, a, dp, di, c->stream), "no fused kernel");
+        }
+        HIPC(hipGetLastError()); NETCHK(c);
+        HIPC(hipStreamSynchronize(c->stream));
+        if (mode == 3) {
+            if (int r = m.check()) return r;
+            return download_act(c, dp, out, pp);
+        }
+        if (int r = upload_act(c, m, dout, pp, &ddout)) return r;
+        if (mode == 4) {
+            float* g = nullptr;
+            const int grid = wgrad_grid_for(s, n, 1);
+            if (int r = wgrad_out(&g, grid)) return r;
+            WgradArgs wa{};
+            wa.in = din; wa.dout = ddout; wa.partial = c->slabs; wa.n = n; wa.bf16 = 1; wa.lut16 = c->lut16; wa.pool_arg = di;
+            launch_conv_wgrad(s, wa, c->stream);
+            launch_reduce_slabs(c->slabs, grid, (int)td.n + cout, g, (int)td.n, g + td.n, cout, c->stream);
+            if (int r = op_finish(c, m)) return r;
+            return read_wgrad(g);
+        }
+        // 5: data gradient; 6 / 7: the fused data + weight gradient launch (block2.conv, block3.conv), returning dW (+ db) / dx
+        HIPC(m.out(&dgi, px * cin * 2, "the data gradient"));
+        ConvArgs g{};
+        g.in = ddout; g.pool_arg = di; g.w = dw; g.out = dgi; g.n = n; g.bf16 = 1; g.wbank = dbank + (long long)cout * bank_ws(cin);
+        float* gw = nullptr;
+        const int fgrid = mode >= 6 ? conv_bwd_fused_grid(s, n) : 0;
+        if (mode >= 6) { g.wg_in = din; g.wg_partial = c->slabs; if (int r = wgrad_out(&gw, fgrid)) return r; }
+        launch_conv_dgrad(s, g, c->stream);
+        if (mode >= 6) launch_reduce_slabs(c->slabs, fgrid, (int)td.n + cout, gw, (int)td.n, gw + td.n, cout, c->stream);
+        if (int r = op_finish(c, m)) return r;
+        return mode == 6 ? read_wgrad(gw) : download_act(c, dgi, out, px * cin);
+    }
+    if (mode >= 1) { ARG(dout, "dout"); if (int r = upload_act(c, m, dout, px * cout, &ddout)) return r; }
+    if (res) { if (int r = upload_act(c, m, res, px * out_ch, &dres)) return r; }
+    if (mask) { if (int r = upload_act(c, m, mask, px * out_ch, &dmask)) return r; }
+    if (mode <= 1) {
+        HIPC(m.out(&dout_buf, px * out_ch * es, mode == 0 ? "the conv output" : "the data gradient"));
+        ConvArgs a{};
+        a.in = (mode == 0) ? din : ddout; a.idx = nullptr; a.in_base = 0; a.w = dw; a.bias = (mode == 0) ? db : nullptr;
+        a.res = dres; a.mask = dmask; a.out = dout_buf; a.lut = c->lut; a.n = n; a.relu_in = (mode == 0) ? relu_in : 0; a.bf16 = c->bf;
+        a.lut16 = c->bf ? c->lut16 : nullptr;
+        if (mode == 0) launch_conv_fwd(s, a, c->stream); else launch_conv_dgrad(s, a, c->stream);
+        if (int r = op_finish(c, m)) return r;
+        return download_act(c, dout_buf, out, px * out_ch);
+    }
+    ARG(c->slabs, "wgrad needs an IMPALA context");
+    float* g = nullptr;
+    const int grid = wgrad_grid_for(s, n, c->bf);
+    if (int r = wgrad_out(&g, grid)) return r;
+    WgradArgs a{};
+    a.in = din; a.idx = nullptr; a.in_base = 0; a.dout = ddout; a.partial = c->slabs; a.lut = c->lut; a.n = n; a.relu_in = relu_in; a.bf16 = c->bf;
+    a.lut16 = c->bf ? c->lut16 : nullptr;
+    launch_conv_wgrad(s, a, c->stream);
+    launch_reduce_slabs(c->slabs, grid, (int)td.n + cout, g, (int)td.n, g + td.n, cout, c->stream);
+    if (int r = op_finish(c, m)) return r;
+    return read_wgrad(g);
+}
+
+// Fused residual block of the bf16 mode, op level.  mode 0: (x, w1, b1, w2, b2) -> a = conv1(relu(x)) + b1, y = conv2(relu(a)) + b2 + x.
+// mode 1: (dy = x, a_fwd, x_fwd, w1, w2) -> out_a = d a = convT2(dy) * (a_fwd > 0), out_y = d x = convT1(d a) * (x_fwd > 0) + dy.
+// mode 4: res1 + res2 in one launch as net_forward runs them in training mode: w1 / b1 = res1's (conv1; conv2), w2 / b2 = res2's,
+// out_a = (A1; A2), out_y = (P1; P2).
+int mi_op_resblock(mi_ctx* c, int32_t mode, int32_t ch, int32_t hw, int32_t n, const float* x, const float* w1_ref, const float* b1,
+                   const float* w2_ref, const float* b2, const float* a_fwd, const float* x_fwd, float* out_a, float* out_y) {
+    ARG(c && x && w1_ref && w2_ref && out_a && out_y && n >= 1, "null"); JOIN(c);
+    ARG(c->bf, "the fused residual-block kernels exist in bf16 precision only");
+    ARG(mode >= 0 && mode <= 4, "mode");
+    ARG((mode == 0 || mode >= 3) ? (b1 && b2) : (a_fwd && x_fwd), "modes 0 / 3 / 4 need the biases, modes 1 / 2 the forward tensors");
+    ConvShape s;
+    if (shape_of(ch, ch, hw, &s)) return -1;
+    const std::string hook = "mi_op_resblock mode " + std::to_string(mode);
+    OpMem m(hook.c_str(), c->stream);
+    const size_t X = (size_t)n * hw * hw * ch, wl = (size_t)ch * ch * 9;
+    const int nc = mode == 4 ? 4 : 2;           // convs: (w1, w2), or mode 4's (res1.conv1, res1.conv2, res2.conv1, res2.conv2)
+    const float* wsrc[4] = {w1_ref, w2_ref, nullptr, nullptr};
+    const float* bsrc[4] = {b1, b2, nullptr, nullptr};
+    if (mode == 4) { wsrc[1] = w1_ref + wl; wsrc[2] = w2_ref; wsrc[3] = w2_ref + wl; bsrc[1] = b1 + ch; bsrc[2] = b2; bsrc[3] = b2 + ch; }
+    TensorDesc td{"w", 0, 0, (int64_t)wl, K_CONVW, ch, ch};
+    std::vector<float> wdev((size_t)nc * (wl + ch), 0.f);
+    for (int k = 0; k < nc; ++k) {
+        to_device_layout(td, wsrc[k], wdev.data() + k * wl);
+        if (bsrc[k]) memcpy(wdev.data() + nc * wl + k * ch, bsrc[k], ch * 4);
+    }
+    float* dparams = nullptr; unsigned short* dbanks = nullptr; BankDesc* ddesc = nullptr;
+    void *dx = nullptr, *da = nullptr, *dxf = nullptr;
+    if (int r = upload(m, wdev.data(), wdev.size() * 4, (void**)&dparams)) return r;
+    const float* bias = dparams + nc * wl;
+    const int ws = bank_ws(ch), nk = ch == 32 ? 9 : 5;
+    const long long bl = (long long)ch * ws;
+    // bank k feeds the kernel's k-th conv: forward the convs as stored; backward (w2^T, w1^T)
+    const bool tr = (mode == 1 || mode == 2);
+    BankDesc d[4];
+    for (int k = 0; k < nc; ++k) d[k] = BankDesc{tr ? (k == 0 ? (long long)wl : 0) : (long long)(k * wl), k * bl, ch, ch, ch, ch, tr ? 1 : 0, ws, nk};
+    HIPC(m.alloc(&dbanks, (size_t)nc * bl * 2));
+    if (int r = upload(m, d, sizeof(BankDesc) * nc, (void**)&ddesc)) return r;
+    launch_pack_banks(dparams, dbanks, ddesc, nc, c->stream);
+    if (int r = upload_act(c, m, x, X, &dx)) return r;
+    if (mode == 2) {        // whole backward of a 16-channel block: out_y = dx, out_a[0 .. 2*(9*ch*ch + ch)) = {dW1, db1, dW2, db2} (reference layout)
+        ARG((s == CS_16_16_32 || s == CS_32_32_16 || s == CS_32_32_8) && c->slabs, "the whole-backward kernels exist for the 16-channel @32x32 and 32-channel @16x16 blocks (IMPALA context)");
+        if (int r = upload_act(c, m, a_fwd, X, &da)) return r;
+        if (int r = upload_act(c, m, x_fwd, X, &dxf)) return r;
+        const int grid = s == CS_16_16_32 ? resblock_bwd_full_grid(n) : resblock_bwd_full32_grid(s, n), slab = (int)wl + ch;
+        void* doy = nullptr; float* g = nullptr;
+        HIPC(m.out(&doy, X * 2, "the data gradient"));
+        HIPC(m.out(&g, (size_t)2 * slab * 4, "the weight / bias gradients", 0));
+        float* sl2 = c->slabs; float* sl1 = c->slabs + (size_t)1024 * slab;
+        HIPC(m.slab_rows(sl2, grid, slab, "conv2's weight-gradient slab rows past the grid"));
+        HIPC(m.slab_rows(sl1, grid, slab, "conv1's weight-gradient slab rows past the grid"));
+        if (s == CS_16_16_32) launch_resblock_bwd_full_bf16(dx, da, dxf, doy, nullptr, n, dbanks, dbanks + bl, sl2, sl1, c->stream);
+        else launch_resblock_bwd_full32_bf16(s, dx, da, dxf, doy, nullptr, n, dbanks, dbanks + bl, sl2, sl1, c->stream);
+        launch_reduce_slabs(sl1, grid, slab, g, (int)wl, g + wl, ch, c->stream);
+        launch_reduce_slabs(sl2, grid, slab, g + slab, (int)wl, g + slab + wl, ch, c->stream);
+        if (int r = op_finish(c, m)) return r;
+        std::vector<float> hg(2 * slab);
+        HIPC(hipMemcpy(hg.data(), g, hg.size() * 4, hipMemcpyDeviceToHost));
+        to_ref_layout(td, hg.data(), out_a); memcpy(out_a + wl, hg.data() + wl, ch * 4);
+        to_ref_layout(td, hg.data() + slab, out_a + slab); memcpy(out_a + slab + wl, hg.data() + slab + wl, ch * 4);
+        return download_act(c, doy, out_y, X);
+    }
+    void* o[4] = {};        // mode 4: A1, P1, A2, P2; otherwise out_a, out_y
+    static const char* oname[4] = {"A1 (res1.conv1 output)", "P1 (res1 output)", "A2 (res2.conv1 output)", "P2 (block output)"};
+    for (int k = 0; k < (mode == 4 ? 4 : 2); ++k) HIPC(m.out(&o[k], X * 2, mode == 4 ? oname[k] : (k ? "out_y" : "out_a")));
+    if (mode == 4) {
+        const float* bb[4] = {bias, bias + ch, bias + 2 * ch, bias + 3 * ch};
+        const unsigned short* bk[4] = {dbanks, dbanks + bl, dbanks + 2 * bl, dbanks + 3 * bl};
+        launch_resblock_pair_bf16(s, dx, bb, o[0], o[1], o[2], o[3], n, bk, c->stream);
+    } else if (mode == 3) {        // res1 + res2 in one launch, both with (w1, b1, w2, b2): out_a = second conv1 output, out_y = second block output
+        const float* bb[4] = {bias, bias + ch, bias, bias + ch};
+        const unsigned short* bk[4] = {dbanks, dbanks + bl, dbanks, dbanks + bl};
+        launch_resblock_pair_bf16(s, dx, bb, nullptr, nullptr, o[0], o[1], n, bk, c->stream);
+    } else if (mode == 0) {
+        launch_resblock_bf16(s, dx, bias, bias + ch, o[0], o[1], n, dbanks, dbanks + bl, c->stream);
+    } else {
+        if (int r = upload_act(c, m, a_fwd, X, &da)) return r;
+        if (int r = upload_act(c, m, x_fwd, X, &dxf)) return r;
+        launch_resblock_bwd_bf16(s, dx, da, dxf, o[0], o[1], n, dbanks, dbanks + bl, c->stream);
+    }
+    if (int r = op_finish(c, m)) return r;
+    if (mode == 4) {
+        for (int k = 0; k < 4; ++k)
+            if (int r = download_act(c, o[k], (k & 1 ? out_y : out_a) + (k >> 1) * X, X)) return r;
+        return 0;
+    }
+    if (int r = download_act(c, o[0], out_a, X)) return r;
+    return download_act(c, o[1], out_y, X);
+}
+
+// Philox4x32-10 known-answer hook: n x {c0,c1,c2,c3,k0,k1} in, n x 4 output words and the n uniforms the sampler would draw
+// for (seed = k0 | k1 << 32, counter = c0 | c1 << 32) out.
+int mi_debug_philox(mi_ctx* c, const uint32_t* ctr_key6, int32_t n, uint32_t* out4, float* u_out) {
+    ARG(c && ctr_key6 && out4 && u_out, "null"); JOIN(c); ARG(n >= 1 && n <= (1 << 24), "n");
+    uint32_t *din = nullptr, *dout = nullptr; float* du = nullptr;
+    HIPC(hipMalloc((void**)&din, (size_t)n * 24)); HIPC(hipMalloc((void**)&dout, (size_t)n * 16)); HIPC(hipMalloc((void**)&du, (size_t)n * 4));
+    HIPC(hipMemcpy(din, ctr_key6, (size_t)n * 24, hipMemcpyHostToDevice));
+    launch_philox_debug(din, n, dout, du, c->stream);
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(c->stream));
+    HIPC(hipMemcpy(out4, dout, (size_t)n * 16, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(u_out, du, (size_t)n * 4, hipMemcpyDeviceToHost));
+    hipFree(din); hipFree(dout); hipFree(du);
+    return 0;
+}
+
+// The fused GRU step of the pipelined rollout (misc.hip gru_step_kernel) on caller data, for tests: n rows, width H (any multiple of 64 up
+// to 512, independent of the context's), weights in nn.GRU's layout.  h_out = h' (and h_copy = the kernel's second copy of it, if not null).
+int mi_debug_gru_step(mi_ctx* c, int32_t n, int32_t H, const float* x, const float* h, const float* done, const float* w_ih, const float* w_hh,
+                      const float* b_ih, const float* b_hh, float* h_out, float* h_copy) {
+    ARG(c && x && h && done && w_ih && w_hh && b_ih && b_hh && h_out, "null"); JOIN(c);
+    ARG(n >= 1 && n <= 65536 && H >= 64 && H <= 512 && H % 64 == 0, "n in [1, 65536], H a multiple of 64 in [64, 512]");
+    const size_t nh = (size_t)n * H, w = (size_t)3 * H * H;
+    std::vector<float*> d(9, nullptr);
+    const size_t sz[9] = {nh, nh, (size_t)n, w, w, (size_t)3 * H, (size_t)3 * H, nh, nh};
+    const float* src[7] = {x, h, done, w_ih, w_hh, b_ih, b_hh};
+    int rc = 0;
+    for (int i = 0; i < 9 && !rc; ++i) if (hipMalloc((void**)&d[i], sz[i] * 4) != hipSuccess) rc = fail(-2, "hipMalloc failed");
+    for (int i = 0; i < 7 && !rc; ++i) if (hipMemcpy(d[i], src[i], sz[i] * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(-2, "upload failed");
+    if (!rc) {
+        launch_gru_step(d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], n, H, c->stream);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(-4, "gru_step_kernel failed");
+    }
+    if (!rc && hipMemcpy(h_out, d[7], nh * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(-2, "download failed");
+    if (!rc && h_copy && hipMemcpy(h_copy, d[8], nh * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(-2, "download failed");
+    for (float* p : d) if (p) hipFree(p);
+    return rc;
+}
+
+// The GRU over a trajectory (gru_seq.hip) on caller data, for tests: n envs x T steps, rows time-major, width H (independent of the context's).
+// Forward: out_h = h_t of all rows.  With dOut (dL/dh_t of all rows) also the backward pass through time and the GEMMs behind it, exactly as
+// mi_minibatch_rec issues them: dX, dW_ih, dW_hh, db_ih, db_hh (from zero).
+int mi_debug_gru_seq(mi_ctx* c, int32_t T, int32_t n, int32_t H, const float* x, const float* h0, const float* mask, const float* w_ih, const float* w_hh,
+                     const float* b_ih, const float* b_hh, const float* dOut, float* out_h, float* dX, float* dW_ih, float* dW_hh, float* db_ih, float* db_hh) {
+    ARG(c && x && h0 && mask && w_ih && w_hh && b_ih && b_hh && out_h, "null"); JOIN(c);
+    ARG(!dOut || (dX && dW_ih && dW_hh && db_ih && db_hh), "null gradient outputs");
+    ARG(gru_seq_width_ok(H), "H must be a multiple of 64 in [64, 512]");
+    ARG(T >= 1 && n >= 1 && (int64_t)T * n <= 65536, "T, n >= 1 and T * n <= 65536");
+    const size_t N = (size_t)T * n, NH = N * H, W = (size_t)3 * H * H, B = (size_t)3 * H;
+    enum { X = 0, H0, MK, WIH, WHH, BIH, BHH, DOUT, GI, OUT, SV, DGI, DGH, HM, DX, GWIH, GWHH, GBIH, GBHH, NBUF };
+    const size_t sz[NBUF] = {NH, (size_t)n * H, N, W, W, B, B, NH, 3 * NH, NH, 4 * NH, 3 * NH, 3 * NH, NH, NH, W, W, B, B};
+    const float* src[8] = {x, h0, mask, w_ih, w_hh, b_ih, b_hh, dOut};
+    std::vector<float*> d(NBUF, nullptr);
+    int rc = 0;
+    for (int i = 0; i < NBUF && !rc; ++i) if (hipMalloc((void**)&d[i], sz[i] * 4) != hipSuccess) rc = fail(-2, "hipMalloc failed");
+    for (int i = 0; i < 8 && !rc; ++i) if (src[i] && hipMemcpy(d[i], src[i], sz[i] * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(-2, "upload failed");
+    for (int i = GWIH; i < NBUF && !rc; ++i) if (hipMemset(d[i], 0, sz[i] * 4) != hipSuccess) rc = fail(-2, "hipMemset failed");
+    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(-2, "sync failed");
+    if (!rc) {
+        linear_fwd(c, d[X], 0, d[WIH], d[BIH], d[GI], (int)N, H, 3 * H, 0);
+        launch_gru_seq_fwd(d[GI], d[H0], d[MK], d[WHH], d[BHH], d[OUT], d[SV], T, n, H, c->stream);
+        if (dOut) {
+            launch_gru_seq_bwd(d[DOUT], d[OUT], d[H0], d[MK], d[SV], d[WHH], d[DGI], d[DGH], d[HM], T, n, H, c->stream);
+            linear_wgrad(c, d[DGI], d[X], 0, d[GWIH], d[GBIH], (int)N, H, 3 * H);
+            linear_wgrad(c, d[DGH], d[HM], 0, d[GWHH], d[GBHH], (int)N, H, 3 * H);
+            linear_dgrad(c, d[DGI], d[WIH], nullptr, d[DX], (int)N, H, 3 * H);
+        }
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(-4, "GRU sequence kernels failed");
+        if (!rc) if (const char* lf = mi_launch_failed_take()) rc = fail(-4, lf);
+    }
+    auto down = [&](float* dst, int k) { if (!rc && hipMemcpy(dst, d[k], sz[k] * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(-2, "download failed"); };
+    down(out_h, OUT);
+    if (dOut) { down(dX, DX); down(dW_ih, GWIH); down(dW_hh, GWHH); down(db_ih, GBIH); down(db_hh, GBHH); }
+    for (float* p : d) if (p) hipFree(p);
+    return rc;
+}
+
+// Measurement hook ("hipGraph"): wall-clock microseconds per policy step of slot t -- the step's launches (conv stack,
+// embedder.fc, fused heads + sample: 5 kernels in bf16 mode) followed by a stream wait, `iters` times back to back -- issued eagerly
+// (mode 0) or as ONE replay of a graph captured from the same launches (mode 1).  What a captured group step could save on the
+// rollout's dependency chain, without touching the production path (whose per-step arguments change: slot, counters, ticket).
+int mi_debug_step_latency(mi_ctx* c, int32_t t, int32_t iters, int32_t mode, float* us_out) {
+    ARG(c && us_out, "null"); JOIN(c); ARG(t >= 0 && t <= c->T && iters >= 1 && (mode == 0 || mode == 1), "t / iters / mode");
+    const int E = c->E;
+    InputSrc src{obs_ring(c), nullptr, (long long)t * E};
+    auto issue = [&]() {
+        c->prof.phase = 0;
+        net_forward(c, src, E, {.recurrent = true, .heads = false});
+        launch_heads_sample(c->feat, c->params + c->wh_off, c->params + c->bh_off, E, c->H, c->A, nullptr, 1234ull, (unsigned long long)t * E,
+                            nullptr, nullptr, c->value + (size_t)t * E, c->h_pack, nullptr, nullptr, nullptr, nullptr, c->stream, nullptr, nullptr, 0, c->lse);
+    };
+    const bool prof_on = c->prof.on; c->prof.on = false;       // (no event records inside a capture)
+    issue();                                                   // warm: packed banks in place, lazy function attributes set
+    HIPC(hipGetLastError()); NETCHK(c);
+    HIPC(hipStreamSynchronize(c->stream));
+    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
+    if (mode == 1) {
+        HIPC(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+        issue();
+        HIPC(hipStreamEndCapture(c->stream, &graph));
+        HIPC(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        HIPC(hipGraphLaunch(exec, c->stream)); HIPC(hipStreamSynchronize(c->stream));
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int k = 0; k < iters; ++k) {
+        if (mode == 1) HIPC(hipGraphLaunch(exec, c->stream)); else issue();
+        HIPC(hipStreamSynchronize(c->stream));
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    *us_out = (float)(std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count() / 1e3 / iters);
+    if (exec) hipGraphExecDestroy(exec);
+    if (graph) hipGraphDestroy(graph);
+    c->prof.on = prof_on;
+    HIPC(hipGetLastError()); NETCHK(c);
+    return 0;
+}
+
+// Read back what the last training-mode pass (mi_minibatch) left in the activation buffers, as fp32 NHWC: which = 8 * block + k with
+// k = 0 P0 (pooled map), 1 A1, 2 P1, 3 A2, 4 P2 (res1.conv1 out, res1 out, res2.conv1 out, block out), 5 the max-pool arg-max bytes
+// (window position ky*3+kx as float); which = 100: the 256 features.  For teacher-forced backward parity tests.
+int mi_debug_read(mi_ctx* c, int32_t which, int32_t n, float* out) {
+    ARG(c && out, "null"); JOIN(c); ARG(n >= 1 && n <= c->NB, "n must be in [1, max_batch]");
+    if (which == 100 || which == 101 || which == 102) {
+        // after a recurrent pass (mi_minibatch_rec) the features -- the embedder output x -- sit in their own buffer: feat holds h_t (101), dfeat dX (102)
+        ARG(which == 100 || c->rec_last, "which = 101 / 102: only after mi_minibatch_rec");
+        const float* srcp = which == 102 ? c->dfeat : (which == 100 && c->rec_last) ? c->rec_x : c->feat;
+        HIPC(hipMemcpyAsync(out, srcp, (size_t)n * c->H * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        return 0;
+    }
+    ARG(c->cfg.arch == MI_ARCH_IMPALA && which >= 0 && which < 24 && (which & 7) <= 5, "which");
+    const Block& k = c->blk[which >> 3];
+    const size_t pe = (size_t)n * (k.hin / 2) * (k.hin / 2) * k.cout;
+    HIPC(hipStreamSynchronize(c->stream));
+    if ((which & 7) == 5) {
+        std::vector<uint8_t> h(pe);
+        HIPC(hipMemcpy(h.data(), k.PI, pe, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < pe; ++i) out[i] = (float)h[i];
+        return 0;
+    }
+    const float* src[5] = {k.P0, k.A1, k.P1, k.A2, k.P2};
+    return download_act(c, src[which & 7], out, pe);
+}
+
+int mi_op_maxpool(mi_ctx* c, int32_t mode, int32_t n, int32_t hw, int32_t ch, const float* in, const float* dout, float* out) {
+    ARG(c && in && out, "null"); JOIN(c); ARG(n >= 1, "n");
+    ARG((hw == 64 && ch == 16) || (hw == 32 && ch == 32) || (hw == 16 && ch == 32), "max pool shapes of the IMPALA blocks only: (64,16), (32,32), (16,32)");
+    ARG(mode == 0 || dout, "dout");
+    OpMem m(mode == 0 ? "mi_op_maxpool mode 0" : "mi_op_maxpool mode 1", c->stream);
+    const size_t X = (size_t)n * hw * hw * ch, p = X / 4, es = c->bf ? 2 : 4;
+    void *din = nullptr, *dp = nullptr, *dd = nullptr, *dg = nullptr; uint8_t* di = nullptr;
+    if (int r = upload_act(c, m, in, X, &din)) return r;
+    HIPC(m.out(&dp, p * es, "the pooled map")); HIPC(m.out(&di, p, "the arg-max bytes", 0));
+    if (c->bf) launch_maxpool_fwd_bf16(din, dp, di, n, hw, ch, c->stream); else launch_maxpool_fwd((const float*)din, (float*)dp, di, n, hw, ch, c->stream);
+    if (mode != 0) {
+        if (int r = upload_act(c, m, dout, p, &dd)) return r;
+        HIPC(m.out(&dg, X * es, "the data gradient"));
+        if (c->bf) launch_maxpool_bwd_bf16(dd, di, dg, n, hw, ch, c->stream); else launch_maxpool_bwd((const float*)dd, di, (float*)dg, n, hw, ch, c->stream);
+    }
+    if (int r = op_finish(c, m)) return r;
+    return mode == 0 ? download_act(c, dp, out, p) : download_act(c, dg, out, X);
+}
+
+int mi_op_gemm(mi_ctx* c, int32_t M, int32_t N, int32_t K, const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk,
+               int64_t sbn, float* C) {
+    ARG(c && A && B && C, "null"); JOIN(c);
+    const size_t na = (size_t)((M - 1) * sam + (K - 1) * sak + 1), nb = (size_t)((K - 1) * sbk + (N - 1) * sbn + 1);
+    float *da = nullptr, *db = nullptr, *dc = nullptr;
+    HIPC(dalloc(&da, na)); HIPC(dalloc(&db, nb)); HIPC(dalloc(&dc, (size_t)M * N));
+    HIPC(hipMemcpy(da, A, na * 4, hipMemcpyHostToDevice)); HIPC(hipMemcpy(db, B, nb * 4, hipMemcpyHostToDevice));
+    GemmArgs g{};
+    g.ws = c->gemm_ws; g.ws_floats = c->gemm_ws_floats;
+    g.A = da; g.B = db; g.C = dc; g.M = M; g.N = N; g.K = K; g.sam = sam; g.sak = sak; g.sbk = sbk; g.sbn = sbn; g.ldc = N;
+    launch_gemm(g, c->stream);
+    HIPC(hipGetLastError()); NETCHK(c);
+    HIPC(hipStreamSynchronize(c->stream));
+    HIPC(hipMemcpy(C, dc, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+    hipFree(da); hipFree(db); hipFree(dc);
+    return 0;
+}
+
+// D = A(16x4) * B(4x16) with asymmetric integer data through the operand maps the kernels assume:
+// A[i = lane&15][k = lane>>4], B[k = lane>>4][j = lane&15], D[row = (lane>>4)*4 + r][col = lane&15]
+__global__ void mfma_selftest_kernel(float* d) {
+    const int lane = threadIdx.x, i = lane & 15, q = lane >> 4;
+    const float a = (float)(i * 7 + q * 3 + 1), b = (float)(q * 5 - i * 2 + 11);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
+    for (int r = 0; r < 4; ++r) d[(q * 4 + r) * 16 + i] = acc[r];
+}
+int mi_selftest_mfma(mi_ctx* c, float* max_err) {
+    ARG(c && max_err, "null"); JOIN(c);
+    float* d = nullptr;
+    HIPC(dalloc(&d, 256));
+    hipLaunchKernelGGL(mfma_selftest_kernel, dim3(1), dim3(64), 0, c->stream, d);
+    HIPC(hipStreamSynchronize(c->stream));
+    float h[256];
+    HIPC(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
+    hipFree(d);
+    float worst = 0.f;
+    for (int m = 0; m < 16; ++m)
+        for (int n = 0; n < 16; ++n) {
+            float ref = 0.f;
+            for (int k = 0; k < 4; ++k) ref += (float)(m * 7 + k * 3 + 1) * (float)(k * 5 - n * 2 + 11);
+            worst = fmaxf(worst, fabsf(ref - h[m * 16 + n]));
+        }
+    *max_err = worst;
+    return 0;
+}
