@@ -216,6 +216,59 @@ int mi_get_gru_grads(mi_ctx* ctx, float* w_ih, float* w_hh, float* b_ih, float* 
 int mi_get_gru_adam_state(mi_ctx* ctx, float* exp_avg, float* exp_avg_sq, int64_t n);
 int mi_set_gru_adam_state(mi_ctx* ctx, const float* exp_avg, const float* exp_avg_sq, int64_t n);
 
+/* ---- the sparse-autoencoder agent (algo: sae; reference agents/sae.py, models common/model.py:1623-1667) on an existing IMPALA context:
+ *      stage 1 trains a sparse autoencoder on the 2048 block-3 features (ImpalaModel.forward_to_pool, common/model.py:186-196) of the
+ *      FROZEN policy, stage 2 a linear probe (fc_policy, fc_value) that acts from its codes.  Non-recurrent, single GPU, serial rollout
+ *      steps: a context with a GRU set, more than one rank or env groups is refused.  The policy's forward pass runs in the context's
+ *      precision; all SAE / probe arithmetic is fp32.  Nothing here changes a number of the PPO entry points.
+ *      mi_sae_create(sae_dim, rho) (SAE.__init__, agents/sae.py:60-65; sae_dim a multiple of 64 in [64, 4096]) allocates, only now: the
+ *      SAE {encoder.0.weight [S][2048], .bias [S], decoder.0.weight [2048][S], .bias [2048]} and the probe {fc_policy.weight [A][S], .bias [A],
+ *      fc_value.weight [1][S], .bias [1]} with gradients and Adam moments, a feature ring [T+1][E][2048] (539 MB at T = E = 256) and a logit
+ *      ring [T][E][A]; the value / action / reward / done rings are the context's own (mi_read_field, mi_put_step, mi_put_policy_outputs).
+ *      `which` selects the model: 0 = SAE, 1 = probe.  Flat vectors are in model.parameters() order and the reference's layouts: the
+ *      encoder's 2048 input columns and the decoder's 2048 rows are channel-major ch*64 + p (Flatten() on NCHW); the library permutes to
+ *      its pixel-major feature order as it does for embedder.fc.weight.  mi_sae_get_hidden / mi_sae_put_ring use the same order. */
+int mi_sae_create(mi_ctx* ctx, int32_t sae_dim, float rho);
+/* releases what mi_sae_create allocated; call it BEFORE mi_destroy (the state is kept beside the context, which does not know of it).
+ * A context destroyed without it leaks those buffers until a later context is created at the same address: every mi_sae_* call checks
+ * that the state it finds was created for THIS context (its parameter buffer and T, E, A) and releases a stale one instead of using it. */
+int mi_sae_destroy(mi_ctx* ctx);
+int64_t mi_sae_param_count(mi_ctx* ctx, int32_t which);
+int mi_sae_set_params(mi_ctx* ctx, int32_t which, const float* flat, int64_t n);
+int mi_sae_get_params(mi_ctx* ctx, int32_t which, float* flat, int64_t n);
+int mi_sae_get_grads(mi_ctx* ctx, int32_t which, float* flat, int64_t n);                  /* accumulated, un-clipped */
+int mi_sae_set_adam_state(mi_ctx* ctx, int32_t which, const float* exp_avg, const float* exp_avg_sq, int64_t n);
+int mi_sae_get_adam_state(mi_ctx* ctx, int32_t which, float* exp_avg, float* exp_avg_sq, int64_t n);
+/* SAEStorage.store / store_last of caller data (common/storage.py:533-548): hidden (E x 2048; t in [0, T]) and the policy's logits
+ * (E x A; t < T) into ring step t.  Either pointer may be NULL.  mi_sae_get_hidden / mi_sae_get_logits read a ring step back;
+ * t == -1: the hidden / logits of the last mi_sae_step that did not store (for the bootstrap step T the logits are read the same way). */
+int mi_sae_put_ring(mi_ctx* ctx, int32_t t, const float* hidden, const float* logits);
+int mi_sae_get_hidden(mi_ctx* ctx, int32_t t, float* out /* E x 2048 */);
+int mi_sae_get_logits(mi_ctx* ctx, int32_t t, float* out /* E x A */);
+/* SAE.get_hidden_and_acts (agents/sae.py:73-86) on E frames: one forward of the frozen policy; hidden = ReLU(block-3 output), the
+ * normalised log-probabilities p.logits and the value; one action per env from Philox4x32-10 keyed by (seed, counter + e), the counter
+ * being the context's own (0 at mi_sae_create, + E per call) -- from the policy's distribution (act_from_probe == 0) or from
+ * Categorical(logits = probe(encode(hidden))) (agents/sae.py:81-84).  u: optional E uniforms instead of the generator.  store != 0:
+ * hidden, the POLICY's logits (never the probe's), value and action go into ring step t (SAEStorage.store); t == T stores hidden and
+ * value only (store_last); the frames go into the context's observation ring (mi_get_obs).  store == 0 changes no ring (validation rollouts: the reference reads storage_valid through fetch_log_data
+ * only).  act_out / value_out (E each) may be NULL. */
+int mi_sae_step(mi_ctx* ctx, int32_t t, const void* obs, size_t bytes, int32_t act_from_probe, int32_t store, uint64_t seed, const float* u,
+                int64_t* act_out, float* value_out);
+/* one minibatch of SAE.optimize_sae (agents/sae.py:151-156) on ring rows idx (flat t*E + e, n <= max_batch): pre = x W_e^T + b_e,
+ * enc = relu(pre), rec = enc W_d^T + b_d, recon = mean((rec - x)^2), rho_hat_j = mean_b enc_bj, KL = sum_j rho log((rho + eps) /
+ * (rho_hat_j + eps)) + (1 - rho) log((1 - rho + eps) / (1 - rho_hat_j + eps)), eps = 1e-10 (common/model.py:1645-1653; rho_hat_j >= 1
+ * gives NaN as there), loss = recon + sparse_coef KL.  Gradients accumulate un-scaled.  log_out (may be NULL): {recon, KL, loss}. */
+int mi_sae_minibatch(mi_ctx* ctx, const int64_t* idx, int32_t n, float sparse_coef, float* log_out);
+/* one minibatch of SAE.optimize_linear_model (agents/sae.py:193-201): the encoder runs forward only; logit_loss = KLDivLoss(batchmean)(
+ * log_softmax(enc W_p^T + b_p), softmax(stored logits)); value_loss = ((value_hat - value_batch)**2).mean() AS WRITTEN there --
+ * (n,1) - (n,) broadcasts, so it is the mean over all n^2 pairs (i, j) of (v_hat_i - v_j)^2; loss = logit_loss + value_loss.
+ * log_out (may be NULL): {value_loss, logit_loss, loss}. */
+int mi_sae_probe_minibatch(mi_ctx* ctx, const int64_t* idx, int32_t n, float* log_out);
+/* clip_grad_norm_ + Adam(eps=1e-5).step + zero_grad on one model (agents/sae.py:159-162, :204-207); adam_step = 1-based step count */
+int mi_sae_optimizer_step(mi_ctx* ctx, int32_t which, float lr, float max_grad_norm, int32_t adam_step, float* grad_norm_out);
+/* test hook: the forward pass of mi_sae_minibatch on ring rows idx -> enc (n x S) and rec (n x 2048, the reference's column order) */
+int mi_sae_debug_forward(mi_ctx* ctx, const int64_t* idx, int32_t n, float* enc_out, float* rec_out);
+
 /* ---- data-parallel collectives inside the boundary: RCCL over xGMI, one communicator per context (SURVEY 8(b) mi_allreduce_grads,
  *      8(e) C1-C3).  Rank 0 obtains a 128-byte id (mi_comm_unique_id) and hands it to every rank by any host channel
  *      (mi355/dist.py uses torch.distributed.broadcast_object_list); every rank then calls mi_comm_init(id, rank, world).

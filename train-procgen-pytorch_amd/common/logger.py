@@ -94,3 +94,23 @@ class Logger(object):
         if self.use_wandb:
             import wandb
             wandb.log(dict(zip(self.columns, row)))
+
+
+class SimpleLogger(Logger):
+    """common/logger.py:217-236: episode statistics + the agent's summary, printed (and sent to wandb); no CSV row."""
+
+    STAT_NAMES = ["Rewards/max_episodes", "Rewards/mean_episodes", "Rewards/median_episodes", "Rewards/min_episodes", "Len/max_episodes",
+                  "Len/mean_episodes", "Len/min_episodes", "Len/mean_timeout", "Len/mean_episodes_pos_reward", "Rewards/balanced_mean"]
+
+    def dump(self, summary={}, lr=0.):
+        wall = time.time() - self.start_time
+        stats = dict(zip(self.STAT_NAMES, self.train.stats()))
+        stats.update(zip(["[Valid] " + k for k in self.STAT_NAMES], self.valid.stats()))
+        stats.update(summary)
+        stats.update({"timesteps": self.timesteps, "wall_time": wall, "num_episodes": self.num_episodes, "learning_rate": lr})
+        self.last = stats
+        if self.use_wandb:
+            import wandb
+            wandb.log(stats)
+        for k, v in stats.items():
+            print(f"{k}:\t\t{v:.3g}" if isinstance(v, (int, float, np.floating)) else f"{k}:\t\t{v}")

@@ -129,3 +129,36 @@ class GRU(nn.Module):
 
     def forward(self, x, hxs, masks):
         raise NotImplementedError("the GRU cell runs inside the engine's policy step; call policy(obs, hx, masks)")
+
+
+class SparseAutoencoder(nn.Module):
+    """Parameter container of the reference's SparseAutoencoder (common/model.py:1623-1653): same module tree, init calls and call
+    order, so a seed gives bit-identical weights and ``state_dict()`` has the keys encoder.0.weight / encoder.0.bias /
+    decoder.0.weight / decoder.0.bias.  The forward pass, the KL sparsity term and their gradients run in the engine
+    (csrc/sae.hip, mi_sae_minibatch)."""
+
+    def __init__(self, input_dim, hidden_dim, rho):
+        super().__init__()
+        self.rho = rho
+        self.input_dim, self.hidden_dim = input_dim, hidden_dim
+        self.encoder = nn.Sequential(nn.Linear(input_dim, hidden_dim), nn.ReLU(inplace=True))
+        self.decoder = nn.Sequential(nn.Linear(hidden_dim, input_dim))
+        self.apply(xavier_uniform_init)
+
+    def forward(self, x):
+        raise NotImplementedError("SparseAutoencoder has no compute path of its own: agents.sae.SAE runs it on the MI355X engine")
+
+
+class LinearSAEProbe(nn.Module):
+    """Parameter container of the reference's LinearSAEProbe (common/model.py:1655-1667): fc_policy (log-softmax logits) and fc_value
+    on the SAE's codes; computed in the engine (mi_sae_probe_minibatch, mi_sae_step)."""
+
+    def __init__(self, hidden_dim, n_actions):
+        super().__init__()
+        self.hidden_dim, self.n_actions = hidden_dim, n_actions
+        self.fc_policy = nn.Linear(hidden_dim, n_actions)
+        self.fc_value = nn.Linear(hidden_dim, 1)
+        self.apply(xavier_uniform_init)
+
+    def forward(self, encoded):
+        raise NotImplementedError("LinearSAEProbe has no compute path of its own: agents.sae.SAE runs it on the MI355X engine")

@@ -278,3 +278,76 @@ class Storage:
         rewards = [r for dq in self.performance_track.values() for r in dq]
         true_average_reward = np.mean(rewards) if rewards else np.nan
         return rew_batch, done_batch, true_average_reward
+
+
+class SAEStorage(Storage):
+    """SAEStorage (reference: common/storage.py:513-569) over the engine's SAE rings (mi_sae_create): features (T+1, E, 2048) and the
+    policy's logits (T, E, A) beside the context's own observation / value / action / reward / done rings.  Same constructor and
+    ``fetch_log_data``; ``store`` / ``store_last`` feed the device rings; ``fetch_train_generator`` yields the minibatches' flat INDEX
+    vectors (drawn exactly as Storage's: one torch.randperm(T*E) per epoch, BatchSampler with drop_last) -- the rows themselves never
+    leave the device; ``collate_data(indices)`` reads the reference's 5-tuple back for whoever wants the tensors."""
+
+    def __init__(self, obs_shape, hidden_state_size, num_steps, num_envs, device, continuous_actions=False, act_shape=None):
+        super().__init__(obs_shape, hidden_state_size, num_steps, num_envs, device, continuous_actions, act_shape)
+        if self.arch != "impala":
+            raise NotImplementedError("SAEStorage: architecture mlpmodel is not supported (the SAE reads ImpalaModel's block-3 features)")
+        self.ring = True
+
+    def attach_engine(self, engine, ring=True):
+        """ring=False: a validation storage -- the engine's steps do not store (mi_sae_step with store = 0), only the host mirrors
+        that fetch_log_data reads are kept (the reference uses storage_valid for nothing else, agents/sae.py:245-254)."""
+        super().attach_engine(engine)
+        self.ring = bool(ring)
+
+    def reset(self):
+        self.info_batch = deque(maxlen=self.num_steps)
+        self.step = 0
+        self._pending = None
+        self._hidden = np.zeros((0,), np.float32)          # (the PPO storage's recurrent-state mirror: unused here)
+        self._stepped = None
+
+    def note_stepped(self, t):
+        """The agent's engine step has already written hidden, logits, value, action and frames of ring step t."""
+        self._stepped = t
+
+    def store(self, obs, hidden, act, rew, done, info, logits, value):
+        eng, t = self._eng(), self.step
+        if self.ring and self._stepped != t:               # caller data (reference path): everything goes up here
+            self._keep = eng.put_obs(t, as_device_obs(obs, self.arch))
+            eng.sae_put_ring(t, np.asarray(hidden), np.asarray(logits))
+            eng.put_policy_outputs(t, np.asarray(act), None, np.asarray(value))
+        self._rew[t] = rew
+        self._done[t] = done
+        if self.ring:
+            eng.put_step(t, self._rew[t], self._done[t])
+        self.info_batch.append(info)
+        self._stepped = None
+        self.step = (self.step + 1) % self.num_steps
+
+    def store_last(self, last_obs, last_hidden, last_value):
+        eng, T = self._eng(), self.num_steps
+        if self.ring and self._stepped != T:
+            self._keep = eng.put_obs(T, as_device_obs(last_obs, self.arch))
+            eng.sae_put_ring(T, np.asarray(last_hidden), None)
+            eng.put_policy_outputs(T, None, None, np.asarray(last_value))
+        self._stepped = None
+
+    hidden_batch = property(lambda self: torch.from_numpy(np.stack([self._eng().sae_get_hidden(t) for t in range(self.num_steps + 1)])))
+    logit_batch = property(lambda self: torch.from_numpy(np.stack([self._eng().sae_get_logits(t) for t in range(self.num_steps)])))
+
+    def collate_data(self, indices):
+        """(obs, hidden, act, logit, value) of explicit indices (storage.py:550-556), read back from the device."""
+        idx = np.asarray(indices, dtype=np.int64)
+        T, E = self.num_steps, self.num_envs
+        t, e = idx // E, idx % E
+        frames = {int(tt): self._obs_as_ref(int(tt)) for tt in np.unique(t)}
+        hid = {int(tt): self._eng().sae_get_hidden(int(tt)) for tt in np.unique(t)}
+        lg = {int(tt): self._eng().sae_get_logits(int(tt)) for tt in np.unique(t)}
+        pick = lambda d: torch.from_numpy(np.stack([d[int(a)][int(b)] for a, b in zip(t, e)]))
+        g = lambda f: self._field(f)[:T].reshape(-1)[idx]
+        return pick(frames), pick(hid), g(M.F_ACT), pick(lg), g(M.F_VALUE)
+
+    def fetch_train_generator(self, mini_batch_size=None, recurrent=False):
+        if recurrent:
+            raise NotImplementedError("SAEStorage.fetch_train_generator(recurrent=True): the SAE agent is non-recurrent")
+        yield from self.minibatch_index_stream(mini_batch_size, False)

@@ -43,7 +43,9 @@ EXPORTS = ("mi_last_error mi_create mi_destroy mi_sync mi_host_alloc mi_host_fre
            "mi_put_policy_outputs mi_read_field mi_write_field mi_policy_step mi_rollout_step mi_rollout_groups mi_rollout_submit mi_rollout_wait mi_predict_staged mi_value_saliency mi_commit_staged mi_set_gru mi_rec_state mi_get_hidden mi_rec_begin mi_get_hidden_ring mi_forward_rec mi_forward mi_compute_estimates "
            "mi_adv_stats mi_adv_apply mi_minibatch mi_minibatch_multi mi_optimizer_step mi_loss_log_read mi_device_ptr "
            "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_gru_step mi_debug_step_latency "
-           "mi_gru_train mi_minibatch_rec mi_get_gru mi_get_gru_grads mi_get_gru_adam_state mi_set_gru_adam_state mi_debug_gru_seq").split()
+           "mi_gru_train mi_minibatch_rec mi_get_gru mi_get_gru_grads mi_get_gru_adam_state mi_set_gru_adam_state mi_debug_gru_seq "
+           "mi_sae_create mi_sae_destroy mi_sae_param_count mi_sae_set_params mi_sae_get_params mi_sae_get_grads mi_sae_set_adam_state mi_sae_get_adam_state mi_sae_put_ring "
+           "mi_sae_get_hidden mi_sae_get_logits mi_sae_step mi_sae_minibatch mi_sae_probe_minibatch mi_sae_optimizer_step mi_sae_debug_forward").split()
 
 
 def load_library():
@@ -58,6 +60,7 @@ def load_library():
     lib = C.CDLL(path)
     lib.mi_last_error.restype = C.c_char_p
     lib.mi_param_count.restype = C.c_int64
+    lib.mi_sae_param_count.restype = C.c_int64
     lib.mi_host_alloc.restype = C.c_void_p
     lib.mi_host_alloc.argtypes = [C.c_size_t]
     lib.mi_host_free.argtypes = [C.c_void_p]
@@ -117,6 +120,9 @@ class Engine:
             for p in list(getattr(self, "_registered", {})):
                 self.lib.mi_host_unregister(p)
             self._registered = {}
+            if getattr(self, "sae_dim", None) is not None:          # the SAE agent's state hangs beside the context (mi_sae_create)
+                self.lib.mi_sae_destroy(self._ctx)
+                self.sae_dim = None
             self.lib.mi_destroy(self._ctx)
             self._ctx = C.c_void_p()
 
@@ -474,6 +480,99 @@ class Engine:
         n = C.c_int32(0)
         self._chk(self.lib.mi_loss_log_read(self._ctx, _fp(out), C.c_int32(max_records), C.byref(n), C.c_int32(int(reset))))
         return out[:n.value].copy()
+
+    # ------------------------------------------------------------------ sparse-autoencoder agent (algo: sae)
+    SAE, PROBE = 0, 1                      # `which` of the mi_sae_* entry points
+    SAE_INPUT_DIM = 2048                   # ImpalaModel.encoded_dim
+    SAE_DIMS = tuple(range(64, 4097, 64))
+
+    def sae_create(self, sae_dim, rho):
+        """Allocates the SAE, the probe, their optimiser state and the feature / logit rings on this context (mi_sae_create)."""
+        if self.arch != ARCH_IMPALA:
+            raise NotImplementedError("architecture mlpmodel: the SAE agent needs ImpalaModel (encoded_dim / forward_to_pool exist only there)")
+        if int(sae_dim) not in self.SAE_DIMS:
+            raise NotImplementedError(f"sae_dim={sae_dim}: supported are the multiples of 64 in [64, 4096]")
+        self._chk(self.lib.mi_sae_create(self._ctx, C.c_int32(int(sae_dim)), C.c_float(rho)))
+        self.sae_dim = int(sae_dim)
+
+    def sae_param_count(self, which):
+        return int(self.lib.mi_sae_param_count(self._ctx, C.c_int32(which)))
+
+    def sae_set_params(self, which, flat):
+        flat = _f32(flat).reshape(-1)
+        self._chk(self.lib.mi_sae_set_params(self._ctx, C.c_int32(which), _fp(flat), C.c_int64(flat.size)))
+
+    def sae_get_params(self, which):
+        out = np.empty(self.sae_param_count(which), np.float32)
+        self._chk(self.lib.mi_sae_get_params(self._ctx, C.c_int32(which), _fp(out), C.c_int64(out.size)))
+        return out
+
+    def sae_get_grads(self, which):
+        out = np.empty(self.sae_param_count(which), np.float32)
+        self._chk(self.lib.mi_sae_get_grads(self._ctx, C.c_int32(which), _fp(out), C.c_int64(out.size)))
+        return out
+
+    def sae_set_adam_state(self, which, m, v):
+        m, v = _f32(m).reshape(-1), _f32(v).reshape(-1)
+        self._chk(self.lib.mi_sae_set_adam_state(self._ctx, C.c_int32(which), _fp(m), _fp(v), C.c_int64(m.size)))
+
+    def sae_get_adam_state(self, which):
+        n = self.sae_param_count(which)
+        m, v = np.empty(n, np.float32), np.empty(n, np.float32)
+        self._chk(self.lib.mi_sae_get_adam_state(self._ctx, C.c_int32(which), _fp(m), _fp(v), C.c_int64(n)))
+        return m, v
+
+    def sae_put_ring(self, t, hidden=None, logits=None):
+        """hidden (E, 2048) in the reference's column order / the policy's logits (E, A) into ring step t (SAEStorage.store / store_last)."""
+        hidden = None if hidden is None else _f32(hidden).reshape(self.E, self.SAE_INPUT_DIM)
+        logits = None if logits is None else _f32(logits).reshape(self.E, self.A)
+        self._chk(self.lib.mi_sae_put_ring(self._ctx, C.c_int32(t), _fp(hidden), _fp(logits)))
+
+    def sae_get_hidden(self, t):
+        out = np.empty((self.E, self.SAE_INPUT_DIM), np.float32)
+        self._chk(self.lib.mi_sae_get_hidden(self._ctx, C.c_int32(t), _fp(out)))
+        return out
+
+    def sae_get_logits(self, t):
+        out = np.empty((self.E, self.A), np.float32)
+        self._chk(self.lib.mi_sae_get_logits(self._ctx, C.c_int32(t), _fp(out)))
+        return out
+
+    def sae_step(self, t, obs, act_from_probe=False, store=True, seed=0, u=None):
+        """SAE.get_hidden_and_acts on E uint8 NHWC frames (mi_sae_step) -> (act (E,) int64, value (E,))."""
+        obs = np.ascontiguousarray(obs, dtype=np.uint8)
+        u = None if u is None else _f32(u)
+        act, val = np.empty(self.E, np.int64), np.empty(self.E, np.float32)
+        self._chk(self.lib.mi_sae_step(self._ctx, C.c_int32(t), _fp(obs), C.c_size_t(obs.nbytes), C.c_int32(int(bool(act_from_probe))),
+                                       C.c_int32(int(bool(store))), C.c_uint64(seed), _fp(u), _fp(act), _fp(val)))
+        return act, val
+
+    def sae_minibatch(self, idx, sparse_coef):
+        """One minibatch of optimize_sae on ring rows idx -> (recon, KL, loss)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        log = np.empty(3, np.float32)
+        self._chk(self.lib.mi_sae_minibatch(self._ctx, _fp(idx), C.c_int32(idx.size), C.c_float(sparse_coef), _fp(log)))
+        return log
+
+    def sae_probe_minibatch(self, idx):
+        """One minibatch of optimize_linear_model on ring rows idx -> (value_loss, logit_loss, loss)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        log = np.empty(3, np.float32)
+        self._chk(self.lib.mi_sae_probe_minibatch(self._ctx, _fp(idx), C.c_int32(idx.size), _fp(log)))
+        return log
+
+    def sae_optimizer_step(self, which, lr, max_grad_norm, adam_step, want_norm=False):
+        g = C.c_float(0)
+        self._chk(self.lib.mi_sae_optimizer_step(self._ctx, C.c_int32(which), C.c_float(lr), C.c_float(max_grad_norm), C.c_int32(adam_step),
+                                                 C.byref(g) if want_norm else None))
+        return g.value if want_norm else None
+
+    def sae_debug_forward(self, idx):
+        """(enc (n, S), rec (n, 2048)) of ring rows idx: the forward pass of sae_minibatch (test hook)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        enc, rec = np.empty((idx.size, self.sae_dim), np.float32), np.empty((idx.size, self.SAE_INPUT_DIM), np.float32)
+        self._chk(self.lib.mi_sae_debug_forward(self._ctx, _fp(idx), C.c_int32(idx.size), _fp(enc), _fp(rec)))
+        return enc, rec
 
     # ------------------------------------------------------------------ RCCL collectives (inside the library)
     def comm_unique_id(self):

@@ -67,3 +67,25 @@ def unflatten(shapes, flat):
     if o != flat.size:
         raise ValueError(f"flat vector has {flat.size} elements, layout needs {o}")
     return out
+
+
+# ---- the 2048 block-3 features (ImpalaModel.forward_to_pool; the SAE agent's input).  The reference flattens NCHW: column ch*64 + p
+# (p = h*8 + w); the engine keeps the block's output pixel-major: column p*32 + ch.  csrc/sae.hip permutes the encoder's input columns,
+# the decoder's rows / biases and the feature ring at the C boundary with this map (as engine.hip does for embedder.fc.weight).
+def feature_device_index():
+    """(2048,) int64: device column of reference column h."""
+    h = np.arange(2048)
+    return (h % 64) * 32 + h // 64
+
+
+def features_to_device(a):
+    """(..., 2048) in the reference's column order -> the engine's."""
+    out = np.empty_like(np.asarray(a))
+    out[..., feature_device_index()] = a
+    return out
+
+
+def features_from_device(a):
+    """(..., 2048) in the engine's column order -> the reference's."""
+    return np.asarray(a)[..., feature_device_index()]
+

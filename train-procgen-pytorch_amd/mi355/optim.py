@@ -90,3 +90,72 @@ class DeviceAdam:
                 self.engine.set_gru_adam_state(np.concatenate([st[p]['exp_avg'].numpy().ravel() for p in gp]),
                                                np.concatenate([st[p]['exp_avg_sq'].numpy().ravel() for p in gp]))
         self.step_count = int(float(next(st[p]['step'] for p in self._params if p in st)))
+
+
+class DeviceModelAdam:
+    """DeviceAdam for one model of the SAE agent (agents/sae.py:64-65: optim.Adam(self.sae.parameters()) / optim.Adam(self.linear_model
+    .parameters()), lr, eps=1e-5): `which` = Engine.SAE or Engine.PROBE selects the flat vector of the mi_sae_* entry points.  The
+    moments live on the device; a never-stepped torch Adam over the module's host parameters produces / consumes torch's own
+    state_dict layout."""
+
+    def __init__(self, module, engine, which, lr, eps=1e-5):
+        self.module, self.engine, self.which = module, engine, which
+        self._params = list(module.parameters())
+        self._adam = optim.Adam(self._params, lr=lr, eps=eps)
+        self.step_count = 0
+        self.device_is_newer = False
+
+    @property
+    def param_groups(self):
+        return self._adam.param_groups
+
+    @property
+    def lr(self):
+        return float(self._adam.param_groups[0]['lr'])
+
+    def zero_grad(self, set_to_none=True):
+        pass                                   # gradients are zeroed inside the fused device step
+
+    def push_params(self):
+        import numpy as np
+        self.engine.sae_set_params(self.which, np.concatenate([p.detach().cpu().numpy().ravel() for p in self._params]))
+        self.device_is_newer = False
+
+    def pull_params(self):
+        """The module's host tensors := the device's working copy (before state_dict() / a checkpoint)."""
+        if not self.device_is_newer:
+            return
+        flat, off = self.engine.sae_get_params(self.which), 0
+        with torch.no_grad():
+            for p in self._params:
+                p.copy_(torch.from_numpy(flat[off:off + p.numel()].reshape(tuple(p.shape)).copy()))
+                off += p.numel()
+        self.device_is_newer = False
+
+    def step(self, max_grad_norm, want_norm=False):
+        self.step_count += 1
+        out = self.engine.sae_optimizer_step(self.which, self.lr, max_grad_norm, self.step_count, want_norm)
+        self.device_is_newer = True
+        return out
+
+    def state_dict(self):
+        if self.step_count > 0:
+            m, v = self.engine.sae_get_adam_state(self.which)
+            off = 0
+            for p in self._params:
+                k = p.numel()
+                self._adam.state[p] = {'step': torch.tensor(float(self.step_count)),
+                                       'exp_avg': torch.from_numpy(m[off:off + k].reshape(tuple(p.shape)).copy()),
+                                       'exp_avg_sq': torch.from_numpy(v[off:off + k].reshape(tuple(p.shape)).copy())}
+                off += k
+        return self._adam.state_dict()
+
+    def load_state_dict(self, sd):
+        import numpy as np
+        self._adam.load_state_dict(sd)
+        st = self._adam.state
+        if len(st) == 0:
+            return
+        self.engine.sae_set_adam_state(self.which, np.concatenate([st[p]['exp_avg'].numpy().ravel() for p in self._params]),
+                                       np.concatenate([st[p]['exp_avg_sq'].numpy().ravel() for p in self._params]))
+        self.step_count = int(float(st[self._params[0]]['step']))

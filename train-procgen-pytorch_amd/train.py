@@ -34,12 +34,13 @@ import yaml
 
 from agents.ppo import PPO
 from agents.ppo_pure import PPOPure
+from agents.sae import SAE, check_supported as sae_check_supported
 from common.env.vec_envs import EnvGroups, SyntheticFrames, create_cartpole, create_procgen_env
-from common.logger import Logger
+from common.logger import Logger, SimpleLogger
 from common.misc_util import set_global_seeds
 from common.model import ImpalaModel, MLPModel
 from common.policy import CategoricalPolicy
-from common.storage import Storage
+from common.storage import SAEStorage, Storage
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -57,6 +58,11 @@ def get_hyperparams(param_name):
     with open(os.path.join(HERE, "hyperparams", "procgen", "config.yml")) as f:      # repo-relative (helper_local.py:207-210 used GLOBAL_DIR)
         sets = yaml.safe_load(f)
     if param_name not in sets:
+        # sets of the agents beside PPO (algo: sae) live in a file of their own: config.yml is the reference's PPO selection
+        with open(os.path.join(HERE, "hyperparams", "procgen", "config_sae.yml")) as f:
+            more = yaml.safe_load(f)
+        if param_name in more:
+            return dict(more[param_name])
         raise KeyError(f"--param_name {param_name}: not one of the shipped PPO sets {sorted(sets)} (other agents / architectures of the "
                        "reference's config.yml are out of scope)")
     return dict(sets[param_name])
@@ -115,8 +121,8 @@ def add_training_args(p):
     p.add_argument('--rollout_groups', type=int, default=0,
                    help="env groups of the pipelined rollout (one group's frame upload + forward beside the host's env.step of another); 0 = auto (from 128 envs per rank: 4, or 2 + 2 when a validation env runs beside the training env; else 2; a recurrent policy: 1); 1 = the reference's serial step; a recurrent policy is pipelined only with an explicit G >= 2")
     p.add_argument('--x_entropy_coef', type=float, default=None)
-    p.add_argument('--algo', type=str, default=None, choices=['ppo', 'ppo-pure'],
-                   help="overrides the set's `algo`: ppo = the reference's agents/ppo.py (a recurrent policy's GRU stays frozen), ppo-pure = agents/ppo_pure.py (a recurrent policy is trained through its GRU with BPTT; single GPU)")
+    p.add_argument('--algo', type=str, default=None, choices=['ppo', 'ppo-pure', 'sae'],
+                   help="overrides the set's `algo`: ppo = the reference's agents/ppo.py (a recurrent policy's GRU stays frozen), ppo-pure = agents/ppo_pure.py (a recurrent policy is trained through its GRU with BPTT; single GPU), sae = agents/sae.py (a sparse autoencoder on the block-3 features of the trained IMPALA policy given by --model_file, then a linear probe on its codes; single GPU, use --param_name sae)")
     return p
 
 
@@ -220,8 +226,20 @@ def train_ppo(args):
     for key, value in hp.items():
         print(key, ':', value)
     algo = hp.get("algo", "ppo")
-    if algo not in ("ppo", "ppo-pure"):
-        raise NotImplementedError("only algo: ppo and algo: ppo-pure are accelerated")
+    if algo not in ("ppo", "ppo-pure", "sae"):
+        raise NotImplementedError("only algo: ppo, algo: ppo-pure and algo: sae are accelerated")
+    if algo == "sae":
+        if args.model_file is None:
+            raise ValueError("algo sae needs --model_file <checkpoint of a trained IMPALA policy>: a sparse autoencoder of an untrained "
+                             "policy's features is not a use case")
+        if hp.get("architecture", "impala") != "impala":
+            raise NotImplementedError(f"algo sae with architecture {hp.get('architecture')} is not supported: encoded_dim / forward_to_pool "
+                                      "exist only on ImpalaModel (architecture: impala)")
+        if int(os.environ.get("WORLD_SIZE", 1)) > 1:
+            raise NotImplementedError(f"algo sae runs on a single GPU: WORLD_SIZE (world size) = {os.environ['WORLD_SIZE']} is not supported")
+        if int(getattr(args, "rollout_groups", 0) or 0) > 1:
+            raise NotImplementedError(f"algo sae runs serial rollout steps: --rollout_groups {args.rollout_groups} (env groups) is not supported")
+        args.rollout_groups = 1                             # (0 = auto would pick groups)
     if hp.get("continuous", False):
         raise NotImplementedError("continuous actions are not part of the accelerated PPO path")
     if args.device != 'gpu':
@@ -258,19 +276,25 @@ def train_ppo(args):
     cfg = dict(vars(args)); cfg.update(hp)
     np.save(os.path.join(logdir, "config.npy"), cfg)
     model, obs_shape, policy = initialize_model(device, env, hp)
-    logger = Logger(n_envs, logdir, use_wandb=args.use_wandb, algo=algo)
+    logger = (SimpleLogger if algo == "sae" else Logger)(n_envs, logdir, use_wandb=args.use_wandb, algo=algo)      # (train.py:195-199)
     logger.max_steps = hp.get("max_steps", 10 ** 3)
-    storage = Storage(obs_shape, model.output_dim, n_steps, n_envs, device)
-    storage_valid = Storage(obs_shape, model.output_dim, n_steps, n_envs, device) if args.use_valid_env else None
-    agent_cls = PPOPure if algo == "ppo-pure" else PPO
+    if algo == "sae":                                       # train.py:206-218: the storage holds the 2048 block-3 features and all A logits
+        sae_check_supported(policy, n_envs, env, hp.get("sae_dim", 1024))
+        make_storage = lambda: SAEStorage(obs_shape, model.encoded_dim, n_steps, n_envs, device, act_shape=env.action_space.n)
+    else:
+        make_storage = lambda: Storage(obs_shape, model.output_dim, n_steps, n_envs, device)
+    storage = make_storage()
+    storage_valid = make_storage() if args.use_valid_env else None
+    agent_cls = SAE if algo == "sae" else PPOPure if algo == "ppo-pure" else PPO
     agent = agent_cls(env, policy, logger, storage, device, args.num_checkpoints, env_valid=env_valid, storage_valid=storage_valid,
                 seed=args.seed + rank, detect_nan=args.detect_nan, **hp)
     if model_file is not None:
         print("Loading agent from %s" % model_file)
         ck = torch.load(model_file, map_location="cpu", weights_only=True)
         agent.policy.load_state_dict(ck["model_state_dict"])
-        agent.optimizer.load_state_dict(ck["optimizer_state_dict"])
-        if "t" in ck:                                       # (new) what the reference's checkpoint forgets: continue the step count / LR schedule
+        if algo != "sae":                                   # train.py:261-263: for algo sae the policy only (the SAE's optimizers are new)
+            agent.optimizer.load_state_dict(ck["optimizer_state_dict"])
+        if algo != "sae" and "t" in ck:                                       # (new) what the reference's checkpoint forgets: continue the step count / LR schedule
             agent.t = int(ck["t"])
             agent.optimizer, _ = agent.adjust_lr(agent.optimizer, agent.learning_rate, agent.t, int(args.num_timesteps))
         rs = ck.get("reward_norm")
@@ -278,7 +302,12 @@ def train_ppo(args):
             if rs and getattr(e, "_rew", None) is not None:
                 e._rew.load_state(rs)
     print('START TRAINING...')
+    if algo == "sae":                                       # the frozen policy as the device holds it, before and after: the same hash
+        import hashlib
+        print("policy parameters on the device, sha256:", hashlib.sha256(agent.engine.get_params().tobytes()).hexdigest())
     agent.train(int(args.num_timesteps))
+    if algo == "sae":
+        print("policy parameters on the device after training, sha256:", hashlib.sha256(agent.engine.get_params().tobytes()).hexdigest())
     return agent
 
 
