@@ -337,6 +337,16 @@ int mi_op_maxpool(mi_ctx* ctx, int32_t mode /*0 fwd,1 bwd*/, int32_t n, int32_t 
                   const float* in, const float* dout, float* out);
 int mi_op_gemm(mi_ctx* ctx, int32_t M, int32_t N, int32_t K, const float* A, int64_t sam, int64_t sak,
                const float* B, int64_t sbk, int64_t sbn, float* C);
+/* bf16 embedder.fc kernels (2048 -> D, D a multiple of 64 in [64, 512]) on caller data through the production launchers; independent of
+ * the context's sizes and precision.  x [n][2048] is rounded to bf16 on the host, W is fc.weight [D][2048] as the kernels index it.
+ * mode 0: (x, W, b) -> out = y [n][D] = relu(relu(x) W^T + b), the update-sized forward; mode 1: the same through the rollout-sized forward;
+ * mode 2: (dy [n][D], W, x = the ReLU mask source, required) -> out = dx [n][2048] = (dy W) * (x > 0), bf16 widened to fp32;
+ * mode 3: (dy, x) with out = gW [D][2048] and out_b = gb [D] holding the initial gradients -> gW += dy^T relu(x), gb += colsum(dy).
+ * Refused (-1): D outside the eight widths, n outside [1, 65536] (the upper limit only keeps the hook's allocations sane), mode 2 without x.
+ * W goes through launch_fc_pack; production fills the same two images in repack_all_kernel, which only the end-to-end tests compare.
+ * Outputs are poisoned and followed by canary bands as in mi_op_resblock. */
+int mi_op_fc_bf16(mi_ctx* ctx, int32_t mode, int32_t n, int32_t D, const float* x, const float* W, const float* b, const float* dy,
+                  float* out, float* out_b);
 int mi_selftest_mfma(mi_ctx* ctx, float* max_err);
 /* what the last mi_minibatch left in the activation buffers (first n samples), fp32 NHWC: which = 8 * block + k, k = 0 pooled map,
  * 1 res1.conv1 out, 2 res1 out, 3 res2.conv1 out, 4 block out, 5 max-pool arg-max (window position ky*3+kx); which = 100: features

@@ -492,6 +492,71 @@ int mi_op_gemm(mi_ctx* c, int32_t M, int32_t N, int32_t K, const float* A, int64
     return 0;
 }
 
+// embedder.fc's bf16 matrix-core kernels (fc_bf16.hip) on caller data, through the production launchers with the arguments
+// backward_impala_bf16 / forward_impala_bf16 pass; independent of the context's sizes and precision.  D = the width (a multiple of 64 in
+// [64, 512]), n rows, K = 2048 inputs.  x goes up rounded to bf16 (host_to_bf16), W [D][2048] through launch_fc_pack.
+// (Production fills fc_wp / fc_wt in the fc section of repack_all_kernel, conv_bf16.hip, not through launch_fc_pack: that the two write the
+// same images is checked by the end-to-end fc tests only, not here.)
+//   mode 0: out = y [n][D] = relu(relu(x) W^T + b), launch_fc_fwd_bf16           mode 1: the same through launch_fc_fwd_small_bf16
+//   mode 2: out = dx [n][2048] = (dy W) * (x > 0), launch_fc_dgrad_bf16 (bf16, widened); x is the mask source and is required: without a
+//           mask the launcher takes the tiled kernel, which needs D % 128 == 0
+//   mode 3: out = gW [D][2048], out_b = gb [D], both in / out: += dy^T relu(x) (launch_fc_tn with the engine's 8 M-float workspace) and
+//           += colsum(dy) (launch_colsum_acc)
+int mi_op_fc_bf16(mi_ctx* c, int32_t mode, int32_t n, int32_t D, const float* x, const float* W, const float* b, const float* dy,
+                  float* out, float* out_b) {
+    ARG(c && out, "null"); JOIN(c);
+    ARG(mode >= 0 && mode <= 3, "mode");
+    ARG(D >= 64 && D <= 512 && D % 64 == 0, "D must be a multiple of 64 in [64, 512]");
+    ARG(n >= 1 && n <= 65536, "n must be in [1, 65536]");
+    ARG(mode != 2 || x, "mode 2 needs the mask source x (the data gradient without a mask has no kernel for every width)");
+    ARG(x && (mode == 3 || W) && (mode >= 2 || b) && (mode <= 1 || dy) && (mode != 3 || out_b), "null");
+    const std::string hook = "mi_op_fc_bf16 mode " + std::to_string(mode);
+    OpMem m(hook.c_str(), c->stream);
+    constexpr int K = 2048;
+    const size_t nx = (size_t)n * K, nd = (size_t)n * D, nw = (size_t)D * K;
+    void* dxb = nullptr; float *dw = nullptr, *db = nullptr, *ddy = nullptr; unsigned short *wp = nullptr, *wt = nullptr;
+    { const auto h = host_to_bf16(x, nx); if (int r = upload(m, h.data(), nx * 2, &dxb)) return r; }
+    if (mode != 3) {
+        if (int r = upload(m, W, nw * 4, (void**)&dw)) return r;
+        HIPC(m.alloc(&wp, nw * 2)); HIPC(m.alloc(&wt, nw * 2));
+        launch_fc_pack(dw, wp, wt, D, K, c->stream);
+    }
+    if (mode <= 1) {
+        float* y = nullptr;
+        if (int r = upload(m, b, (size_t)D * 4, (void**)&db)) return r;
+        HIPC(m.out(&y, nd * 4, "y"));
+        if (mode == 0) launch_fc_fwd_bf16(dxb, wp, db, y, n, D, c->stream);
+        else launch_fc_fwd_small_bf16(dxb, wp, db, y, n, D, c->stream);
+        if (int r = op_finish(c, m)) return r;
+        HIPC(hipMemcpy(out, y, nd * 4, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    if (int r = upload(m, dy, nd * 4, (void**)&ddy)) return r;
+    if (mode == 2) {
+        void* dxo = nullptr;
+        HIPC(m.out(&dxo, nx * 2, "dx"));
+        launch_fc_dgrad_bf16(ddy, wt, dxb, dxo, n, D, c->stream);
+        if (int r = op_finish(c, m)) return r;
+        std::vector<uint16_t> h(nx);
+        HIPC(hipMemcpy(h.data(), dxo, nx * 2, hipMemcpyDeviceToHost));
+        host_from_bf16(h.data(), out, nx);
+        return 0;
+    }
+    // the engine's workspaces (mi_create): 8 M floats of split slabs, 64 x 4096 floats of column-sum partials.  Poisoned: the sums read
+    // exactly what the kernels before them must have written
+    const size_t ws_floats = (size_t)8 << 20;
+    float *gw = nullptr, *gb = nullptr, *ws = nullptr, *col_ws = nullptr;
+    HIPC(m.out(&gw, nw * 4, "gW")); HIPC(m.out(&gb, (size_t)D * 4, "gb"));
+    HIPC(m.out(&ws, ws_floats * 4, "the split workspace")); HIPC(m.out(&col_ws, (size_t)64 * 4096 * 4, "the column-sum workspace"));
+    HIPC(hipStreamSynchronize(c->stream));          // (the fills run on the context's stream, the copies on the null stream)
+    HIPC(hipMemcpy(gw, out, nw * 4, hipMemcpyHostToDevice)); HIPC(hipMemcpy(gb, out_b, (size_t)D * 4, hipMemcpyHostToDevice));
+    launch_fc_tn(ddy, (const unsigned short*)dxb, gw, ws, ws_floats, D, K, n, c->stream);
+    launch_colsum_acc(ddy, n, D, D, gb, col_ws, c->stream);
+    if (int r = op_finish(c, m)) return r;
+    HIPC(hipMemcpy(out, gw, nw * 4, hipMemcpyDeviceToHost)); HIPC(hipMemcpy(out_b, gb, (size_t)D * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // D = A(16x4) * B(4x16) with asymmetric integer data through the operand maps the kernels assume:
 // A[i = lane&15][k = lane>>4], B[k = lane>>4][j = lane&15], D[row = (lane>>4)*4 + r][col = lane&15]
 __global__ void mfma_selftest_kernel(float* d) {

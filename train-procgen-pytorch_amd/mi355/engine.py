@@ -42,7 +42,7 @@ EXPORTS = ("mi_last_error mi_create mi_destroy mi_sync mi_host_alloc mi_host_fre
            "mi_get_params mi_copy_params mi_get_grads mi_set_adam_state mi_get_adam_state mi_put_obs mi_get_obs mi_put_step "
            "mi_put_policy_outputs mi_read_field mi_write_field mi_policy_step mi_rollout_step mi_rollout_groups mi_rollout_submit mi_rollout_wait mi_predict_staged mi_value_saliency mi_commit_staged mi_set_gru mi_rec_state mi_get_hidden mi_rec_begin mi_get_hidden_ring mi_forward_rec mi_forward mi_compute_estimates "
            "mi_adv_stats mi_adv_apply mi_minibatch mi_minibatch_multi mi_optimizer_step mi_loss_log_read mi_device_ptr "
-           "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_gru_step mi_debug_step_latency "
+           "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_op_fc_bf16 mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_gru_step mi_debug_step_latency "
            "mi_gru_train mi_minibatch_rec mi_get_gru mi_get_gru_grads mi_get_gru_adam_state mi_set_gru_adam_state mi_debug_gru_seq "
            "mi_sae_create mi_sae_destroy mi_sae_param_count mi_sae_set_params mi_sae_get_params mi_sae_get_grads mi_sae_set_adam_state mi_sae_get_adam_state mi_sae_put_ring "
            "mi_sae_get_hidden mi_sae_get_logits mi_sae_step mi_sae_minibatch mi_sae_probe_minibatch mi_sae_optimizer_step mi_sae_debug_forward").split()
@@ -681,6 +681,23 @@ class Engine:
         self._chk(self.lib.mi_op_gemm(self._ctx, C.c_int32(M), C.c_int32(N), C.c_int32(K), _fp(A), C.c_int64(sam),
                                       C.c_int64(sak), _fp(B), C.c_int64(sbk), C.c_int64(sbn), _fp(out)))
         return out
+
+    def op_fc_bf16(self, mode, D, x=None, W=None, b=None, dy=None, gW0=None, gb0=None):
+        """The bf16 embedder.fc kernels (2048 -> D) on caller data through the production launchers (mi_op_fc_bf16), any context.
+        mode 0 / 1 (x, W, b) -> y (n, D) by the update-sized / rollout-sized forward; mode 2 (dy, W, x = mask source) -> dx (n, 2048);
+        mode 3 (dy, x, gW0, gb0) -> (gW0 + dy^T relu(x), gb0 + colsum(dy))."""
+        x, W, b, dy = (None if a is None else _f32(a) for a in (x, W, b, dy))
+        n = (dy if mode >= 2 and dy is not None else x).shape[0]
+        out_b = None
+        if mode <= 1:
+            out = np.empty((n, D), np.float32)
+        elif mode == 2:
+            out = np.empty((n, 2048), np.float32)
+        else:
+            out, out_b = np.array(gW0, dtype=np.float32, order="C"), np.array(gb0, dtype=np.float32, order="C")
+        self._chk(self.lib.mi_op_fc_bf16(self._ctx, C.c_int32(mode), C.c_int32(n), C.c_int32(D), _fp(x), _fp(W), _fp(b), _fp(dy), _fp(out),
+                                         _fp(out_b)))
+        return (out, out_b) if mode == 3 else out
 
     def debug_read(self, which, n):
         """Activation tensor `which` (see include/mi355ppo.h mi_debug_read) of the last minibatch pass, first n samples, fp32 NHWC."""
