@@ -85,7 +85,7 @@ def impala_backward(p, cache, dfeat_post, feat, rounding=True, dtype=torch.float
     gy = r((dq @ wfc).reshape(cache["x3"].shape) * (cache["x3"] > 0))
     if fs_coef:
         # + fs_coef * d mean_j max_b tanh(|100 h_bj|) / dh (common/model.py:207): one element per column, the row torch.max picks;
-        # the engine adds it to the stored (bf16) gradient element and rounds again (misc.hip fs_apply_kernel)
+        # the engine adds it to the stored (bf16) gradient element and rounds again (loss.hip fs_apply_kernel)
         h = cache["flat"]
         t, am = torch.max(torch.tanh(torch.abs(h * 100)), 0)
         cols = torch.arange(h.shape[1])

@@ -29,10 +29,10 @@ ADDR_OPS = ("v_and_b32", "v_lshrrev_b32", "v_lshlrev_b32", "v_mul_u32_u24", "v_x
             "v_and_or_b32", "v_lshl_or_b32", "v_mul_lo_u32", "v_bfe_u32", "v_add_lshl_u32", "v_sub_u32", "v_mad_u64_u32", "v_lshl_add_u64", "v_ashrrev_i32")
 
 
-def makefile_flags():
-    """HIPCC, and CXXFLAGS with $(ARCH) filled in, as csrc/Makefile sets them."""
+def makefile_flags(csrc=CSRC):
+    """HIPCC, and CXXFLAGS with $(ARCH) filled in, as csrc/Makefile sets them (csrc: that directory of another checkout)."""
     var = {}
-    for line in open(os.path.join(CSRC, "Makefile")):
+    for line in open(os.path.join(csrc, "Makefile")):
         m = re.match(r"^(\w+)\s*\??=\s*(.*)$", line.rstrip("\n"))
         if m and m.group(1) not in var:
             var[m.group(1)] = m.group(2).strip()
@@ -40,11 +40,11 @@ def makefile_flags():
     return os.environ.get("HIPCC", var.get("HIPCC", "hipcc")), flags.split()
 
 
-def compile_to_asm(src):
-    hipcc, flags = makefile_flags()
+def compile_to_asm(src, csrc=CSRC, extra=()):
+    hipcc, flags = makefile_flags(csrc)
     fd, out = tempfile.mkstemp(suffix=".s")
     os.close(fd)
-    cmd = [hipcc] + flags + ["-I", CSRC, "--cuda-device-only", "-S", src, "-o", out]
+    cmd = [hipcc] + flags + list(extra) + ["-I", csrc, "--cuda-device-only", "-S", src, "-o", out]
     r = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
     if r.returncode != 0:
         sys.exit(r.stderr)

@@ -22,11 +22,11 @@ int main(int argc, char** argv) {
         float ms; hipEventElapsedTime(&ms, e0, e1);
         printf("%-10s n=%d: %.1f us/launch  (%s)\n", nm, n, ms * 1000 / reps, hipGetErrorString(hipGetLastError()));
     };
-    timeit("forward", [&] { launch_fc_fwd_bf16(x, wp, bias, y, n, st); });
+    timeit("forward", [&] { launch_fc_fwd_bf16(x, wp, bias, y, n, 256, st); });
 #ifdef FC_TIMING
     unsigned long long zero[8] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_fc_timing), zero, sizeof zero);
 #endif
-    timeit("dgrad", [&] { launch_fc_dgrad_bf16(dy, wt, x, dx, n, st); });
+    timeit("dgrad", [&] { launch_fc_dgrad_bf16(dy, wt, x, dx, n, 256, st); });
 #ifdef FC_TIMING
     unsigned long long t[8]; hipMemcpyFromSymbol(t, HIP_SYMBOL(g_fc_timing), sizeof t);
     const double wgs = (double)(2048 / (64 * FD_STEPS)) * (n / 128) * (reps + 1);

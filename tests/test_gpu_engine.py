@@ -427,7 +427,7 @@ def test_copy_params_device_to_device(precision):
 
 
 def test_philox_known_answers_and_the_samplers_uniforms():
-    """The generator every real rollout samples with (csrc/misc.hip philox4x32_10 / philox_uniform) against (a) the Random123
+    """The generator every real rollout samples with (csrc/policy_math.h philox4x32_10 / philox_uniform) against (a) the Random123
     known-answer vectors for philox4x32 with 10 rounds (counter 0 / key 0, all ones, the pi digits), (b) the numpy restatement
     oracle/philox.py -- itself pinned to the same vectors on the CPU -- on 100 000 random (counter, key) pairs, bit for bit, and (c) the
     float conversion: the uniform the sample kernels draw for (seed, counter) is the top 24 bits of word 0 times 2^-24."""

@@ -1,5 +1,5 @@
 """Host-side helpers of the PPO path (reference: common/misc_util.py:67-96).  The loss helpers of
-that file (cross_batch_entropy etc.) live inside the fused HIP loss kernel (csrc/misc.hip)."""
+that file (cross_batch_entropy etc.) live inside the fused HIP loss kernel (csrc/loss.hip)."""
 import numpy as np
 import torch
 import torch.nn as nn

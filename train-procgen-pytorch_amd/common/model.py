@@ -121,7 +121,7 @@ class MLPModel(_EngineBacked):
 class GRU(nn.Module):
     """Weights of the recurrent wrapper (model.py:212-216; orthogonal_init is a no-op on nn.GRU, so torch's
     default uniform init stays).  In ``algo: ppo`` the reference runs the GRU in predict only and never trains it
-    (SURVEY 8(a) A9): the cell runs inside the engine's policy step (csrc/misc.hip gru_gates_kernel)."""
+    (SURVEY 8(a) A9): the cell runs inside the engine's policy step (csrc/gru_cell.hip gru_gates_kernel)."""
 
     def __init__(self, input_size, hidden_size):
         super().__init__()

@@ -22,9 +22,9 @@
 // loop; the four waves are summed through LDS in a fixed order and every workgroup writes one
 // slab, which reduce_slabs adds up in a fixed order (bitwise reproducible, no float atomics).
 #include "common.h"
+#include "device_util.h"
 #include <mutex>
 
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 template <int CIN_, int CINP_, int COUT_, int HW_, int TH_, int TW_, int NIMG_, bool IN_U8_, bool TRANSW_, bool BFIO_ = false>
 struct FwdCfg {
@@ -53,8 +53,6 @@ struct FwdCfg {
 // Input-tile staging is split in two so that the HBM latency of tile i+1 hides under the MFMAs of tile i
 // (issue-early / write-late): tile_load puts the next tile's global loads in flight into registers before the
 // compute phase, tile_store converts (uint8 -> fp32 table / ReLU) and writes them to LDS after it.
-__device__ __forceinline__ unsigned short f2bf(float x) { __bf16 h = (__bf16)x; return __builtin_bit_cast(unsigned short, h); }
-__device__ __forceinline__ float bf2f(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
 template <bool BF> __device__ __forceinline__ float ld_act(const void* p, long long o) {
     if constexpr (BF) return bf2f(((const unsigned short*)p)[o]); else return ((const float*)p)[o];
 }

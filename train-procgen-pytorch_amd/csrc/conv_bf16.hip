@@ -9,20 +9,12 @@
 // (lane quarter kq owns channels 8kq..8kq+7); for 16 input channels it is two taps (kq>>1 selects the tap,
 // kq&1 the 8-channel half), the 10th "tap" being a zero column of the filter bank.
 #include "common.h"
+#include "device_util.h"
 #include <mutex>
 #include <type_traits>
 
 static int c1_grid(int n);          // persistent grid of the block1.conv weight-gradient kernel (defined with it)
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;      // ds_read_b64_tr_b16 operand
-#define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
-__device__ __forceinline__ unsigned short f2bf(float x) {
-    __bf16 h = (__bf16)x;                                   // v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN
-    return __builtin_bit_cast(unsigned short, h);
-}
-__device__ __forceinline__ float bf2f(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
 
 // ------------------------------------------------------------------------------------------ max-pool backward as an operand stage
 // The gradient of a block's first conv output is never stored: its consumers (the conv's data-gradient and weight-gradient
@@ -1254,16 +1246,8 @@ using C1P = C1T<9>;
 #ifndef C1P_SC
 #define C1P_SC 24         // conv-output tile pixel stride in LDS (bf16 elements)
 #endif
-// block1.conv forward bank in the LDS layout of the conv1 kernels: [16 filters][C1_WS], K index k = tap*4 + ci (ci == 3 and k >= 36 zero)
-__global__ void pack_conv1_bank_kernel(const float* __restrict__ w, unsigned short* __restrict__ bank) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= 16 * C1_WS) return;
-    const int j = e / C1_WS, k = e % C1_WS, tap = k / 4, ci = k % 4;
-    bank[e] = f2bf((k < 36 && ci < 3) ? w[(j * 9 + tap) * 3 + ci] : 0.f);
-}
-void launch_pack_conv1_bank(const float* w, unsigned short* bank, hipStream_t st) {
-    hipLaunchKernelGGL(pack_conv1_bank_kernel, dim3((16 * C1_WS + 255) / 256), dim3(256), 0, st, w, bank);
-}
+// block1.conv forward bank in the LDS layout of the conv1 kernels: [16 filters][C1_WS], K index k = tap*4 + ci (ci == 3 and k >= 36 zero);
+// repack_all_kernel packs it
 int conv1_bank_elems() { return 16 * C1_WS; }
 // Every bf16 image of the parameters in ONE launch after an optimizer step (three launches before): blocks [0, 8 n_desc) the conv filter
 // banks (pack_banks_kernel's element loop, 8 blocks per bank), the next few block1.conv's bank, the rest embedder.fc's two packed
@@ -1326,7 +1310,7 @@ __global__ __launch_bounds__(256, 4) void conv1_pool_fwd_bf16_kernel(ConvArgs a,
 #ifdef WG_TIMING
     long long tacc_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast_ = clock64();
 #endif
-    if (a.wbank) {                                         // pre-packed by pack_conv1_bank_kernel: one 16-byte load per thread (the rollout-sized
+    if (a.wbank) {                                         // pre-packed by repack_all_kernel: one 16-byte load per thread (the rollout-sized
         if (tid < 16 * C1_WS / 8) ((uint4*)s_w)[tid] = ((const uint4*)a.wbank)[tid];      // launch runs this prologue for 2 items only)
     } else {
         for (int e = tid; e < 16 * C1_WS; e += 256) {
@@ -1781,13 +1765,6 @@ using BD_32_32_8  = BfCfg<32, 32,  8,  8,  8, 4, true>;
 
 template <class C, bool POOLIN>
 static constexpr size_t bf_lds_bytes() { return C::LDS_BYTES + (POOLIN ? PoolStage<C::CIN, C::HW / 2, C::TH / 2 + 3>::BYTES : 0); }
-template <class C, bool POOLIN>
-static int bf_grid(int n) {
-    int bpc = (int)((160 * 1024) / bf_lds_bytes<C, POOLIN>());
-    bpc = bpc < 1 ? 1 : (bpc > 4 ? 4 : bpc);
-    int grid = (C::NIMG > 1) ? (n + C::NIMG - 1) / C::NIMG : n * C::TPI;
-    return grid > 256 * bpc ? 256 * bpc : grid;
-}
 template <class C, bool POOLIN = false>
 static void launch_bf_t(const ConvArgs& a, hipStream_t st) {
     static std::once_flag attr;

@@ -7,12 +7,10 @@
 // backward: the gradient of the conv output is never materialised either.  PoolStage (conv_bf16.hip) rebuilds any window of it
 //           in LDS from (pooled gradient, arg-max bytes) for the conv's weight-gradient and data-gradient kernels.
 #include "common.h"
+#include "device_util.h"
 #include <mutex>
 #include <math.h>
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-#define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
-__device__ __forceinline__ unsigned short cp_f2bf(float x) { __bf16 h = (__bf16)x; return __builtin_bit_cast(unsigned short, h); }
 
 template <int CIN_, int COUT_, int HW_>
 struct CpCfg {

@@ -253,7 +253,7 @@ int mi_create(const mi_config* cfg, mi_ctx** out) {
         }
         HIPC(dalloc(&c->slabs, c->slab_floats));
         HIPC(hipMalloc((void**)&c->d_slab_desc, sizeof(SlabDesc) * 15)); c->slab_desc_n = 0; c->slab_desc_cached_n = -1;
-        HIPC(dalloc(&c->fs_scratch, (size_t)MI_MAX_SEG * 128 * 2048));      // (segments x) FS_GROUPS x 2048 partial column maxima (misc.hip)
+        HIPC(dalloc(&c->fs_scratch, (size_t)MI_MAX_SEG * 128 * 2048));      // (segments x) FS_GROUPS x 2048 partial column maxima (loss.hip)
         HIPC(dalloc(&c->fs_colmax, (size_t)2048)); HIPC(dalloc(&c->fs_arg, (size_t)2048));
         HIPC(dalloc(&c->fs_keys, (size_t)2048)); HIPC(dalloc(&c->fs_keys_local, (size_t)2048)); HIPC(dalloc(&c->d_gpos, (size_t)NB));
         HIPC(hipHostMalloc((void**)&c->h_gpos, (size_t)NB * 4, hipHostMallocDefault));
@@ -692,7 +692,7 @@ void linear_wgrad(mi_ctx* c, const float* dY, const float* X, int relu_x, float*
 
 static void net_heads(mi_ctx* c, int n, int soff = 0) {
     // (tests/test_gpu_lse_value.py::test_update_sized_heads_and_partial_loss_block picks its 1040 samples to be past this threshold)
-    if (c->H == 256 && c->A + 1 <= 16 && n >= 1024) {      // update-sized batches: dedicated kernel (misc.hip heads_fwd_kernel)
+    if (c->H == 256 && c->A + 1 <= 16 && n >= 1024) {      // update-sized batches: dedicated kernel (heads.hip heads_fwd_kernel)
         ProfScope ps(c, PC_GEMM, n, 4.0 * ((double)n * c->H + (double)n * (c->A + 1) + (double)c->H * (c->A + 1)), 2.0 * n * c->H * (c->A + 1));
         launch_heads_fwd(c->feat + (size_t)soff * c->H, c->params + c->wh_off, c->params + c->bh_off, c->hout + (size_t)soff * (c->A + 1), n, c->A + 1, CUR(c));
         return;
@@ -822,7 +822,7 @@ void net_forward(mi_ctx* c, const InputSrc& src, int n, const FwdOpts& o) {
 }
 
 // ---- backward
-// The heads' three gradients from dY (n x (A+1)).  fused (each caller's own condition): one launch (misc.hip heads_bwd_kernel) that also sums
+// The heads' three gradients from dY (n x (A+1)).  fused (each caller's own condition): one launch (heads.hip heads_bwd_kernel) that also sums
 // its slabs unless an armed side stream does (with_reduce false; it forks on done_ev = this launch's own completion); else two GEMMs + a
 // column sum.  prof: only net_backward's launch is bracketed for the profiler.
 static void heads_backward(mi_ctx* c, int n, int relu_mask, bool fused, bool prof, hipStream_t st, bool with_reduce = true, hipEvent_t done_ev = nullptr) {
@@ -848,7 +848,7 @@ static void backward_mlp(mi_ctx* c, int n) {
     issue_grad_allreduce(c, 0, c->n_params, true);
 }
 
-// + fs_coef * d(feature sparsity) / d(block3 output): one element per column (launch_fs_grad, misc.hip)
+// + fs_coef * d(feature sparsity) / d(block3 output): one element per column (launch_fs_grad, loss.hip)
 static void fs_gradient(mi_ctx* c, int n, float* G) {
     if (c->fs_grad_coef == 0.f) return;
     if (c->fs_global_apply) { if (n > 0) launch_fs_apply_keys(G, c->bf, 2048, c->fs_keys, c->fs_keys_local, c->fs_arg, c->fs_grad_coef, CUR(c)); }      // the column's winner among the ranks
@@ -1164,7 +1164,7 @@ static int group_issue(mi_ctx* c, int g, const GroupJob& j) {
             while (clk() < start) __builtin_ia32_pause();
         }
         // page-locked, device-visible frames are PULLED by a kernel on the group's stream: a DMA copy in front of the first conv costs the
-        // hand-over from the compute queue to the copy engine and back on top of the transfer (misc.hip pull_i32_kernel)
+        // hand-over from the compute queue to the copy engine and back on top of the transfer (xfer.hip pull_i32_kernel)
         if (j.pull) launch_pull_bytes(j.frames, dst, j.bytes, st);
         else HIPC(hipMemcpyAsync(dst, j.frames, j.bytes, hipMemcpyHostToDevice, st));
     }
@@ -1176,7 +1176,7 @@ static int group_issue(mi_ctx* c, int g, const GroupJob& j) {
     net_forward(c, src, ng, {.heads = false, .soff = e0});
     const float* hin = c->feat + (size_t)e0 * c->H;          // what the heads read: the embedder output, or h' of a GRU context
     if (c->gru_on) {
-        // the GRU cell as ONE launch (misc.hip gru_step_kernel): input state from hidden-ring slot t (mi_rec_begin's upload at t == 0, else
+        // the GRU cell as ONE launch (gru_cell.hip gru_step_kernel): input state from hidden-ring slot t (mi_rec_begin's upload at t == 0, else
         // step t-1's output), masked by the group's done (mi_rec_begin's at t == 0, else the copy above); h' -> h_state rows, and slot t+1
         // unless this is the bootstrap step.  The heads read h' from h_state (the cell cannot overwrite feat, which its other workgroups read).
         const size_t H = c->H;

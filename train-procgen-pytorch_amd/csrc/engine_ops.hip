@@ -327,7 +327,7 @@ int mi_debug_philox(mi_ctx* c, const uint32_t* ctr_key6, int32_t n, uint32_t* ou
     return 0;
 }
 
-// The fused GRU step of the pipelined rollout (misc.hip gru_step_kernel) on caller data, for tests: n rows, width H (any multiple of 64 up
+// The fused GRU step of the pipelined rollout (gru_cell.hip gru_step_kernel) on caller data, for tests: n rows, width H (any multiple of 64 up
 // to 512, independent of the context's), weights in nn.GRU's layout.  h_out = h' (and h_copy = the kernel's second copy of it, if not null).
 int mi_debug_gru_step(mi_ctx* c, int32_t n, int32_t H, const float* x, const float* h, const float* done, const float* w_ih, const float* w_hh,
                       const float* b_ih, const float* b_hh, float* h_out, float* h_copy) {

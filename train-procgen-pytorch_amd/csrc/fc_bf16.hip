@@ -7,21 +7,17 @@
 //   TN kernel : gW[M][N] += A[K][M]^T * relu(B[K][N])   (weight gradient; both operands K(=batch)-major in memory ->
 //               ds_read_b64_tr_b16 fragments; split over the batch, slabs summed in fixed order)
 #include "common.h"
+#include "device_util.h"
 #include <mutex>
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
-#define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
-__device__ __forceinline__ unsigned short fc_f2bf(float x) { __bf16 h = (__bf16)x; return __builtin_bit_cast(unsigned short, h); }
 __device__ __forceinline__ unsigned fc_pack2(float lo, float hi) { return mi_pk_bf16(lo, hi); }
 __device__ __forceinline__ unsigned fc_relu2(unsigned w) { const unsigned neg = (w >> 15) & 0x00010001u; return w & ~(neg * 0xFFFFu); }
 
 __global__ void fc_pack_kernel(const float* __restrict__ w, unsigned short* __restrict__ wp, unsigned short* __restrict__ wt, int N, int K) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N * K) return;
-    const unsigned short h = fc_f2bf(w[e]);
+    const unsigned short h = f2bf(w[e]);
     wp[e] = h;                                   // [n][k]
     wt[(long long)(e % K) * N + e / K] = h;      // [k][n]
 }

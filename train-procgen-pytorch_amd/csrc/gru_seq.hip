@@ -19,9 +19,9 @@
 // A row's numbers depend on that row's inputs only -- every output element is one lane's accumulator over a fixed k order -- so they
 // do not change with n, with the row's tile or with its neighbours.
 #include "common.h"
+#include "device_util.h"
 #include <mutex>
 
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 __device__ __forceinline__ float gru_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
 

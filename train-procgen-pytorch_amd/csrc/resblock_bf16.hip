@@ -13,32 +13,17 @@
 // MFMA operand order as in conv_bf16.hip: filter rows = A, pixels = B, so a lane owns 4 consecutive channels of a
 // pixel and every global / LDS access of the epilogues is an 8-byte word.
 #include "common.h"
+#include "device_util.h"
 #include <hip/hip_ext.h>
 #include <mutex>
 #include <type_traits>
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-#define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
-__device__ __forceinline__ unsigned short rb_f2bf(float x) { __bf16 h = (__bf16)x; return __builtin_bit_cast(unsigned short, h); }
-// ReLU of two packed bf16 as a signed 16-bit max with 0: one v_pk_max_i16.  Every half with its sign bit set (-0 and negative NaNs included)
-// becomes +0, every other half keeps its bits -- the same bits for every input as the shift / mask / multiply form this replaces (4 instructions).
-typedef short rb_s16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned rb_relu2(unsigned w) {
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(rb_s16x2, w), (rb_s16x2){0, 0}));
-}
-__device__ __forceinline__ float rb_lane(uint2 w, int r) {          // bf16 element r (0..3) of an 8-byte word, widened
-    const unsigned u = (r >> 1) ? w.y : w.x;
-    return (r & 1) ? __uint_as_float(u & 0xffff0000u) : __uint_as_float(u << 16);
-}
 // bf16 element r of an 8-byte word is > 0, tested on the bits without widening: the high half of a dword is positive and non-zero <=> the
-// dword as int32 >= 0x10000; the low half is a signed 16-bit compare.  The same truth as rb_lane(w, r) > 0.f for every finite value, +-0 and
+// dword as int32 >= 0x10000; the low half is a signed 16-bit compare.  The same truth as mi_bf16x4_lane(w, r) > 0.f for every finite value, +-0 and
 // +-inf (denormals are kept in this build: float_denorm_mode_32 = 3); only a positive NaN, which the float compare calls false, differs.
 __device__ __forceinline__ bool rb_pos(uint2 w, int r) {
     const unsigned u = (r >> 1) ? w.y : w.x;
     return (r & 1) ? (int)u >= 0x10000 : (short)(unsigned short)u > (short)0;
-}
-__device__ __forceinline__ uint2 rb_pack(const float (&v)[4]) {
-    return (uint2){mi_pk_bf16(v[0], v[1]), mi_pk_bf16(v[2], v[3])};
 }
 
 #ifndef RB_ROWPAD8
@@ -105,7 +90,7 @@ __device__ __forceinline__ void rb_conv(const unsigned short* s_src, const unsig
             av[mt] = *(const bf16x8*)(s_src + abase[mt] + koff[m]);
             if (RELU_A) {                                   // the image holds raw values (they also serve as the skip connection)
                 const uint4 u = __builtin_bit_cast(uint4, av[mt]);
-                av[mt] = __builtin_bit_cast(bf16x8, (uint4){rb_relu2(u.x), rb_relu2(u.y), rb_relu2(u.z), rb_relu2(u.w)});
+                av[mt] = __builtin_bit_cast(bf16x8, (uint4){mi_relu_bf16x2(u.x), mi_relu_bf16x2(u.y), mi_relu_bf16x2(u.z), mi_relu_bf16x2(u.w)});
             }
         }
 #pragma unroll
@@ -170,7 +155,7 @@ __global__ __launch_bounds__(C::NT) void resblock_bf16_kernel(ResblockArgs a) {
             if (e < C::NSRC) {
                 const int c8 = e % C::C8, px = (e / C::C8) % C::HW, rr = e / (C::C8 * C::HW);      // rr = img * XR + r
                 uint4 v = regs[k];
-                if (!BWD) { v.x = rb_relu2(v.x); v.y = rb_relu2(v.y); v.z = rb_relu2(v.z); v.w = rb_relu2(v.w); }
+                if (!BWD) { v.x = mi_relu_bf16x2(v.x); v.y = mi_relu_bf16x2(v.y); v.z = mi_relu_bf16x2(v.z); v.w = mi_relu_bf16x2(v.w); }
                 *(uint4*)(s_x + (rr * C::P + px + 1) * C::S + c8 * 8) = v;
             }
         }
@@ -216,12 +201,12 @@ __global__ __launch_bounds__(C::NT) void resblock_bf16_kernel(ResblockArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         v[r] = acc[mt][nb][r] + b1r[nb][r];
-                        if (BWD) v[r] = rb_lane(e_m[mt][nb], r) > 0.f ? v[r] : 0.f;
+                        if (BWD) v[r] = mi_bf16x4_lane(e_m[mt][nb], r) > 0.f ? v[r] : 0.f;
                     }
-                    uint2 raw = rb_pack(v);
+                    uint2 raw = mi_pk_bf16x4(v);
                     if (!inimg[mt]) raw = (uint2){0u, 0u};                          // outside the image: the second conv's zero padding
                     if (a.a_out && owned[mt]) *(uint2*)(a.a_out + goff[mt] + nb * 16) = raw;
-                    *(uint2*)(s_y + ybase[mt] + nb * 16) = BWD ? raw : (uint2){rb_relu2(raw.x), rb_relu2(raw.y)};
+                    *(uint2*)(s_y + ybase[mt] + nb * 16) = BWD ? raw : (uint2){mi_relu_bf16x2(raw.x), mi_relu_bf16x2(raw.y)};
                 }
             }
         }
@@ -263,10 +248,10 @@ __global__ __launch_bounds__(C::NT) void resblock_bf16_kernel(ResblockArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         v[r] = acc[mt][nb][r] + b2r[nb][r];
-                        if (BWD) v[r] = rb_lane(e_m[mt][nb], r) > 0.f ? v[r] : 0.f;
-                        v[r] += rb_lane(e_res[mt][nb], r);
+                        if (BWD) v[r] = mi_bf16x4_lane(e_m[mt][nb], r) > 0.f ? v[r] : 0.f;
+                        v[r] += mi_bf16x4_lane(e_res[mt][nb], r);
                     }
-                    *(uint2*)(a.y_out + goff[mt] + nb * 16) = rb_pack(v);
+                    *(uint2*)(a.y_out + goff[mt] + nb * 16) = mi_pk_bf16x4(v);
                 }
             }
         }
@@ -430,9 +415,9 @@ __global__ __launch_bounds__(C::NT) void resblock_pair_bf16_kernel(ResblockPairA
                         const f32x4 bq = *(const f32x4*)(s_b + (2 * st) * C::C + nb * 16 + kq * 4);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] = acc[mt][nb][r] + bq[r];
-                        const uint2 raw = rb_pack(v);
+                        const uint2 raw = mi_pk_bf16x4(v);
                         if (a_out && on) *(uint2*)(a_out + base + poff[mt] + nb * 16) = raw;
-                        *(uint2*)(s_y + abase[mt] + CENTER + eq + nb * 16) = (uint2){rb_relu2(raw.x), rb_relu2(raw.y)};
+                        *(uint2*)(s_y + abase[mt] + CENTER + eq + nb * 16) = (uint2){mi_relu_bf16x2(raw.x), mi_relu_bf16x2(raw.y)};
                     }
                 }
             }
@@ -451,8 +436,8 @@ __global__ __launch_bounds__(C::NT) void resblock_pair_bf16_kernel(ResblockPairA
                         const f32x4 bq = *(const f32x4*)(s_b + (2 * st + 1) * C::C + nb * 16 + kq * 4);
                         const uint2 sk = *(const uint2*)(s_x + abase[mt] + CENTER + eq + nb * 16);      // skip connection: this stage's raw input
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = acc[mt][nb][r] + bq[r] + rb_lane(sk, r);
-                        const uint2 raw = rb_pack(v);
+                        for (int r = 0; r < 4; ++r) v[r] = acc[mt][nb][r] + bq[r] + mi_bf16x4_lane(sk, r);
+                        const uint2 raw = mi_pk_bf16x4(v);
                         if (y_out && on) *(uint2*)(y_out + base + poff[mt] + nb * 16) = raw;
                         if (st == 0) *(uint2*)(s_x + abase[mt] + CENTER + eq + nb * 16) = raw;      // res2's input (raw: conv operand ReLU'd on read, skip as is)
                     }
@@ -540,7 +525,7 @@ __global__ __launch_bounds__(512, 2) void resblock_pair32r_bf16_kernel(ResblockP
         bf16x8 av[2][5];
         auto rd = [&](int q, int m) {
             bf16x8 v = *(const bf16x8*)(s_src + org[q] + kq * 8 + koffc(m));
-            if (relu) { const uint4 u = __builtin_bit_cast(uint4, v); v = __builtin_bit_cast(bf16x8, (uint4){rb_relu2(u.x), rb_relu2(u.y), rb_relu2(u.z), rb_relu2(u.w)}); }
+            if (relu) { const uint4 u = __builtin_bit_cast(uint4, v); v = __builtin_bit_cast(bf16x8, (uint4){mi_relu_bf16x2(u.x), mi_relu_bf16x2(u.y), mi_relu_bf16x2(u.z), mi_relu_bf16x2(u.w)}); }
             return v;
         };
 #pragma unroll
@@ -595,9 +580,9 @@ __global__ __launch_bounds__(512, 2) void resblock_pair32r_bf16_kernel(ResblockP
                         float v[4];
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] = acc[q2][nb][r] + bq[0][nb][r];
-                        const uint2 raw = rb_pack(v);
+                        const uint2 raw = mi_pk_bf16x4(v);
                         if (a_out && (C::NIMG == 1 || pl[q2] / (C::HW * C::HW) < left)) *(uint2*)(a_out + base + (long long)pl[q2] * C::C + nb * 16 + kq * 4) = raw;
-                        *(uint2*)(s_mid + org[q2] + CENTER + nb * 16 + kq * 4) = (uint2){rb_relu2(raw.x), rb_relu2(raw.y)};
+                        *(uint2*)(s_mid + org[q2] + CENTER + nb * 16 + kq * 4) = (uint2){mi_relu_bf16x2(raw.x), mi_relu_bf16x2(raw.y)};
                     }
             }
         }
@@ -621,8 +606,8 @@ __global__ __launch_bounds__(512, 2) void resblock_pair32r_bf16_kernel(ResblockP
                     for (int nb = 0; nb < 2; ++nb) {
                         float v[4];
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = acc[q2][nb][r] + bq[1][nb][r] + rb_lane(sk[q2][nb], r);
-                        const uint2 raw = rb_pack(v);
+                        for (int r = 0; r < 4; ++r) v[r] = acc[q2][nb][r] + bq[1][nb][r] + mi_bf16x4_lane(sk[q2][nb], r);
+                        const uint2 raw = mi_pk_bf16x4(v);
                         if (y_out && (C::NIMG == 1 || pl[q2] / (C::HW * C::HW) < left)) *(uint2*)(y_out + base + (long long)pl[q2] * C::C + nb * 16 + kq * 4) = raw;
                         if (role_a) *(uint2*)(s_nxt + org[q2] + CENTER + nb * 16 + kq * 4) = raw;
                     }
@@ -665,8 +650,6 @@ static void launch_rbp_t(const ResblockPairArgs& a, hipStream_t st) {
 // one slab per workgroup and layer; bias gradients = MFMA against ones.
 // One kernel per shape: resblock_bwd_full16d_bf16_kernel (16 channels @32x32, the largest share of the update's HBM
 // traffic), resblock_bwd_full32s_bf16_kernel (32 @16x16), resblock_bwd_full32q_bf16_kernel (32 @8x8).
-typedef short rb_s16x4 __attribute__((ext_vector_type(4)));
-typedef rb_s16x4 __attribute__((address_space(3))) * rb_lds_s16x4_ptr;
 
 struct RbFullArgs {
     const unsigned short *dy, *a_fwd, *x_fwd;   // bf16 NHWC [n][32][32][16]
@@ -802,7 +785,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
     };
     auto relu8 = [](bf16x8 v) {
         const uint4 u = __builtin_bit_cast(uint4, v);
-        return __builtin_bit_cast(bf16x8, (uint4){rb_relu2(u.x), rb_relu2(u.y), rb_relu2(u.z), rb_relu2(u.w)});
+        return __builtin_bit_cast(bf16x8, (uint4){mi_relu_bf16x2(u.x), mi_relu_bf16x2(u.y), mi_relu_bf16x2(u.z), mi_relu_bf16x2(u.w)});
     };
     // weight gradient of one layer over this wave's NR consecutive pixel rows: d = output-gradient tile (row offset d_row), b = RAW input tile
     // Conv2's weight gradient (phase 1) issues the NEXT item's row DMAs between its MFMA groups, a few per pixel row -- issued back to
@@ -817,8 +800,8 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
 #pragma unroll
         for (int h = 0; h < 2; ++h) ocol[h] = (16 * (kq >> 1) + 8 * h + 4 * (kq & 1) + rq) * C::S + 4 * cp;
         auto tr = [&](const unsigned short* base, int off) {
-            const rb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(base + ocol[0] + off));
-            const rb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(base + ocol[1] + off));
+            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(base + ocol[0] + off));
+            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(base + ocol[1] + off));
             return (bf16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
         };
         bf16x8 dd[C::NR];
@@ -902,7 +885,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
                     float v[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = rb_pos(mk[q], r) ? acc[q][r] : 0.f;
-                    const uint2 raw = rb_pack(v);
+                    const uint2 raw = mi_pk_bf16x4(v);
                     *(uint2*)(s_y + yb[q]) = raw;
                     if (a.da_out) {
                         const int mt = g0 + q < C::MT1 ? g0 + q : C::MT1 - 1;
@@ -944,8 +927,8 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full16d_bf16_kernel(RbFul
                     const int oy = ry0 + 2 * (g0 + q);
                     float v[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = (rb_pos(mk[q], r) ? acc[q][r] : 0.f) + rb_lane(sk[q], r);
-                    *(uint2*)(a.dx_out + ((img * C::HW + ty0 + oy) * C::HW + px) * C::C + kq * 4) = rb_pack(v);
+                    for (int r = 0; r < 4; ++r) v[r] = (rb_pos(mk[q], r) ? acc[q][r] : 0.f) + mi_bf16x4_lane(sk[q], r);
+                    *(uint2*)(a.dx_out + ((img * C::HW + ty0 + oy) * C::HW + px) * C::C + kq * 4) = mi_pk_bf16x4(v);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -1165,8 +1148,8 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32s_bf16_kernel(RbFul
         // address is affine in t, and the second row is the first + 8 pixels
         auto tr = [&](int base, int off) {
             const unsigned short* p = smem_h + base + t * (2 * C::P * C::S) + off;
-            const rb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)p);
-            const rb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(p + 8 * C::S));
+            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)p);
+            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p + 8 * C::S));
             return (bf16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
         };
         // all operand reads of the step go out before its first MFMA: with one column's read in flight the MFMA stream runs at the
@@ -1198,8 +1181,8 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32s_bf16_kernel(RbFul
                 const int ok = o + k * (NT2 / 64) * C::P * C::S;
                 const uint4 va = __builtin_bit_cast(uint4, st[22 + KX2 + k]), vp = __builtin_bit_cast(uint4, st[22 + KX2 + KA2 + k]);
                 *(uint4*)(s_x + ok + 2 * C::P * C::S) = __builtin_bit_cast(uint4, st[22 + k]);
-                *(uint4*)(s_a + ok + C::P * C::S) = (uint4){rb_relu2(va.x), rb_relu2(va.y), rb_relu2(va.z), rb_relu2(va.w)};
-                *(uint4*)(s_p + ok + C::P * C::S) = (uint4){rb_relu2(vp.x), rb_relu2(vp.y), rb_relu2(vp.z), rb_relu2(vp.w)};
+                *(uint4*)(s_a + ok + C::P * C::S) = (uint4){mi_relu_bf16x2(va.x), mi_relu_bf16x2(va.y), mi_relu_bf16x2(va.z), mi_relu_bf16x2(va.w)};
+                *(uint4*)(s_p + ok + C::P * C::S) = (uint4){mi_relu_bf16x2(vp.x), mi_relu_bf16x2(vp.y), mi_relu_bf16x2(vp.z), mi_relu_bf16x2(vp.w)};
             }
         } else if (!conv_role) {
 #pragma unroll
@@ -1213,8 +1196,8 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32s_bf16_kernel(RbFul
                 if (e < C::NA) {
                     const int o = ((e / (4 * C::HW)) * C::P + (e >> 2) % C::HW + 1) * C::S + (e & 3) * 8;
                     const uint4 va = __builtin_bit_cast(uint4, st[22 + KX2 + k]), vp = __builtin_bit_cast(uint4, st[22 + KX2 + KA2 + k]);
-                    *(uint4*)(s_a + o) = (uint4){rb_relu2(va.x), rb_relu2(va.y), rb_relu2(va.z), rb_relu2(va.w)};
-                    *(uint4*)(s_p + o) = (uint4){rb_relu2(vp.x), rb_relu2(vp.y), rb_relu2(vp.z), rb_relu2(vp.w)};
+                    *(uint4*)(s_a + o) = (uint4){mi_relu_bf16x2(va.x), mi_relu_bf16x2(va.y), mi_relu_bf16x2(va.z), mi_relu_bf16x2(va.w)};
+                    *(uint4*)(s_p + o) = (uint4){mi_relu_bf16x2(vp.x), mi_relu_bf16x2(vp.y), mi_relu_bf16x2(vp.z), mi_relu_bf16x2(vp.w)};
                 }
             }
         }
@@ -1248,7 +1231,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32s_bf16_kernel(RbFul
                     float v[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = rb_pos(mk, r) ? acc[nb][r] : 0.f;
-                    const uint2 raw = rb_pack(v);
+                    const uint2 raw = mi_pk_bf16x4(v);
                     *(uint2*)(s_y + yb + nb * 16) = raw;
                     if (a.da_out) {
                         const int gy = ty0 - 1 + ry;
@@ -1290,8 +1273,8 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32s_bf16_kernel(RbFul
                     const uint2 mk = nb ? mk1 : mk0, sk = nb ? sk1 : sk0;
                     float v[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = (rb_pos(mk, r) ? acc[nb][r] : 0.f) + rb_lane(sk, r);
-                    *(uint2*)(a.dx_out + ((img * C::HW + ty0 + oy) * C::HW + px) * C::C + nb * 16 + kq * 4) = rb_pack(v);
+                    for (int r = 0; r < 4; ++r) v[r] = (rb_pos(mk, r) ? acc[nb][r] : 0.f) + mi_bf16x4_lane(sk, r);
+                    *(uint2*)(a.dx_out + ((img * C::HW + ty0 + oy) * C::HW + px) * C::C + nb * 16 + kq * 4) = mi_pk_bf16x4(v);
                 }
             }
         } else {
@@ -1433,8 +1416,8 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32q_bf16_kernel(RbFul
         // The step only adds a constant to the lane's base, and the second row is the tile row below the first.
         auto tr = [&](int base, int off) {
             const unsigned short* p = smem_h + base + ((t >> 1) * C::R + 4 * (t & 1)) * C::P * C::S + off;
-            const rb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)p);
-            const rb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((rb_lds_s16x4_ptr)(p + C::P * C::S));
+            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)p);
+            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p + C::P * C::S));
             return (bf16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
         };
         bf16x8 d[2], b[QM];
@@ -1467,8 +1450,8 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32q_bf16_kernel(RbFul
                 const uint4 vx = on ? __builtin_bit_cast(uint4, st[22 + k]) : z, va = on ? __builtin_bit_cast(uint4, st[22 + C::KW + k]) : z,
                             vp = on ? __builtin_bit_cast(uint4, st[22 + 2 * C::KW + k]) : z;
                 *(uint4*)(s_x + o) = vx;
-                *(uint4*)(s_a + o) = (uint4){rb_relu2(va.x), rb_relu2(va.y), rb_relu2(va.z), rb_relu2(va.w)};
-                *(uint4*)(s_p + o) = (uint4){rb_relu2(vp.x), rb_relu2(vp.y), rb_relu2(vp.z), rb_relu2(vp.w)};
+                *(uint4*)(s_a + o) = (uint4){mi_relu_bf16x2(va.x), mi_relu_bf16x2(va.y), mi_relu_bf16x2(va.z), mi_relu_bf16x2(va.w)};
+                *(uint4*)(s_p + o) = (uint4){mi_relu_bf16x2(vp.x), mi_relu_bf16x2(vp.y), mi_relu_bf16x2(vp.z), mi_relu_bf16x2(vp.w)};
             }
         }
         __syncthreads();
@@ -1500,7 +1483,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32q_bf16_kernel(RbFul
                     float v[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = rb_pos(mk, r) ? acc[nb][r] : 0.f;
-                    const uint2 raw = rb_pack(v);
+                    const uint2 raw = mi_pk_bf16x4(v);
                     *(uint2*)(s_y + yb + nb * 16) = raw;
                     if (a.da_out) {
                         const int pl = t * 16 + i;
@@ -1543,8 +1526,8 @@ __global__ __launch_bounds__(512, 2) void resblock_bwd_full32q_bf16_kernel(RbFul
                         const uint2 mk = nb ? mk1 : mk0, sk = nb ? sk1 : sk0;
                         float v[4];
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = (rb_pos(mk, r) ? acc[nb][r] : 0.f) + rb_lane(sk, r);
-                        *(uint2*)(a.dx_out + ((long long)img0 * 64 + pl) * C::C + nb * 16 + kq * 4) = rb_pack(v);
+                        for (int r = 0; r < 4; ++r) v[r] = (rb_pos(mk, r) ? acc[nb][r] : 0.f) + mi_bf16x4_lane(sk, r);
+                        *(uint2*)(a.dx_out + ((long long)img0 * 64 + pl) * C::C + nb * 16 + kq * 4) = mi_pk_bf16x4(v);
                     }
                 }
             }

@@ -14,20 +14,10 @@
 // pool; conv1 output and block output -> bf16), same first-maximum pooling on order-preserving keys -- the outputs are bit-identical
 // (tests/test_gpu_bf16.py::test_fused_rollout_tail_equals_the_four_launches).  Inference only: nothing but the block-3 output is stored.
 #include "common.h"
+#include "device_util.h"
 #include <mutex>
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short rt_s16x2 __attribute__((ext_vector_type(2)));
-#define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 __device__ __forceinline__ unsigned rt_relu2(unsigned w) { const unsigned neg = (w >> 15) & 0x00010001u; return w & ~(neg * 0xFFFFu); }
-__device__ __forceinline__ unsigned rt_relu2_max(unsigned w) {
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(rt_s16x2, w), (rt_s16x2){0, 0}));
-}
-__device__ __forceinline__ float rt_lane(uint2 w, int r) {
-    const unsigned u = (r >> 1) ? w.y : w.x;
-    return (r & 1) ? __uint_as_float(u & 0xffff0000u) : __uint_as_float(u << 16);
-}
-__device__ __forceinline__ uint2 rt_pack(const float (&v)[4]) { return (uint2){mi_pk_bf16(v[0], v[1]), mi_pk_bf16(v[2], v[3])}; }
 
 #ifndef RT_NT
 #define RT_NT 512           // threads per workgroup (= per image).  1024 (one 16x16 pixel tile per wave, 4 waves per SIMD) needs <= 128
@@ -79,7 +69,7 @@ __device__ __forceinline__ void rt_conv(const unsigned short* s_src, const unsig
             av[mt] = *(const bf16x8*)(s_src + abase[mt] + koff(m));
             if (RELU_A) {
                 const uint4 u = __builtin_bit_cast(uint4, av[mt]);
-                av[mt] = __builtin_bit_cast(bf16x8, (uint4){rt_relu2_max(u.x), rt_relu2_max(u.y), rt_relu2_max(u.z), rt_relu2_max(u.w)});
+                av[mt] = __builtin_bit_cast(bf16x8, (uint4){mi_relu_bf16x2(u.x), mi_relu_bf16x2(u.y), mi_relu_bf16x2(u.z), mi_relu_bf16x2(u.w)});
             }
         }
         const bf16x8 b0 = *(const bf16x8*)(s_w + bbase + m * 32), b1 = *(const bf16x8*)(s_w + bbase + 16 * WS + m * 32);
@@ -98,7 +88,7 @@ __device__ __forceinline__ f32x4 rt_conv1(const unsigned short* s_src, const uns
         bf16x8 av = *(const bf16x8*)(s_src + abase + koff(m));
         if (RELU_A) {
             const uint4 u = __builtin_bit_cast(uint4, av);
-            av = __builtin_bit_cast(bf16x8, (uint4){rt_relu2_max(u.x), rt_relu2_max(u.y), rt_relu2_max(u.z), rt_relu2_max(u.w)});
+            av = __builtin_bit_cast(bf16x8, (uint4){mi_relu_bf16x2(u.x), mi_relu_bf16x2(u.y), mi_relu_bf16x2(u.z), mi_relu_bf16x2(u.w)});
         }
         acc = MFMA_BF16(*(const bf16x8*)(s_w + bbase + m * 32), av, acc);
     }
@@ -232,7 +222,7 @@ __global__ __launch_bounds__(rt::NT) void rollout_tail_bf16_kernel(RolloutTailAr
                         float v[4];
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] = acc[mt][nb][r] + bq[r];
-                        const uint2 raw = rt_pack(v);
+                        const uint2 raw = mi_pk_bf16x4(v);
                         *(uint2*)(s_y + cen[mt] + nb * 16) = (uint2){rt_relu2(raw.x), rt_relu2(raw.y)};
                     }
                 bank_step(k1);
@@ -246,8 +236,8 @@ __global__ __launch_bounds__(rt::NT) void rollout_tail_bf16_kernel(RolloutTailAr
                         const uint2 sk = *(const uint2*)(s_x + cen[mt] + nb * 16);
                         float v[4];
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = acc[mt][nb][r] + bq[r] + rt_lane(sk, r);
-                        *(uint2*)(s_x + cen[mt] + nb * 16) = rt_pack(v);           // raw: the next conv applies the ReLU on its operand reads
+                        for (int r = 0; r < 4; ++r) v[r] = acc[mt][nb][r] + bq[r] + mi_bf16x4_lane(sk, r);
+                        *(uint2*)(s_x + cen[mt] + nb * 16) = mi_pk_bf16x4(v);           // raw: the next conv applies the ReLU on its operand reads
                     }
                 bank_step(k2);
                 __syncthreads();
@@ -313,7 +303,7 @@ __global__ __launch_bounds__(rt::NT) void rollout_tail_bf16_kernel(RolloutTailAr
                     float v[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = acc[r] + bq[r];
-                    const uint2 raw = rt_pack(v);
+                    const uint2 raw = mi_pk_bf16x4(v);
                     *(uint2*)(s_y8 + cen) = (uint2){rt_relu2(raw.x), rt_relu2(raw.y)};
                 }
                 bank_step(k1);
@@ -324,8 +314,8 @@ __global__ __launch_bounds__(rt::NT) void rollout_tail_bf16_kernel(RolloutTailAr
                     const uint2 sk = *(const uint2*)(s_x8 + cen);
                     float v[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = acc[r] + bq[r] + rt_lane(sk, r);
-                    const uint2 raw = rt_pack(v);
+                    for (int r = 0; r < 4; ++r) v[r] = acc[r] + bq[r] + mi_bf16x4_lane(sk, r);
+                    const uint2 raw = mi_pk_bf16x4(v);
                     if (k2 < 9) *(uint2*)(s_x8 + cen) = raw;
                     else *(uint2*)(a.y + ((long long)img * 64 + pl) * 32 + nb * 16 + kq * 4) = raw;
                 }

@@ -8,10 +8,11 @@
 // device order and permuted at the host boundary, exactly as embedder.fc.weight is (engine.hip to_device_layout, K_FCW).
 //   SAE vector   {W_e [S][2048], b_e [S], W_d [2048][S], b_d [2048]}
 //   probe vector {W [(A+1)][S] = fc_policy rows then the fc_value row, b [A+1]}      (host: fc_policy.weight, .bias, fc_value.weight, .bias)
-// The GEMMs are the engine's generic fp32-MFMA kernel (misc.hip gemm_kernel).  The forward products never split K (GemmArgs.ws null):
+// The GEMMs are the engine's generic fp32-MFMA kernel (gemm.hip gemm_kernel).  The forward products never split K (GemmArgs.ws null):
 // launch_gemm picks its split from the number of output tiles, i.e. from n, and a row's codes must not depend on n or on its
 // neighbours; without a split a row is one fixed-order sum over K whatever the batch.  The weight gradients (K = n) may split.
 #include "engine_ctx.h"
+#include "device_util.h"
 
 namespace {
 constexpr int D = 2048;            // encoded_dim = latent_dim * 8 * 8 (common/model.py:175)
@@ -53,21 +54,6 @@ static mi_sae* sae_of(const mi_ctx* c) {
 }
 
 // ------------------------------------------------------------------------------------------ kernels
-template <typename T>
-__device__ __forceinline__ T sae_wave_sum(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-// sum over a 256-thread block in a fixed order; valid in every thread
-__device__ __forceinline__ double sae_block_sum(double v, double* sb) {
-    v = sae_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sb[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return sb[0] + sb[1] + sb[2] + sb[3];
-}
-
 // hidden = ReLU(block-3 output) (common/model.py:186-196), fp32, device column order
 __global__ __launch_bounds__(256) void sae_hidden_kernel(const void* p2, int bf16, float* dst, long long n) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -97,7 +83,7 @@ __global__ __launch_bounds__(256) void sae_recon_kernel(float4* rec, const float
         r.x *= scale; r.y *= scale; r.z *= scale; r.w *= scale;
         rec[e] = r;
     }
-    const double t = sae_block_sum(s, sb);
+    const double t = block_sum256(s, sb);
     if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
@@ -134,8 +120,8 @@ __global__ __launch_bounds__(256) void sae_finish_kernel(const double* part, int
     double a = 0.0, k = 0.0;
     for (int i = threadIdx.x; i < nblk; i += 256) a += part[i];
     for (int j = threadIdx.x; j < S; j += 256) k += (double)kl_term[j];
-    a = sae_block_sum(a, sb);
-    k = sae_block_sum(k, sb);
+    a = block_sum256(a, sb);
+    k = block_sum256(k, sb);
     if (threadIdx.x == 0) {
         const float recon = (float)(a * inv_count), kl = (float)k;
         log[0] = recon; log[1] = kl; log[2] = recon + coef * kl;
@@ -170,8 +156,8 @@ __global__ __launch_bounds__(256) void sae_probe_loss_kernel(const float* out, c
         }
         vh = (double)z[A]; vv = (double)value[idx[b]];
     }
-    const double s0 = sae_block_sum(kl, sb), s1 = sae_block_sum(vh, sb), s2 = sae_block_sum(vh * vh, sb), s3 = sae_block_sum(vv, sb),
-                 s4 = sae_block_sum(vv * vv, sb);
+    const double s0 = block_sum256(kl, sb), s1 = block_sum256(vh, sb), s2 = block_sum256(vh * vh, sb), s3 = block_sum256(vv, sb),
+                 s4 = block_sum256(vv * vv, sb);
     if (threadIdx.x == 0) { double* q = part + (long long)blockIdx.x * 5; q[0] = s0; q[1] = s1; q[2] = s2; q[3] = s3; q[4] = s4; }
 }
 // The reference writes value_loss = ((value_hat - value_batch)**2).mean() with value_hat (n,1) and value_batch (n,): the difference
@@ -183,7 +169,7 @@ __global__ __launch_bounds__(256) void sae_probe_finish_kernel(const double* par
     double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     for (int i = threadIdx.x; i < nblk; i += 256)
         for (int q = 0; q < 5; ++q) s[q] += part[(long long)i * 5 + q];
-    for (int q = 0; q < 5; ++q) s[q] = sae_block_sum(s[q], sb);
+    for (int q = 0; q < 5; ++q) s[q] = block_sum256(s[q], sb);
     if (threadIdx.x == 0) {
         const double inv = 1.0 / (double)n, mvh = s[1] * inv, mv = s[3] * inv;
         const float vloss = (float)(s[2] * inv - 2.0 * mvh * mv + s[4] * inv), lloss = (float)(s[0] * inv);
@@ -198,7 +184,7 @@ __global__ __launch_bounds__(256) void sae_probe_value_kernel(const float* out, 
     dY[(long long)b * (A + 1) + A] = (float)(2.0 * ((double)out[(long long)b * (A + 1) + A] - stat[0]) / (double)n);
 }
 
-// clip_grad_norm_ + optim.Adam(eps=1e-5).step() + zero_grad() on one flat vector: misc.hip's adam_kernel with torch's own constants.
+// clip_grad_norm_ + optim.Adam(eps=1e-5).step() + zero_grad() on one flat vector: optim.hip's adam_kernel with torch's own constants.
 // torch computes 1 - beta1 and 1 - beta2 in Python (float64) and hands the kernels the ROUNDED results, 0.1f and 0.001f; adam_kernel
 // subtracts in fp32, 1.f - 0.999f = 0.000999987: exp_avg_sq 1.3e-5 and the step 6.5e-6 (relative) away from torch's -- inside the PPO
 // tests' absolute bounds, 20 x outside this agent's (8 x torch's own fp32 error, tests/test_gpu_sae.py).  The PPO path's kernel stays
@@ -209,7 +195,7 @@ __global__ __launch_bounds__(256) void sae_adam_kernel(float* p, float* g, float
     const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     double t = 0.0;
     for (int q = threadIdx.x & 63; q < 128; q += 64) t += sumsq[q];
-    t = sae_wave_sum(t);
+    t = wave_sum(t);
     const float norm = (float)sqrt(__shfl(t, 0, 64));
     float coef = max_norm / (norm + 1e-6f);
     coef = coef > 1.f ? 1.f : coef;
