@@ -107,7 +107,7 @@ int mi_rollout_step(mi_ctx* ctx, int32_t t, const float* rew_prev, const float* 
 /* ---- pipelined rollout: the same step as mi_rollout_step, per ENV GROUP and split into submit / wait, so that the frame upload and
  *      forward pass of one group run beside the host's env.step of another (agents/ppo.py:225-231 is strictly serial; an env's next
  *      observation depends on its own action only, so G contiguous groups of E/G envs form G independent chains).
- *      mi_rollout_groups(G) (1 <= G <= 4, E % G == 0) creates a stream per group.  mi_rollout_submit(t, g, frames, ...) enqueues on
+ *      mi_rollout_groups(G) (1 <= G <= 4, E % G == 0) gives each group a stream (a lane, below). mi_rollout_submit(t, g, frames, ...) enqueues on
  *      group g's stream: the H2D copy of the group's E/G observations (frames: pinned host memory from mi_host_alloc, valid until the
  *      matching wait; NULL = ring slot t already holds them) into ring slot t, the forward + sample on them, and the store of the
  *      previous step's reward / done of the group (rew_prev / done_prev: E/G floats each, may be NULL at t == 0); it returns at once.
@@ -121,6 +121,13 @@ int mi_rollout_groups(mi_ctx* ctx, int32_t n_groups);
 int mi_rollout_submit(mi_ctx* ctx, int32_t t, int32_t group, const void* frames, size_t bytes, const float* rew_prev,
                       const float* done_prev, uint64_t seed, const float* u);
 int mi_rollout_wait(mi_ctx* ctx, int32_t group, int64_t* act_out, float* logp_out, float* value_out);
+/* The group streams are LANES: at most four streams per process and device, created at the greatest stream priority on first use,
+ * lent to the contexts and destroyed when the last context that holds one is destroyed.  A context with G groups holds G different
+ * lanes for its lifetime; two live contexts hold disjoint lanes as long as their groups number four or fewer in all, beyond that lanes are shared
+ * (still correct: every group orders itself by its own events).  mi_rollout_lane_info reports what the groups of this context run
+ * on: *n = groups with a lane, prio[g] = the stream priority, stream_id[g] = an id of the stream that is equal for two groups (of any
+ * contexts) exactly when they share a lane. */
+int mi_rollout_lane_info(mi_ctx* ctx, int32_t* n, int32_t* prio /* [4] */, uint64_t* stream_id /* [4] */);
 
 /* ---- PPO.predict(obs, hidden, done) on caller data (agents/ppo.py:72-81) when the caller has not said which
  *      storage slot the observation belongs to: obs (E frames / rows) is staged on the device, forward + sample
@@ -372,6 +379,10 @@ int mi_debug_gru_seq(mi_ctx* ctx, int32_t T, int32_t n, int32_t H, const float* 
 /* measurement hook: wall-clock microseconds per policy step of slot t (the step's launches + a stream wait, `iters` times), issued
  * eagerly (mode 0) or as one replay of a hipGraph captured from the same launches (mode 1) */
 int mi_debug_step_latency(mi_ctx* ctx, int32_t t, int32_t iters, int32_t mode, float* us_out);
+/* measurement hook: do the lanes run side by side?  Launches on the stream of every group in `mask` (bit g = group g of this context)
+ * one 64-thread workgroup that executes s_sleep 127 `iters` times (capped at 4096; a fixed trip count, nothing to wait on), waits for
+ * all of them and returns the host wall time from first launch to last completion in microseconds. */
+int mi_debug_lane_probe(mi_ctx* ctx, int32_t mask, int32_t iters, float* usec);
 /* bit 0 set: rollout-sized bf16 inference passes use the separate block-2 / block-3 kernels instead of the fused launch
  * (rollout_bf16.hip) -- the A side of the bit-equality test of the two paths;
  * bit 2 set: a group's frames always go up by DMA copy, never pulled by a kernel (A/B timing);

@@ -7,11 +7,11 @@ key = "Stream_Id" if "Stream_Id" in rows[0] else "Queue_Id"
 by = collections.defaultdict(list)
 for r in rows:
     by[r[key]].append(r)
-streams = [(k, v) for k, v in by.items() if sum(1 for r in v if r["Kernel_Name"].startswith("heads_sample")) > 200]
+streams = [(k, v) for k, v in by.items() if sum(1 for r in v if "heads_sample" in r["Kernel_Name"]) > 200]
 print("streams with a rollout chain:", [(k, len(v)) for k, v in streams], "key", key)
 k, v = streams[0]
 v.sort(key=lambda r: int(r["Start_Timestamp"]))
-idx = [i for i, r in enumerate(v) if r["Kernel_Name"].startswith("heads_sample")]
+idx = [i for i, r in enumerate(v) if "heads_sample" in r["Kernel_Name"]]
 a, b = idx[-150], idx[-149]
 base = int(v[a]["End_Timestamp"])
 for r in v[a + 1:b + 1]:

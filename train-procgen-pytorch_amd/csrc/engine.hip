@@ -12,6 +12,7 @@
 // File map:
 //   engine_ctx.h    mi_ctx and the structs it embeds, the error plumbing (fail, HIPC, ARG, NETCHK, JOIN, CUR), and the declarations of
 //                   the functions of this file that engine_ops.hip calls
+//   lanes.h         which stream an env group of the pipelined rollout runs on: the process-wide lane registry (plain C++, host-tested)
 //   engine.hip      create / destroy, rollout storage, profiler, the network program (forward_* / backward_* per mode), rollout steps and
 //                   env groups, minibatch passes, optimizer, GRU, collectives
 //   engine_ops.hip  mi_op_*, mi_debug_* (but mi_debug_flags: it sets production state) and mi_selftest_mfma: tests and micro-benchmarks only
@@ -28,6 +29,7 @@
 //    9 join, slab sum          the remaining slab sum(s) into the flat gradient
 //   10 mi_optimizer_step       gradient norm + Adam (its own entry point)
 #include "engine_ctx.h"
+#include "lanes.h"
 
 thread_local std::string g_err;
 thread_local hipStream_t tl_stream = nullptr;
@@ -62,7 +64,25 @@ struct GroupWorker {
 static inline char* obs_stage(mi_ctx* c) { return c->stage_frames ? (char*)c->stage_frames : (char*)c->stage_obs; }   // staged observations [NB]
 struct GemmWs { float* p; size_t floats; };
 static inline GemmWs gemm_ws(mi_ctx* c) { return tl_ws ? GemmWs{tl_ws, tl_ws_floats} : GemmWs{c->gemm_ws, c->gemm_ws_floats}; }   // split-K workspace (a group worker: its slice)
-// the first env group's stream when there is one (idle during an update, joined by JOIN(); one hardware queue less in use), else an own stream
+// ---- rollout lanes (lanes.h): one registry per device, streams at the greatest priority the device offers.  The runtime keeps a pool of
+// hardware queues per stream priority; the default stream, torch's streams and every context's own stream live in the normal pool, so
+// the lanes are the only tenants of theirs and four of them sit on four queues even where the normal pool's four are all taken.
+static constexpr int MAX_LANE_DEVICES = 64;
+static LaneRegistry* const g_lanes = new LaneRegistry[MAX_LANE_DEVICES];      // (never destructed: a context may be destroyed during process exit)
+static void* lane_make(int device, int, int* prio) {
+    int dev0 = 0, least = 0, greatest = 0;
+    hipStream_t s = nullptr;
+    if (hipGetDevice(&dev0) != hipSuccess || hipSetDevice(device) != hipSuccess) return nullptr;
+    const bool ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&
+                    hipStreamCreateWithPriority(&s, hipStreamNonBlocking, greatest) == hipSuccess &&
+                    hipStreamGetPriority(s, prio) == hipSuccess;
+    hipSetDevice(dev0);
+    if (!ok && s) { hipStreamDestroy(s); s = nullptr; }
+    return s;
+}
+static void lane_drop(void* s) { hipStreamDestroy((hipStream_t)s); }
+
+// the first env group's lane when there is one (idle during an update, joined by JOIN(); one hardware queue less in use), else an own stream
 static hipStream_t side_stream(mi_ctx* c) {
     hipStream_t ss = (c->n_groups > 0 && c->gs[0]) ? c->gs[0] : c->side_stream;
     if (!ss) { hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking); ss = c->side_stream; }
@@ -204,6 +224,7 @@ int mi_create(const mi_config* cfg, mi_ctx** out) {
             "impala out_dim (output_dim) must be a multiple of 64 in [64, 512]");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(-3, "no HIP device: the MI355X library has no CPU fallback");
+    ARG(cfg->device >= 0 && cfg->device < ndev && cfg->device < MAX_LANE_DEVICES, "device");
     HIPC(hipSetDevice(cfg->device));
     mi_ctx* c = new mi_ctx();
     c->cfg = *cfg;
@@ -359,7 +380,8 @@ int mi_destroy(mi_ctx* c) {
     for (int g = 0; g < mi_ctx::MAX_GROUPS; ++g) if (c->gs[g]) hipStreamSynchronize(c->gs[g]);
     prof_harvest(c);
     hipStreamSynchronize(c->stream);
-    for (int g = 0; g < mi_ctx::MAX_GROUPS; ++g) if (c->gs[g]) { hipStreamDestroy(c->gs[g]); hipEventDestroy(c->ev_fork[g]); hipEventDestroy(c->ev_join[g]); }
+    for (int g = 0; g < mi_ctx::MAX_GROUPS; ++g) if (c->gs[g]) { hipEventDestroy(c->ev_fork[g]); hipEventDestroy(c->ev_join[g]); c->gs[g] = nullptr; }
+    g_lanes[c->cfg.device].give_back(c, lane_drop);      // (waited for above; the streams go when the last holder of the device returns its lanes)
     for (hipEvent_t e : c->prof.pool) hipEventDestroy(e);
     float* fl[] = {c->params, c->grads, c->adam_m, c->adam_v, c->rew, c->done, c->logp, c->adv, c->ret, c->value, c->obsf,
                    c->feat, c->dfeat, c->hout, c->dY, c->GC, c->GP[0], c->GP[1], c->GP[2], c->slabs, c->gemm_ws, c->col_ws,
@@ -1225,15 +1247,26 @@ int mi_rollout_groups(mi_ctx* c, int32_t n_groups) {
     ARG(c->E % n_groups == 0, "n_envs must be divisible by the number of groups");
     for (int g = 0; g < c->n_groups; ++g) ARG(!c->g_busy[g], "a group step is still in flight: mi_rollout_wait it first");
     JOIN(c);
+    void* lane[mi_ctx::MAX_GROUPS]; int prio[mi_ctx::MAX_GROUPS];
+    const int have = [&] { int k = 0; while (k < mi_ctx::MAX_GROUPS && c->gs[k]) ++k; return k; }();
+    if (n_groups > have && !g_lanes[c->cfg.device].borrow(c, n_groups, c->cfg.device, lane_make, lane, prio))
+        return fail(-2, "no stream for an env group (hipStreamCreateWithPriority failed)");
     for (int g = 0; g < n_groups; ++g)
         if (!c->gs[g]) {
-            HIPC(hipStreamCreateWithFlags(&c->gs[g], hipStreamNonBlocking));
+            c->gs[g] = (hipStream_t)lane[g]; c->gs_prio[g] = prio[g];
             HIPC(hipEventCreateWithFlags(&c->ev_fork[g], hipEventDisableTiming));
             HIPC(hipEventCreateWithFlags(&c->ev_join[g], hipEventDisableTiming));
             c->gw[g] = new GroupWorker();
             c->gw[g]->th = std::thread(group_worker_main, c, g);
         }
     c->n_groups = n_groups;
+    return 0;
+}
+
+int mi_rollout_lane_info(mi_ctx* c, int32_t* n, int32_t* prio, uint64_t* stream_id) {
+    ARG(c && n && prio && stream_id, "null");
+    *n = 0;
+    for (int g = 0; g < c->n_groups && c->gs[g]; ++g) { prio[g] = c->gs_prio[g]; stream_id[g] = (uint64_t)(uintptr_t)c->gs[g]; *n = g + 1; }
     return 0;
 }
 

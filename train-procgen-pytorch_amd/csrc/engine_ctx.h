@@ -129,7 +129,8 @@ struct mi_ctx {
     // pipelined rollout (mi_rollout_submit / mi_rollout_wait): contiguous env groups, each on its own stream with its own rows of the
     // activation buffers, so that one group's frame upload + forward runs beside the host's wait for another group's actions
     static constexpr int MAX_GROUPS = 4;
-    int n_groups; hipStream_t main_stream, gs[MAX_GROUPS]; hipEvent_t ev_fork[MAX_GROUPS], ev_join[MAX_GROUPS];
+    // gs[g]: a lane borrowed from the process-wide registry (lanes.h, g_lanes in engine.hip), never a stream of the context's own
+    int n_groups; hipStream_t main_stream, gs[MAX_GROUPS]; int gs_prio[MAX_GROUPS]; hipEvent_t ev_fork[MAX_GROUPS], ev_join[MAX_GROUPS];
     bool g_forked[MAX_GROUPS], g_busy[MAX_GROUPS], g_last[MAX_GROUPS], g_dirty[MAX_GROUPS]; unsigned g_ticket[MAX_GROUPS]; bool groups_live;
     struct GroupWorker* gw[MAX_GROUPS];      // one host thread per group issues that group's copies + launches (a step is ~9 API calls = ~30 us of host time)
     std::atomic<int64_t> copy_slot_ns{0}; double copy_rate_bytes_per_us;      // uploads of the env groups take turns on the PCIe link (group_issue)

@@ -428,6 +428,27 @@ int mi_debug_step_latency(mi_ctx* c, int32_t t, int32_t iters, int32_t mode, flo
     return 0;
 }
 
+// Measurement hook ("Lanes"): do the group streams of this context run side by side?  One 64-thread workgroup per
+// stream in `mask` sleeps a fixed number of times -- no flag, no clock, no memory traffic, so it cannot wait on anything -- and the host
+// times first launch to last completion: one lane's time when the lanes sit on hardware queues of their own, a multiple where they share.
+__global__ void __launch_bounds__(64) lane_probe_kernel(int iters) {
+    for (int i = 0; i < iters; ++i) __builtin_amdgcn_s_sleep(127);
+}
+int mi_debug_lane_probe(mi_ctx* c, int32_t mask, int32_t iters, float* usec) {
+    ARG(c && usec, "null"); JOIN(c);
+    ARG(mask > 0 && mask < (1 << c->n_groups) && iters >= 1, "mask (bits of this context's groups) / iters");
+    for (int g = 0; g < c->n_groups; ++g) ARG(c->gs[g] && !c->g_busy[g], "call mi_rollout_groups first; no group step in flight");
+    if (iters > 4096) iters = 4096;
+    for (int g = 0; g < c->n_groups; ++g) if (mask >> g & 1) HIPC(hipStreamSynchronize(c->gs[g]));
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int g = 0; g < c->n_groups; ++g) if (mask >> g & 1) lane_probe_kernel<<<1, 64, 0, c->gs[g]>>>(iters);
+    for (int g = 0; g < c->n_groups; ++g) if (mask >> g & 1) HIPC(hipStreamSynchronize(c->gs[g]));
+    const auto t1 = std::chrono::steady_clock::now();
+    HIPC(hipGetLastError());
+    *usec = (float)(std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count() / 1e3);
+    return 0;
+}
+
 // Read back what the last training-mode pass (mi_minibatch) left in the activation buffers, as fp32 NHWC: which = 8 * block + k with
 // k = 0 P0 (pooled map), 1 A1, 2 P1, 3 A2, 4 P2 (res1.conv1 out, res1 out, res2.conv1 out, block out), 5 the max-pool arg-max bytes
 // (window position ky*3+kx as float); which = 100: the 256 features.  For teacher-forced backward parity tests.

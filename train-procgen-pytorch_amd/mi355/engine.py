@@ -40,9 +40,9 @@ def lib_path():
 
 EXPORTS = ("mi_last_error mi_create mi_destroy mi_sync mi_host_alloc mi_host_free mi_host_register mi_host_unregister mi_param_count mi_set_params "
            "mi_get_params mi_copy_params mi_get_grads mi_set_adam_state mi_get_adam_state mi_put_obs mi_get_obs mi_put_step "
-           "mi_put_policy_outputs mi_read_field mi_write_field mi_policy_step mi_rollout_step mi_rollout_groups mi_rollout_submit mi_rollout_wait mi_predict_staged mi_value_saliency mi_commit_staged mi_set_gru mi_rec_state mi_get_hidden mi_rec_begin mi_get_hidden_ring mi_forward_rec mi_forward mi_compute_estimates "
+           "mi_put_policy_outputs mi_read_field mi_write_field mi_policy_step mi_rollout_step mi_rollout_groups mi_rollout_lane_info mi_rollout_submit mi_rollout_wait mi_predict_staged mi_value_saliency mi_commit_staged mi_set_gru mi_rec_state mi_get_hidden mi_rec_begin mi_get_hidden_ring mi_forward_rec mi_forward mi_compute_estimates "
            "mi_adv_stats mi_adv_apply mi_minibatch mi_minibatch_multi mi_optimizer_step mi_loss_log_read mi_device_ptr "
-           "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_op_fc_bf16 mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_gru_step mi_debug_step_latency "
+           "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_op_fc_bf16 mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_gru_step mi_debug_step_latency mi_debug_lane_probe "
            "mi_gru_train mi_minibatch_rec mi_get_gru mi_get_gru_grads mi_get_gru_adam_state mi_set_gru_adam_state mi_debug_gru_seq "
            "mi_sae_create mi_sae_destroy mi_sae_param_count mi_sae_set_params mi_sae_get_params mi_sae_get_grads mi_sae_set_adam_state mi_sae_get_adam_state mi_sae_put_ring "
            "mi_sae_get_hidden mi_sae_get_logits mi_sae_step mi_sae_minibatch mi_sae_probe_minibatch mi_sae_optimizer_step mi_sae_debug_forward").split()
@@ -269,6 +269,12 @@ class Engine:
     def rollout_groups(self, n_groups):
         self._chk(self.lib.mi_rollout_groups(self._ctx, C.c_int32(n_groups)))
         self.n_groups = n_groups
+
+    def lane_info(self):
+        """[(stream priority, stream id)] of this engine's env groups; two groups share a lane exactly when their ids are equal"""
+        n, prio, sid = C.c_int32(0), (C.c_int32 * 4)(), (C.c_uint64 * 4)()
+        self._chk(self.lib.mi_rollout_lane_info(self._ctx, C.byref(n), prio, sid))
+        return [(int(prio[g]), int(sid[g])) for g in range(n.value)]
 
     def rollout_submit(self, t, group, frames=None, rew_prev=None, done_prev=None, seed=0, u=None):
         """frames: this group's observations in PINNED memory (Engine.pinned), kept unchanged until rollout_wait(group); None = slot t holds them."""
@@ -737,6 +743,12 @@ class Engine:
         """microseconds per policy step of slot t (launches + stream wait), eager or as a replayed hipGraph of the same launches"""
         us = C.c_float(0)
         self._chk(self.lib.mi_debug_step_latency(self._ctx, C.c_int32(t), C.c_int32(iters), C.c_int32(int(graph)), C.byref(us)))
+        return us.value
+
+    def debug_lane_probe(self, mask, iters):
+        """microseconds from first launch to last completion of one fixed-length sleeping workgroup on each group stream in `mask`"""
+        us = C.c_float(0)
+        self._chk(self.lib.mi_debug_lane_probe(self._ctx, C.c_int32(mask), C.c_int32(iters), C.byref(us)))
         return us.value
 
     def debug_flags(self, flags):
