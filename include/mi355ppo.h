@@ -276,6 +276,38 @@ int mi_sae_optimizer_step(mi_ctx* ctx, int32_t which, float lr, float max_grad_n
 /* test hook: the forward pass of mi_sae_minibatch on ring rows idx -> enc (n x S) and rec (n x 2048, the reference's column order) */
 int mi_sae_debug_forward(mi_ctx* ctx, const int64_t* idx, int32_t n, float* enc_out, float* rec_out);
 
+/* ---- the IPL agent (algo: IPL; reference agents/IPL.py:109-225 with IPLStorage, common/storage.py:279-361) on a plain context: the same
+ *      rings, network passes, clip, Adam and parameter vectors as PPO -- mi_optimizer_step, mi_get/set_params, mi_get/set_adam_state and
+ *      mi_get_grads are reused unchanged.  The loss arithmetic is fp32 in both precision modes.
+ *      mi_ipl_minibatch: one minibatch of IPL.optimize on ring rows idx (flat t*E + e, t < T); nobs is ring row idx + E (slot T is what
+ *      store_last / the bootstrap step wrote).  v = V(obs), nv = V(nobs) with nv[done] = rew[done] (no gradient through those rows),
+ *      modifier = alpha or, with MI_IPL_ENTROPY_MODIFIED, alpha (1 - exp(logp)); pred = modifier logp + v - gamma nv;
+ *      loss = mean((pred - rew)^2) - [MI_IPL_REWARD_INCENTIVE] mean(pred) - [MI_IPL_ADV_INCENTIVE] mean(max_k logp_k) + entropy_coef mean(H).
+ *      Three forward and two backward passes: the gradient reaches the network through obs AND nobs and ACCUMULATES into the flat
+ *      gradient buffer like mi_minibatch's.  n <= max_batch; the means are taken over n_global.  Appends one 8-float record to the loss
+ *      log (mi_loss_log_read), in the order of IPL's summary: {entropy, mutual_info, total, rew_corr, gamma, alpha loss (NaN: the
+ *      temperature is not learned), alpha, mean pred}.  Refused by name: multirank mode != 0 or an armed gradient exchange, a context with
+ *      a GRU set, one created with value_from_logits, n > max_batch.
+ *      mi_ipl_read_pred: pred and the gathered reward of the last mi_ipl_minibatch (IPL.last_predicted_reward / last_reward), n = its size.
+ *      mi_predict_greedy: IPL.predict(obs, greedy=True) (IPL.py:82-94) on E caller observations, staged like mi_predict_staged (so that
+ *      mi_commit_staged can store them): act = the first arg-max of the normalised log-probabilities, its log-prob, the value. */
+enum { MI_IPL_ENTROPY_MODIFIED = 1, MI_IPL_REWARD_INCENTIVE = 2, MI_IPL_ADV_INCENTIVE = 4,
+       MI_IPL_DEBUG_ZERO_OBS_SEED = 256 /* test switch: the obs-side seed dY is zeroed, only the nobs path carries gradient */ };
+typedef struct mi_ipl_hparams {
+    float gamma, alpha, entropy_coef;
+    int32_t flags;         /* MI_IPL_* */
+} mi_ipl_hparams;
+int mi_ipl_minibatch(mi_ctx* ctx, const int64_t* idx, int32_t n, int32_t n_global, const mi_ipl_hparams* hp);
+int mi_ipl_read_pred(mi_ctx* ctx, float* pred_out, float* rew_out, int32_t n);
+int mi_predict_greedy(mi_ctx* ctx, const void* obs, size_t bytes, int64_t* act_out, float* logp_out, float* value_out);
+/* op-level test hook: only the IPL kernels (next value, loss + finaliser, next-side seed) on caller arrays -- hout [n][A+1] of the obs
+ * pass, nv_raw [n] = V(nobs) before the done overwrite, act / rew / done [n].  Out (any may be NULL): rec8 the record, dY [n][A+1] the
+ * obs-side seed, gnext [n] = d loss / d nv (exactly 0 on done rows), pred [n].  n in [1, 65536], A in [1, 16], means over n. */
+int mi_op_ipl_loss(mi_ctx* ctx, int32_t n, int32_t A, const float* hout, const float* nv_raw, const int32_t* act, const float* rew,
+                   const float* done, const mi_ipl_hparams* hp, float* rec8_out, float* dY_out, float* gnext_out, float* pred_out);
+/* op-level test hook: the greedy action of n head rows hout [n][A+1] -> act [n] (lowest index among equal maxima) */
+int mi_op_ipl_greedy(mi_ctx* ctx, int32_t n, int32_t A, const float* hout, int32_t* act_out);
+
 /* ---- data-parallel collectives inside the boundary: RCCL over xGMI, one communicator per context (SURVEY 8(b) mi_allreduce_grads,
  *      8(e) C1-C3).  Rank 0 obtains a 128-byte id (mi_comm_unique_id) and hands it to every rank by any host channel
  *      (mi355/dist.py uses torch.distributed.broadcast_object_list); every rank then calls mi_comm_init(id, rank, world).

@@ -13,6 +13,7 @@ EPISODE_KEYS = ["max_episode_rewards", "mean_episode_rewards", "median_episode_r
 LOSS_KEYS = ["loss_pi", "loss_v", "loss_entropy", "loss_x_entropy", "atn_entropy", "atn_entropy2", "loss_sparsity",
              "loss_feature_sparsity", "loss_total"]
 LOSS_KEYS_PURE = ["loss_pi", "loss_v", "loss_entropy", "loss_x_entropy", "loss_total"]      # algo ppo-pure / espo (common/logger.py:65-66)
+LOSS_KEYS_IPL = ["entropy", "mutual_info", "loss_total", "rew_corr", "gamma", "loss_alpha", "alpha", "pred_reward"]      # algo IPL (common/logger.py:67-69)
 
 
 class _EpisodeTracker:
@@ -55,7 +56,7 @@ class Logger(object):
         self.max_steps = 10 ** 3
         self.train, self.valid = _EpisodeTracker(n_envs), _EpisodeTracker(n_envs)
         self.columns = (["timesteps", "wall_time", "num_episodes"] + EPISODE_KEYS + ["val_" + k for k in EPISODE_KEYS]
-                        + ["ema_rewards"] + (LOSS_KEYS_PURE if algo in ("ppo-pure", "espo") else LOSS_KEYS) + ["learning_rate"])
+                        + ["ema_rewards"] + (LOSS_KEYS_PURE if algo in ("ppo-pure", "espo") else LOSS_KEYS_IPL if algo == "IPL" else LOSS_KEYS) + ["learning_rate"])
         self.rows = []
         self.timesteps = 0
         self.num_episodes = 0

@@ -351,3 +351,52 @@ class SAEStorage(Storage):
         if recurrent:
             raise NotImplementedError("SAEStorage.fetch_train_generator(recurrent=True): the SAE agent is non-recurrent")
         yield from self.minibatch_index_stream(mini_batch_size, False)
+
+
+class IPLStorage(Storage):
+    """IPLStorage (reference: common/storage.py:279-361) on the engine's ring: observations (T + 1 slots), action, reward, done and value.
+    The reference's constructor (no hidden state), ``store(obs, act, rew, done, info, value)`` / ``store_last(obs, value)``, ``fetch_log_data``;
+    ``fetch_train_generator`` yields the reference's 6-tuple ``(obs, nobs, act, done, value, rew)`` as host tensors read back from the
+    device; the agent itself takes ``minibatch_index_stream`` -- the same permutation draw -- and the rows never leave the device."""
+
+    def __init__(self, obs_shape, num_steps, num_envs, device):
+        super().__init__(obs_shape, 0, num_steps, num_envs, device)
+
+    def store(self, obs, act, rew, done, info, value):
+        eng, t = self._eng(), self.step
+        pend = self._pending if self._claim(t, obs) else None
+        if pend is None:
+            self._keep = eng.put_obs(t, as_device_obs(obs, self.arch))
+        if pend is None or pend[2] is not act or pend[4] is not value:
+            eng.put_policy_outputs(t, np.asarray(act), None, np.asarray(value))
+        self._rew[t] = rew
+        self._done[t] = done
+        eng.put_step(t, self._rew[t], self._done[t])
+        self.info_batch.append(info)
+        self._pending = None
+        self.step = (self.step + 1) % self.num_steps
+
+    def store_last(self, last_obs, last_value):
+        eng, T = self._eng(), self.num_steps
+        pend = self._pending if self._claim(T, last_obs) else None
+        if pend is None:
+            self._keep = eng.put_obs(T, as_device_obs(last_obs, self.arch))
+        if pend is None or pend[4] is not last_value:
+            eng.put_policy_outputs(T, None, None, np.asarray(last_value))
+        self._pending = None
+
+    def collate_data(self, indices):
+        """(obs, nobs, act, done, value, rew) of explicit indices (storage.py:320-327), read back from the device."""
+        idx = np.asarray(indices, dtype=np.int64)
+        T, E = self.num_steps, self.num_envs
+        t, e = idx // E, idx % E
+        frames = {int(tt): self._obs_as_ref(int(tt)) for tt in np.unique(np.concatenate([t, t + 1]))}
+        pick = lambda tt: torch.from_numpy(np.stack([frames[int(a)][int(b)] for a, b in zip(tt, e)]))
+        g = lambda f: self._field(f)[:T].reshape(-1)[idx]
+        return pick(t), pick(t + 1), g(M.F_ACT), g(M.F_DONE), g(M.F_VALUE), g(M.F_REW)
+
+    def fetch_train_generator(self, mini_batch_size=None, recurrent=False):
+        if recurrent:
+            raise NotImplementedError("IPLStorage.fetch_train_generator(recurrent=True): the IPL agent is non-recurrent")
+        for idx in self.minibatch_index_stream(mini_batch_size, False):
+            yield self.collate_data(idx)

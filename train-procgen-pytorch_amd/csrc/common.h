@@ -211,6 +211,30 @@ void launch_fs_apply_keys(void* Gd, int bf16, int d, const long long* keys, cons
 void launch_fs_from_keys(const long long* keys, int d, float* fs_out, hipStream_t st);
 void launch_fs_grad(const void* x, int bf16, int n, int d, const float* part, int G, void* Gd, float fs_coef, float* colmax, int* arg, hipStream_t st);
 
+// ---------------------------------------------------------------- ipl.hip: the IPL loss (agents/IPL.py), greedy action
+constexpr int IPL_SUMS = 8;           // scalar columns of a block partial row (then A columns of sum p_k)
+// per-sample scalars are gathered through idx (flat index t*E+e; null: row s itself) from the (T,E) rollout arrays
+struct IplArgs {
+    const float* hout;        // [n][A+1] of the obs pass
+    const int32_t* idx;       // [n] or null
+    const int32_t* act; const float* rew; const float* done;
+    float* nv;                // [n] next values after the done overwrite
+    float* dY;                // [n][A+1] obs-side seed
+    float* g_next;            // [n] d loss / d nv (0 on done rows)
+    float *pred, *rew_out;    // [n] predicted reward and the gathered reward (last_predicted_reward / last_reward)
+    double* partial;          // [nblk][IPL_SUMS + A]
+    int n, A;
+    float inv_n_global, gamma, alpha, entropy_coef;
+    int entropy_modified, reward_incentive, adv_incentive, zero_obs_seed;
+};
+int  ipl_blocks(int n);
+int  ipl_partial_cols(int A);
+void launch_ipl_next_value(const IplArgs& a, const float* v_src, int v_stride, int v_off, hipStream_t st);
+void launch_ipl_loss(const IplArgs& a, float* rec8, hipStream_t st);          // loss kernel + finaliser -> one 8-float record
+void launch_ipl_next_seed(const float* g_next, float* dY, int n, int A, hipStream_t st);
+void launch_ipl_shift_idx(const int32_t* idx, int32_t* idx2, int n, int shift, hipStream_t st);
+void launch_ipl_greedy(const float* hout, int n, int A, int32_t* act, float* logp, float* value, hipStream_t st);
+
 // ---------------------------------------------------------------- estimates.hip: GAE, advantage normalisation
 void launch_gae(const float* rew, const float* done, const float* value, float* adv, float* ret, int T, int E,
                 float gamma, float lmbda, int use_gae, hipStream_t st);

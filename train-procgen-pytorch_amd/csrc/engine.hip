@@ -402,6 +402,7 @@ int mi_destroy(mi_ctx* c) {
     if (c->h_ring) hipFree(c->h_ring); if (c->h_rec_stage) hipHostFree(c->h_rec_stage); if (c->ev_rec) hipEventDestroy(c->ev_rec);
     { float* gt[] = {c->gru_g, c->gru_m, c->gru_v, c->rec_x, c->rec_gi, c->rec_sv, c->rec_dgi, c->rec_dgh, c->rec_hm, c->rec_mask, c->rec_h0}; for (float* q : gt) if (q) hipFree(q); }
     if (c->gru_sumsq) hipFree(c->gru_sumsq);
+    if (c->ipl_idx2) { hipFree(c->ipl_idx2); hipFree(c->ipl_nv); hipFree(c->ipl_gnext); hipFree(c->ipl_pred); hipFree(c->ipl_rew); hipFree(c->ipl_partial); }
     hipFree(c->act); hipFree(c->adv_stats); hipFree(c->d_idx); hipFree(c->sumsq);
     if (c->fs_colmax) hipFree(c->fs_colmax); if (c->fs_arg) hipFree(c->fs_arg);
     if (c->fs_keys) hipFree(c->fs_keys); if (c->fs_keys_local) hipFree(c->fs_keys_local); if (c->d_gpos) hipFree(c->d_gpos); if (c->h_gpos) hipHostFree(c->h_gpos);
@@ -1349,6 +1350,23 @@ int mi_predict_staged(mi_ctx* c, const void* obs, size_t bytes, uint64_t seed, u
     return 0;
 }
 
+// IPL.predict(obs, greedy=True) (agents/IPL.py:82-94): mi_predict_staged with the first arg-max in place of the sampler
+int mi_predict_greedy(mi_ctx* c, const void* obs, size_t bytes, int64_t* act_out, float* logp_out, float* value_out) {
+    ARG(c && obs, "null"); JOIN(c);
+    ARG(!c->gru_on, "mi_predict_greedy: a recurrent context (mi_set_gru) is not supported"); ARG(!c->lse, "mi_predict_greedy: value_from_logits is not supported");
+    const int E = c->E;
+    ARG(bytes == (size_t)E * c->obs_bytes_per_env, "obs byte count != E * bytes_per_env");
+    void* stage = obs_stage(c);
+    HIPC(hipMemcpyAsync(stage, obs, bytes, hipMemcpyHostToDevice, c->stream));
+    InputSrc src{stage, nullptr, 0};
+    net_forward(c, src, E, {});
+    launch_ipl_greedy(c->hout, E, c->A, c->s_act, c->s_logp, c->s_val, c->stream);
+    HIPC(hipGetLastError()); NETCHK(c);
+    if (int r = read_back_staged(c, c->s_act, c->s_logp, c->s_val, act_out, logp_out, value_out)) return r;
+    c->staged_valid = true;
+    return 0;
+}
+
 // PPO.predict_w_value_saliency (agents/ppo.py:83-94): predict + d value / d observation.  grad_out: IMPALA [E][64][64][3] (NHWC,
 // wrt the k/255 float frames), MLP [E][obs_dim].  Runs the training-mode forward and the whole backward pass with dY = e_value on
 // the E staged observations; the parameter gradients it produces on the way are discarded (the gradient buffer is zeroed again),
@@ -1703,6 +1721,68 @@ int mi_minibatch_finish(mi_ctx* c) {
     c->fs_grad_coef = 0.f; c->fs_global_apply = false; c->fs_global_pending = false;
     c->pending_n = -1;
     HIPC(hipGetLastError()); NETCHK(c);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ IPL (algo: IPL)
+// One minibatch of IPL.optimize (agents/IPL.py:125-192).  The loss reads the network at obs[t] AND obs[t + 1]; with one activation set the
+// schedule is three forward and two backward passes:
+//   1 forward(nobs), inference   -> nv = done ? rew : V(nobs)                      (ipl.hip next-value kernel)
+//   2 forward(obs), training     -> loss kernel: pred, dY, g_next, the record      -> backward(obs)
+//   3 forward(nobs), training    -> dY = {0 .., g_next}                            -> backward(nobs), into the same gradient buffer
+// nobs = ring row idx + E (slot T holds the bootstrap observation).  Everything runs on the main stream (no side-stream job is armed).
+static int ipl_alloc(mi_ctx* c) {
+    if (c->ipl_idx2) return 0;
+    const size_t NB = c->NB;
+    HIPC(dalloc(&c->ipl_idx2, NB)); HIPC(dalloc(&c->ipl_nv, NB)); HIPC(dalloc(&c->ipl_gnext, NB)); HIPC(dalloc(&c->ipl_pred, NB)); HIPC(dalloc(&c->ipl_rew, NB));
+    HIPC(dalloc(&c->ipl_partial, (size_t)ipl_blocks(c->NB) * ipl_partial_cols(c->A)));
+    return 0;
+}
+int mi_ipl_minibatch(mi_ctx* c, const int64_t* idx, int32_t n, int32_t n_global, const mi_ipl_hparams* hp) {
+    ARG(c && hp && idx, "null"); JOIN(c);
+    ARG(c->multirank == 0, "mi_ipl_minibatch: multirank mode must be 0 (IPL runs on one rank)");
+    ARG(!c->ar_armed && !c->ar_inflight, "mi_ipl_minibatch: an armed gradient exchange (mi_allreduce_arm) is not supported");
+    ARG(!c->gru_on, "mi_ipl_minibatch: a recurrent context (mi_set_gru) is not supported");
+    ARG(!c->lse, "mi_ipl_minibatch: value_from_logits is not supported");
+    ARG(n <= c->NB, "mi_ipl_minibatch: n > max_batch");
+    ARG(n >= 1, "mi_ipl_minibatch: n must be at least 1"); ARG(n_global >= 1, "n_global");
+    ARG(c->pending_n < 0, "previous multirank minibatch not finished");
+    ARG(c->log_count + 1 <= c->log_cap, "loss log full: call mi_loss_log_read(reset=1)");
+    const int64_t TE = (int64_t)c->T * c->E;
+    for (int k = 0; k < n; ++k) ARG(idx[k] >= 0 && idx[k] < TE, "minibatch index out of range");
+    if (int r = ipl_alloc(c)) return r;
+    if (int r = stage_indices(c, n, [&](int32_t* h) { for (int k = 0; k < n; ++k) h[k] = (int32_t)idx[k]; }, false)) return r;
+    launch_ipl_shift_idx(c->d_idx, c->ipl_idx2, n, c->E, c->stream);
+    const InputSrc obs = minibatch_src(c), nobs{obs_ring(c), c->ipl_idx2, 0};
+    c->prof.phase = 1;
+    c->prof.sample_now = (c->prof.mb_count++ % c->prof.period) == 0;
+    c->rec_last = false;
+    IplArgs a{};
+    a.hout = c->hout; a.idx = c->d_idx; a.act = c->act; a.rew = c->rew; a.done = c->done;
+    a.nv = c->ipl_nv; a.dY = c->dY; a.g_next = c->ipl_gnext; a.pred = c->ipl_pred; a.rew_out = c->ipl_rew; a.partial = c->ipl_partial;
+    a.n = n; a.A = c->A; a.inv_n_global = 1.0f / (float)n_global;
+    a.gamma = hp->gamma; a.alpha = hp->alpha; a.entropy_coef = hp->entropy_coef;
+    a.entropy_modified = (hp->flags & MI_IPL_ENTROPY_MODIFIED) != 0; a.reward_incentive = (hp->flags & MI_IPL_REWARD_INCENTIVE) != 0;
+    a.adv_incentive = (hp->flags & MI_IPL_ADV_INCENTIVE) != 0; a.zero_obs_seed = (hp->flags & MI_IPL_DEBUG_ZERO_OBS_SEED) != 0;
+    net_forward(c, nobs, n, {});
+    launch_ipl_next_value(a, c->hout, c->A + 1, c->A, c->stream);
+    net_forward(c, obs, n, {.train = true});
+    launch_ipl_loss(a, c->loss_log + (size_t)c->log_count * 8, c->stream);
+    c->log_count += 1;
+    c->ipl_last_n = n;
+    net_backward(c, obs, n);
+    net_forward(c, nobs, n, {.train = true});
+    launch_ipl_next_seed(c->ipl_gnext, c->dY, n, c->A, c->stream);
+    net_backward(c, nobs, n);
+    HIPC(hipGetLastError()); NETCHK(c);
+    return 0;
+}
+int mi_ipl_read_pred(mi_ctx* c, float* pred_out, float* rew_out, int32_t n) {
+    ARG(c && (pred_out || rew_out), "null"); JOIN(c);
+    ARG(c->ipl_idx2 && c->ipl_last_n > 0, "mi_ipl_read_pred: no mi_ipl_minibatch has run"); ARG(n == c->ipl_last_n, "mi_ipl_read_pred: n != the last minibatch's size");
+    if (pred_out) HIPC(hipMemcpyAsync(pred_out, c->ipl_pred, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (rew_out) HIPC(hipMemcpyAsync(rew_out, c->ipl_rew, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
     return 0;
 }
 

@@ -162,6 +162,10 @@ struct mi_ctx {
     // gates, dgi / dgh, the masked input states, the masks 1 - done and the minibatch's initial states
     bool gru_train, rec_last; float *gru_g, *gru_m, *gru_v; double* gru_sumsq;
     float *rec_x, *rec_gi, *rec_sv, *rec_dgi, *rec_dgh, *rec_hm, *rec_mask, *rec_h0;
+    // IPL (mi_ipl_minibatch; allocated by its first call, max_batch rows each): ring rows of obs[t + 1], next values, d loss / d nv, the last
+    // minibatch's pred / reward, the loss kernel's fp64 block partials
+    int32_t* ipl_idx2 = nullptr; float *ipl_nv = nullptr, *ipl_gnext = nullptr, *ipl_pred = nullptr, *ipl_rew = nullptr; double* ipl_partial = nullptr;
+    int ipl_last_n = 0;
 };
 
 static inline char* obs_ring(mi_ctx* c) { return c->frames ? (char*)c->frames : (char*)c->obsf; }      // rollout observations [(T+1)][E]: uint8 frames or fp32 rows

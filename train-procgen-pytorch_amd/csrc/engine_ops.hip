@@ -578,6 +578,60 @@ int mi_op_fc_bf16(mi_ctx* c, int32_t mode, int32_t n, int32_t D, const float* x,
     return 0;
 }
 
+// The IPL kernels alone (ipl.hip) on caller arrays: what mi_ipl_minibatch launches between its network passes
+int mi_op_ipl_loss(mi_ctx* c, int32_t n, int32_t A, const float* hout, const float* nv_raw, const int32_t* act, const float* rew,
+                   const float* done, const mi_ipl_hparams* hp, float* rec8_out, float* dY_out, float* gnext_out, float* pred_out) {
+    ARG(c && hout && nv_raw && act && rew && done && hp, "null"); JOIN(c);
+    ARG(n >= 1 && n <= 65536, "n must be in [1, 65536]"); ARG(A >= 1 && A <= 16, "A must be in [1, 16]");
+    for (int k = 0; k < n; ++k) ARG(act[k] >= 0 && act[k] < A, "action out of range");
+    OpMem m("mi_op_ipl_loss", c->stream);
+    const size_t nh = (size_t)n * (A + 1);
+    float *dh = nullptr, *dnvr = nullptr, *drew = nullptr, *ddone = nullptr; int32_t* dact = nullptr;
+    if (int r = upload(m, hout, nh * 4, (void**)&dh)) return r;
+    if (int r = upload(m, nv_raw, (size_t)n * 4, (void**)&dnvr)) return r;
+    if (int r = upload(m, act, (size_t)n * 4, (void**)&dact)) return r;
+    if (int r = upload(m, rew, (size_t)n * 4, (void**)&drew)) return r;
+    if (int r = upload(m, done, (size_t)n * 4, (void**)&ddone)) return r;
+    IplArgs a{};
+    float *rec = nullptr, *seed = nullptr;
+    HIPC(m.out(&a.nv, (size_t)n * 4, "nv")); HIPC(m.out(&a.dY, nh * 4, "dY")); HIPC(m.out(&a.g_next, (size_t)n * 4, "g_next"));
+    HIPC(m.out(&a.pred, (size_t)n * 4, "pred")); HIPC(m.out(&a.rew_out, (size_t)n * 4, "rew_out"));
+    HIPC(m.out(&a.partial, (size_t)ipl_blocks(n) * ipl_partial_cols(A) * 8, "the block partials"));
+    HIPC(m.out(&rec, 8 * 4, "the record")); HIPC(m.out(&seed, nh * 4, "the next-side seed"));
+    a.hout = dh; a.idx = nullptr; a.act = dact; a.rew = drew; a.done = ddone; a.n = n; a.A = A; a.inv_n_global = 1.0f / (float)n;
+    a.gamma = hp->gamma; a.alpha = hp->alpha; a.entropy_coef = hp->entropy_coef;
+    a.entropy_modified = (hp->flags & MI_IPL_ENTROPY_MODIFIED) != 0; a.reward_incentive = (hp->flags & MI_IPL_REWARD_INCENTIVE) != 0;
+    a.adv_incentive = (hp->flags & MI_IPL_ADV_INCENTIVE) != 0; a.zero_obs_seed = (hp->flags & MI_IPL_DEBUG_ZERO_OBS_SEED) != 0;
+    launch_ipl_next_value(a, dnvr, 1, 0, c->stream);
+    launch_ipl_loss(a, rec, c->stream);
+    launch_ipl_next_seed(a.g_next, seed, n, A, c->stream);
+    if (int r = op_finish(c, m)) return r;
+    if (rec8_out) HIPC(hipMemcpy(rec8_out, rec, 8 * 4, hipMemcpyDeviceToHost));
+    if (dY_out) HIPC(hipMemcpy(dY_out, a.dY, nh * 4, hipMemcpyDeviceToHost));
+    if (gnext_out) {        // read from the seed's value column: what the second backward pass receives; its logit columns must be zeros
+        std::vector<float> h(nh);
+        HIPC(hipMemcpy(h.data(), seed, nh * 4, hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i) {
+            for (int k = 0; k < A; ++k) if (h[(size_t)i * (A + 1) + k] != 0.f) return fail(-4, "mi_op_ipl_loss: the next-side seed has a non-zero logit column");
+            gnext_out[i] = h[(size_t)i * (A + 1) + A];
+        }
+    }
+    if (pred_out) HIPC(hipMemcpy(pred_out, a.pred, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+int mi_op_ipl_greedy(mi_ctx* c, int32_t n, int32_t A, const float* hout, int32_t* act_out) {
+    ARG(c && hout && act_out, "null"); JOIN(c);
+    ARG(n >= 1 && n <= 65536, "n must be in [1, 65536]"); ARG(A >= 1 && A <= 16, "A must be in [1, 16]");
+    OpMem m("mi_op_ipl_greedy", c->stream);
+    float *dh = nullptr, *lp = nullptr, *v = nullptr; int32_t* da = nullptr;
+    if (int r = upload(m, hout, (size_t)n * (A + 1) * 4, (void**)&dh)) return r;
+    HIPC(m.out(&da, (size_t)n * 4, "act")); HIPC(m.out(&lp, (size_t)n * 4, "logp")); HIPC(m.out(&v, (size_t)n * 4, "value"));
+    launch_ipl_greedy(dh, n, A, da, lp, v, c->stream);
+    if (int r = op_finish(c, m)) return r;
+    HIPC(hipMemcpy(act_out, da, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // D = A(16x4) * B(4x16) with asymmetric integer data through the operand maps the kernels assume:
 // A[i = lane&15][k = lane>>4], B[k = lane>>4][j = lane&15], D[row = (lane>>4)*4 + r][col = lane&15]
 __global__ void mfma_selftest_kernel(float* d) {

@@ -34,6 +34,14 @@ class _HParams(C.Structure):
                                          "entropy_multiplier", "fs_coef")]
 
 
+class _IplHParams(C.Structure):
+    _fields_ = [("gamma", C.c_float), ("alpha", C.c_float), ("entropy_coef", C.c_float), ("flags", C.c_int32)]
+
+
+IPL_ENTROPY_MODIFIED, IPL_REWARD_INCENTIVE, IPL_ADV_INCENTIVE, IPL_DEBUG_ZERO_OBS_SEED = 1, 2, 4, 256
+IPL_FIELDS = ("entropy", "mutual_info", "total", "rew_corr", "gamma", "alpha_loss", "alpha", "pred_reward")
+
+
 def lib_path():
     return os.path.join(_HERE, "libmi355ppo.so")
 
@@ -45,7 +53,8 @@ EXPORTS = ("mi_last_error mi_create mi_destroy mi_sync mi_host_alloc mi_host_fre
            "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_op_fc_bf16 mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_gru_step mi_debug_step_latency mi_debug_lane_probe "
            "mi_gru_train mi_minibatch_rec mi_get_gru mi_get_gru_grads mi_get_gru_adam_state mi_set_gru_adam_state mi_debug_gru_seq "
            "mi_sae_create mi_sae_destroy mi_sae_param_count mi_sae_set_params mi_sae_get_params mi_sae_get_grads mi_sae_set_adam_state mi_sae_get_adam_state mi_sae_put_ring "
-           "mi_sae_get_hidden mi_sae_get_logits mi_sae_step mi_sae_minibatch mi_sae_probe_minibatch mi_sae_optimizer_step mi_sae_debug_forward").split()
+           "mi_sae_get_hidden mi_sae_get_logits mi_sae_step mi_sae_minibatch mi_sae_probe_minibatch mi_sae_optimizer_step mi_sae_debug_forward "
+           "mi_ipl_minibatch mi_ipl_read_pred mi_predict_greedy mi_op_ipl_loss mi_op_ipl_greedy").split()
 
 
 def load_library():
@@ -486,6 +495,52 @@ class Engine:
         n = C.c_int32(0)
         self._chk(self.lib.mi_loss_log_read(self._ctx, _fp(out), C.c_int32(max_records), C.byref(n), C.c_int32(int(reset))))
         return out[:n.value].copy()
+
+    # ------------------------------------------------------------------ IPL agent (algo: IPL)
+    @staticmethod
+    def ipl_hparams(gamma=0.99, alpha=1.0, entropy_coef=0.0, entropy_modified=False, reward_incentive=False, adv_incentive=False,
+                    debug_zero_obs_seed=False):
+        flags = (IPL_ENTROPY_MODIFIED * bool(entropy_modified) | IPL_REWARD_INCENTIVE * bool(reward_incentive) |
+                 IPL_ADV_INCENTIVE * bool(adv_incentive) | IPL_DEBUG_ZERO_OBS_SEED * bool(debug_zero_obs_seed))
+        return _IplHParams(gamma, alpha, entropy_coef, int(flags))
+
+    def ipl_minibatch(self, idx, n_global, hp):
+        """One minibatch of IPL.optimize on ring rows idx (mi_ipl_minibatch): gradients accumulate, one record (IPL_FIELDS) in the loss log."""
+        idx = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        self._chk(self.lib.mi_ipl_minibatch(self._ctx, _fp(idx), C.c_int32(idx.size), C.c_int32(n_global), C.byref(hp)))
+
+    def ipl_read_pred(self, n):
+        """(pred, rew) of the last ipl_minibatch (n = its size): IPL.last_predicted_reward / last_reward."""
+        pred, rew = np.empty(n, np.float32), np.empty(n, np.float32)
+        self._chk(self.lib.mi_ipl_read_pred(self._ctx, _fp(pred), _fp(rew), C.c_int32(n)))
+        return pred, rew
+
+    def predict_greedy(self, obs):
+        """IPL.predict(obs, greedy=True) on E observations, staged like predict_staged -> (act, logp, value)."""
+        want = np.uint8 if self.arch == ARCH_IMPALA else np.float32
+        obs = np.ascontiguousarray(obs, dtype=want)
+        act, logp, val = np.empty(self.E, np.int64), np.empty(self.E, np.float32), np.empty(self.E, np.float32)
+        self._chk(self.lib.mi_predict_greedy(self._ctx, _fp(obs), C.c_size_t(obs.nbytes), _fp(act), _fp(logp), _fp(val)))
+        return act, logp, val
+
+    def op_ipl_loss(self, hout, nv_raw, act, rew, done, hp):
+        """The IPL kernels alone on caller arrays (mi_op_ipl_loss): hout (n, A + 1), nv_raw / act / rew / done (n,) ->
+        (record (8,), dY (n, A + 1), g_next (n,), pred (n,))."""
+        hout = _f32(hout)
+        n, A = hout.shape[0], hout.shape[1] - 1
+        nv_raw, rew, done = (_f32(a).reshape(n) for a in (nv_raw, rew, done))
+        act = np.ascontiguousarray(act, dtype=np.int32).reshape(n)
+        rec, dY, gn, pred = np.empty(8, np.float32), np.empty((n, A + 1), np.float32), np.empty(n, np.float32), np.empty(n, np.float32)
+        self._chk(self.lib.mi_op_ipl_loss(self._ctx, C.c_int32(n), C.c_int32(A), _fp(hout), _fp(nv_raw), _fp(act), _fp(rew), _fp(done),
+                                          C.byref(hp), _fp(rec), _fp(dY), _fp(gn), _fp(pred)))
+        return rec, dY, gn, pred
+
+    def op_ipl_greedy(self, hout):
+        """First arg-max of the normalised log-probabilities of head rows hout (n, A + 1) (mi_op_ipl_greedy)."""
+        hout = _f32(hout)
+        act = np.empty(hout.shape[0], np.int32)
+        self._chk(self.lib.mi_op_ipl_greedy(self._ctx, C.c_int32(hout.shape[0]), C.c_int32(hout.shape[1] - 1), _fp(hout), _fp(act)))
+        return act
 
     # ------------------------------------------------------------------ sparse-autoencoder agent (algo: sae)
     SAE, PROBE = 0, 1                      # `which` of the mi_sae_* entry points

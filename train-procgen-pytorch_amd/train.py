@@ -35,12 +35,13 @@ import yaml
 from agents.ppo import PPO
 from agents.ppo_pure import PPOPure
 from agents.sae import SAE, check_supported as sae_check_supported
+from agents.ipl import IPL, check_supported as ipl_check_supported
 from common.env.vec_envs import EnvGroups, SyntheticFrames, create_cartpole, create_procgen_env
 from common.logger import Logger, SimpleLogger
 from common.misc_util import set_global_seeds
 from common.model import ImpalaModel, MLPModel
 from common.policy import CategoricalPolicy
-from common.storage import SAEStorage, Storage
+from common.storage import IPLStorage, SAEStorage, Storage
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -58,11 +59,12 @@ def get_hyperparams(param_name):
     with open(os.path.join(HERE, "hyperparams", "procgen", "config.yml")) as f:      # repo-relative (helper_local.py:207-210 used GLOBAL_DIR)
         sets = yaml.safe_load(f)
     if param_name not in sets:
-        # sets of the agents beside PPO (algo: sae) live in a file of their own: config.yml is the reference's PPO selection
-        with open(os.path.join(HERE, "hyperparams", "procgen", "config_sae.yml")) as f:
-            more = yaml.safe_load(f)
-        if param_name in more:
-            return dict(more[param_name])
+        # sets of the agents beside PPO (algo: sae, algo: IPL) live in files of their own: config.yml is the reference's PPO selection
+        for name in ("config_sae.yml", "config_ipl.yml"):
+            with open(os.path.join(HERE, "hyperparams", "procgen", name)) as f:
+                more = yaml.safe_load(f)
+            if param_name in more:
+                return dict(more[param_name])
         raise KeyError(f"--param_name {param_name}: not one of the shipped PPO sets {sorted(sets)} (other agents / architectures of the "
                        "reference's config.yml are out of scope)")
     return dict(sets[param_name])
@@ -121,8 +123,8 @@ def add_training_args(p):
     p.add_argument('--rollout_groups', type=int, default=0,
                    help="env groups of the pipelined rollout (one group's frame upload + forward beside the host's env.step of another); 0 = auto (from 128 envs per rank: 4, or 2 + 2 when a validation env runs beside the training env; else 2; a recurrent policy: 1); 1 = the reference's serial step; a recurrent policy is pipelined only with an explicit G >= 2")
     p.add_argument('--x_entropy_coef', type=float, default=None)
-    p.add_argument('--algo', type=str, default=None, choices=['ppo', 'ppo-pure', 'sae'],
-                   help="overrides the set's `algo`: ppo = the reference's agents/ppo.py (a recurrent policy's GRU stays frozen), ppo-pure = agents/ppo_pure.py (a recurrent policy is trained through its GRU with BPTT; single GPU), sae = agents/sae.py (a sparse autoencoder on the block-3 features of the trained IMPALA policy given by --model_file, then a linear probe on its codes; single GPU, use --param_name sae)")
+    p.add_argument('--algo', type=str, default=None, choices=['ppo', 'ppo-pure', 'sae', 'IPL'],
+                   help="overrides the set's `algo`: ppo = the reference's agents/ppo.py (a recurrent policy's GRU stays frozen), ppo-pure = agents/ppo_pure.py (a recurrent policy is trained through its GRU with BPTT; single GPU), sae = agents/sae.py (a sparse autoencoder on the block-3 features of the trained IMPALA policy given by --model_file, then a linear probe on its codes; single GPU, use --param_name sae), IPL = agents/IPL.py (non-recurrent, single GPU; sets hard-500-ipl and ipl_cartpole)")
     return p
 
 
@@ -226,8 +228,13 @@ def train_ppo(args):
     for key, value in hp.items():
         print(key, ':', value)
     algo = hp.get("algo", "ppo")
-    if algo not in ("ppo", "ppo-pure", "sae"):
-        raise NotImplementedError("only algo: ppo, algo: ppo-pure and algo: sae are accelerated")
+    if algo == "IPL_ICM":
+        raise NotImplementedError("algo: IPL_ICM is not supported (algo: IPL is)")
+    if algo not in ("ppo", "ppo-pure", "sae", "IPL"):
+        raise NotImplementedError("only algo: ppo, algo: ppo-pure, algo: sae and algo: IPL are accelerated")
+    if algo == "IPL":                                       # everything outside the built scope, by name, before any engine exists
+        hp["learned_gamma"] = bool(hp.get("learned_gamma", False)) or bool(getattr(args, "learned_gamma", False))
+        ipl_check_supported(hp, use_greedy_env=bool(getattr(args, "use_greedy_env", False)))
     if algo == "sae":
         if args.model_file is None:
             raise ValueError("algo sae needs --model_file <checkpoint of a trained IMPALA policy>: a sparse autoencoder of an untrained "
@@ -276,16 +283,18 @@ def train_ppo(args):
     cfg = dict(vars(args)); cfg.update(hp)
     np.save(os.path.join(logdir, "config.npy"), cfg)
     model, obs_shape, policy = initialize_model(device, env, hp)
-    logger = (SimpleLogger if algo == "sae" else Logger)(n_envs, logdir, use_wandb=args.use_wandb, algo=algo)      # (train.py:195-199)
+    logger = (SimpleLogger if algo == "sae" else Logger)(n_envs, logdir, use_wandb=args.use_wandb, algo=algo)      # (train.py:195-199; algo IPL: its own loss columns)
     logger.max_steps = hp.get("max_steps", 10 ** 3)
     if algo == "sae":                                       # train.py:206-218: the storage holds the 2048 block-3 features and all A logits
         sae_check_supported(policy, n_envs, env, hp.get("sae_dim", 1024))
         make_storage = lambda: SAEStorage(obs_shape, model.encoded_dim, n_steps, n_envs, device, act_shape=env.action_space.n)
+    elif algo == "IPL":                                     # train.py:220-223
+        make_storage = lambda: IPLStorage(obs_shape, n_steps, n_envs, device)
     else:
         make_storage = lambda: Storage(obs_shape, model.output_dim, n_steps, n_envs, device)
     storage = make_storage()
     storage_valid = make_storage() if args.use_valid_env else None
-    agent_cls = SAE if algo == "sae" else PPOPure if algo == "ppo-pure" else PPO
+    agent_cls = SAE if algo == "sae" else IPL if algo == "IPL" else PPOPure if algo == "ppo-pure" else PPO
     agent = agent_cls(env, policy, logger, storage, device, args.num_checkpoints, env_valid=env_valid, storage_valid=storage_valid,
                 seed=args.seed + rank, detect_nan=args.detect_nan, **hp)
     if model_file is not None:
