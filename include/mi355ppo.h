@@ -236,9 +236,8 @@ int mi_set_gru_adam_state(mi_ctx* ctx, const float* exp_avg, const float* exp_av
  *      encoder's 2048 input columns and the decoder's 2048 rows are channel-major ch*64 + p (Flatten() on NCHW); the library permutes to
  *      its pixel-major feature order as it does for embedder.fc.weight.  mi_sae_get_hidden / mi_sae_put_ring use the same order. */
 int mi_sae_create(mi_ctx* ctx, int32_t sae_dim, float rho);
-/* releases what mi_sae_create allocated; call it BEFORE mi_destroy (the state is kept beside the context, which does not know of it).
- * A context destroyed without it leaks those buffers until a later context is created at the same address: every mi_sae_* call checks
- * that the state it finds was created for THIS context (its parameter buffer and T, E, A) and releases a stale one instead of using it. */
+/* releases what mi_sae_create allocated, so that the context can get another SAE.  Optional: the state belongs to the context and
+ * mi_destroy releases a live one.  Returns 0 also when there is nothing to release. */
 int mi_sae_destroy(mi_ctx* ctx);
 int64_t mi_sae_param_count(mi_ctx* ctx, int32_t which);
 int mi_sae_set_params(mi_ctx* ctx, int32_t which, const float* flat, int64_t n);
@@ -421,6 +420,9 @@ int mi_debug_lane_probe(mi_ctx* ctx, int32_t mask, int32_t iters, float* usec);
  * bit 4 set: a minibatch pass keeps the logged statistics and embedder.fc's weight gradient on the main stream instead of
  * forking them onto the side stream -- the A side of the bit-equality test of the two orders */
 int mi_debug_flags(mi_ctx* ctx, int32_t flags);
+/* out = {device allocations, pinned host allocations, events} that the contexts of this process (and the agents' state on them) hold
+ * right now.  Destroying a context takes each count back to what it was before mi_create. */
+int mi_debug_live_resources(int64_t out[3]);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,7 @@
 //   engine_ctx.h    mi_ctx and the structs it embeds, the error plumbing (fail, HIPC, ARG, NETCHK, JOIN, CUR), and the declarations of
 //                   the functions of this file that engine_ops.hip calls
 //   lanes.h         which stream an env group of the pipelined rollout runs on: the process-wide lane registry (plain C++, host-tested)
+//   devpool.h       who frees what: the pool that owns a context's device buffers, pinned buffers and events (plain C++, host-tested)
 //   engine.hip      create / destroy, rollout storage, profiler, the network program (forward_* / backward_* per mode), rollout steps and
 //                   env groups, minibatch passes, optimizer, GRU, collectives
 //   engine_ops.hip  mi_op_*, mi_debug_* (but mi_debug_flags: it sets production state) and mi_selftest_mfma: tests and micro-benchmarks only
@@ -36,6 +37,29 @@ thread_local hipStream_t tl_stream = nullptr;
 thread_local float* tl_ws = nullptr;
 thread_local size_t tl_ws_floats = 0;
 const char* mi_last_error(void) { return g_err.c_str(); }
+
+// ---- the HIP backend of every pool (devpool.h), and the process-wide counts of what the pools hold: device allocations, pinned
+// allocations, events (mi_debug_live_resources: back at their earlier values once a context is destroyed)
+static std::atomic<int64_t> g_live[3];
+static int hip_dev_alloc(void** p, size_t bytes, bool zero) {
+    hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) return e;
+    // hipMemset is asynchronous on the NULL stream and the context's stream is non-blocking: without this wait a
+    // kernel launched right after (the op-level test hooks do that) can be overtaken by the zero fill
+    if (zero && ((e = hipMemset(*p, 0, bytes)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess)) { hipFree(*p); return e; }
+    ++g_live[0];
+    return 0;
+}
+static void hip_dev_free(void* p) { hipFree(p); --g_live[0]; }
+static int hip_pinned_alloc(void** p, size_t bytes, unsigned flags) { const hipError_t e = hipHostMalloc(p, bytes, flags); g_live[1] += e == hipSuccess; return e; }
+static void hip_pinned_free(void* p) { hipHostFree(p); --g_live[1]; }
+static int hip_event_create(void** ev, unsigned flags) { const hipError_t e = hipEventCreateWithFlags((hipEvent_t*)ev, flags); g_live[2] += e == hipSuccess; return e; }
+static void hip_event_destroy(void* ev) { hipEventDestroy((hipEvent_t)ev); --g_live[2]; }
+const DevPool::Backend* hip_pool() {
+    static const DevPool::Backend be = {hip_dev_alloc, hip_dev_free, hip_pinned_alloc, hip_pinned_free, hip_event_create, hip_event_destroy};
+    return &be;
+}
+int mi_debug_live_resources(int64_t out[3]) { ARG(out, "null"); for (int k = 0; k < 3; ++k) out[k] = g_live[k].load(); return 0; }
 
 #define NCCLC(x)                                                                                         \
     do {                                                                                                 \
@@ -211,6 +235,8 @@ static int download_flat(mi_ctx* c, const float* dbuf, float* flat, int64_t n) {
 }
 
 // ------------------------------------------------------------------------------------------ create / destroy
+static int ctx_build(mi_ctx* c);
+static void ctx_release(mi_ctx* c);
 int mi_create(const mi_config* cfg, mi_ctx** out) {
     ARG(cfg && out, "null cfg/out");
     ARG(cfg->arch == MI_ARCH_IMPALA || cfg->arch == MI_ARCH_MLP, "arch");
@@ -228,122 +254,112 @@ int mi_create(const mi_config* cfg, mi_ctx** out) {
     HIPC(hipSetDevice(cfg->device));
     mi_ctx* c = new mi_ctx();
     c->cfg = *cfg;
+    if (int r = ctx_build(c)) { const std::string why = g_err; ctx_release(c); return fail(r, why); }      // whatever it got so far goes back
+    *out = c;
+    return 0;
+}
+// Everything the context owns from its first call on (c->cfg is set, every other member has its default).  It may fail anywhere:
+// what it acquired is in the pool or is one of the explicit streams, and ctx_release takes a half-built context.
+static int ctx_build(mi_ctx* c) {
+    const mi_config* cfg = &c->cfg;
+    DevPool& m = c->pool;
     c->T = cfg->n_steps; c->E = cfg->n_envs; c->A = cfg->n_actions;
     c->H = (cfg->arch == MI_ARCH_IMPALA && cfg->out_dim == 0) ? 256 : cfg->out_dim;
     c->NB = cfg->max_batch < cfg->n_envs ? cfg->n_envs : cfg->max_batch;
     c->bf = (cfg->arch == MI_ARCH_IMPALA) && cfg->precision == 1;
     c->lse = cfg->value_from_logits;
     c->es = c->bf ? 2.0 : 4.0;
-    if (cfg->stream) { c->stream = (hipStream_t)cfg->stream; c->own_stream = false; }
+    if (cfg->stream) c->stream = (hipStream_t)cfg->stream;
     else { HIPC(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
-    HIPC(hipEventCreateWithFlags(&c->ev_side_fork, hipEventDisableTiming)); HIPC(hipEventCreateWithFlags(&c->ev_side_join, hipEventDisableTiming));
-    c->side_stream = nullptr; c->side_on = true; c->side.armed = false;
+    c->main_stream = c->stream;
+    HIPC(m.event(&c->ev_side_fork, hipEventDisableTiming)); HIPC(m.event(&c->ev_side_join, hipEventDisableTiming));
     if (cfg->arch == MI_ARCH_IMPALA) build_impala_layout(c); else build_mlp_layout(c);
-    if (cfg->arch == MI_ARCH_IMPALA && !impala_regions_ok(c)) { delete c; return fail(-1, "internal: parameter layout does not split at embedder.fc.weight"); }
+    if (cfg->arch == MI_ARCH_IMPALA && !impala_regions_ok(c)) return fail(-1, "internal: parameter layout does not split at embedder.fc.weight");
 
     const int64_t P = c->n_params, T = c->T, E = c->E, NB = c->NB;
-    HIPC(dalloc(&c->params, P)); HIPC(dalloc(&c->grads, P)); HIPC(dalloc(&c->adam_m, P)); HIPC(dalloc(&c->adam_v, P));
-    HIPC(dalloc(&c->rew, T * E)); HIPC(dalloc(&c->done, T * E)); HIPC(dalloc(&c->logp, T * E));
-    HIPC(dalloc(&c->adv, T * E)); HIPC(dalloc(&c->ret, T * E)); HIPC(dalloc(&c->value, (T + 1) * E));
-    HIPC(dalloc(&c->act, T * E)); HIPC(dalloc(&c->adv_stats, 4));
-    c->frames = nullptr; c->obsf = nullptr; c->stage_frames = nullptr; c->stage_obs = nullptr;
+    HIPC(m.dev(&c->params, P)); HIPC(m.dev(&c->grads, P)); HIPC(m.dev(&c->adam_m, P)); HIPC(m.dev(&c->adam_v, P));
+    HIPC(m.dev(&c->rew, T * E)); HIPC(m.dev(&c->done, T * E)); HIPC(m.dev(&c->logp, T * E));
+    HIPC(m.dev(&c->adv, T * E)); HIPC(m.dev(&c->ret, T * E)); HIPC(m.dev(&c->value, (T + 1) * E));
+    HIPC(m.dev(&c->act, T * E)); HIPC(m.dev(&c->adv_stats, 4));
     if (cfg->arch == MI_ARCH_IMPALA) {
         c->obs_bytes_per_env = 64 * 64 * 3;
-        HIPC(dalloc(&c->frames, (size_t)(T + 1) * E * c->obs_bytes_per_env));
-        HIPC(dalloc(&c->stage_frames, (size_t)NB * c->obs_bytes_per_env));
+        HIPC(m.dev(&c->frames, (size_t)(T + 1) * E * c->obs_bytes_per_env));
+        HIPC(m.dev(&c->stage_frames, (size_t)NB * c->obs_bytes_per_env));
         const int chan[4] = {3, 16, 32, 32};
         int hin = 64;
         for (int b = 0; b < 3; ++b) {
             Block& k = c->blk[b];
             k.cin = chan[b]; k.cout = chan[b + 1]; k.hin = hin;
             const size_t X = (size_t)NB * hin * hin * k.cout, p = X / 4;
-            k.C = nullptr;                       // conv output before the pool: bf16 mode keeps it in LDS (fused conv + pool kernels)
-            if (!c->bf) HIPC(dalloc(&k.C, X));
-            HIPC(dalloc(&k.PI, p));
-            HIPC(dalloc(&k.P0, p)); HIPC(dalloc(&k.A1, p)); HIPC(dalloc(&k.P1, p)); HIPC(dalloc(&k.A2, p)); HIPC(dalloc(&k.P2, p));
+            if (!c->bf) HIPC(m.dev(&k.C, X));   // conv output before the pool: bf16 mode keeps it in LDS (fused conv + pool kernels)
+            HIPC(m.dev(&k.PI, p));
+            HIPC(m.dev(&k.P0, p)); HIPC(m.dev(&k.A1, p)); HIPC(m.dev(&k.P1, p)); HIPC(m.dev(&k.A2, p)); HIPC(m.dev(&k.P2, p));
             hin /= 2;
         }
-        c->GC = nullptr;                         // gradient of the pre-pool conv output: bf16 mode rebuilds it in LDS (PoolStage)
-        if (!c->bf) HIPC(dalloc(&c->GC, (size_t)NB * 64 * 64 * 16));
-        for (int k = 0; k < 3; ++k) HIPC(dalloc(&c->GP[k], (size_t)NB * 32 * 32 * 16));
+        if (!c->bf) HIPC(m.dev(&c->GC, (size_t)NB * 64 * 64 * 16));      // gradient of the pre-pool conv output: bf16 mode rebuilds it in LDS (PoolStage)
+        for (int k = 0; k < 3; ++k) HIPC(m.dev(&c->GP[k], (size_t)NB * 32 * 32 * 16));
         // every conv layer owns a slab region (persistent grids never exceed 4 workgroups x 256 CUs)
-        c->slab_floats = 0;
         for (size_t l = 0; l < c->convs.size() && l < 15; ++l) {
             c->slab_off[l] = (long long)c->slab_floats;
             c->slab_floats += (size_t)1024 * (size_t)(c->convs[l].cout * 9 * c->convs[l].cin + c->convs[l].cout);
         }
-        HIPC(dalloc(&c->slabs, c->slab_floats));
-        HIPC(hipMalloc((void**)&c->d_slab_desc, sizeof(SlabDesc) * 15)); c->slab_desc_n = 0; c->slab_desc_cached_n = -1;
-        HIPC(dalloc(&c->fs_scratch, (size_t)MI_MAX_SEG * 128 * 2048));      // (segments x) FS_GROUPS x 2048 partial column maxima (loss.hip)
-        HIPC(dalloc(&c->fs_colmax, (size_t)2048)); HIPC(dalloc(&c->fs_arg, (size_t)2048));
-        HIPC(dalloc(&c->fs_keys, (size_t)2048)); HIPC(dalloc(&c->fs_keys_local, (size_t)2048)); HIPC(dalloc(&c->d_gpos, (size_t)NB));
-        HIPC(hipHostMalloc((void**)&c->h_gpos, (size_t)NB * 4, hipHostMallocDefault));
+        HIPC(m.dev(&c->slabs, c->slab_floats));
+        HIPC(m.dev_raw(&c->d_slab_desc, sizeof(SlabDesc) * 15));
+        HIPC(m.dev(&c->fs_scratch, (size_t)MI_MAX_SEG * 128 * 2048));      // (segments x) FS_GROUPS x 2048 partial column maxima (loss.hip)
+        HIPC(m.dev(&c->fs_colmax, (size_t)2048)); HIPC(m.dev(&c->fs_arg, (size_t)2048));
+        HIPC(m.dev(&c->fs_keys, (size_t)2048)); HIPC(m.dev(&c->fs_keys_local, (size_t)2048)); HIPC(m.dev(&c->d_gpos, (size_t)NB));
+        HIPC(m.pinned(&c->h_gpos, (size_t)NB * 4, hipHostMallocDefault));
     } else {
         c->obs_bytes_per_env = (size_t)cfg->obs_dim * sizeof(float);
-        HIPC(dalloc(&c->obsf, (size_t)(T + 1) * E * cfg->obs_dim));
-        HIPC(dalloc(&c->stage_obs, (size_t)NB * cfg->obs_dim));
+        HIPC(m.dev(&c->obsf, (size_t)(T + 1) * E * cfg->obs_dim));
+        HIPC(m.dev(&c->stage_obs, (size_t)NB * cfg->obs_dim));
         c->mlp_act.resize(c->mlp.size() + 1);
-        HIPC(dalloc(&c->mlp_act[0], (size_t)NB * cfg->obs_dim));
-        for (size_t l = 0; l < c->mlp.size(); ++l) HIPC(dalloc(&c->mlp_act[l + 1], (size_t)NB * c->mlp[l].out));
-        c->GC = nullptr; c->slabs = nullptr; c->fs_scratch = nullptr; c->d_slab_desc = nullptr; c->slab_desc_n = 0; c->slab_desc_cached_n = -1;
+        HIPC(m.dev(&c->mlp_act[0], (size_t)NB * cfg->obs_dim));
+        for (size_t l = 0; l < c->mlp.size(); ++l) HIPC(m.dev(&c->mlp_act[l + 1], (size_t)NB * c->mlp[l].out));
         const int wmax = cfg->mlp_width > c->H ? cfg->mlp_width : c->H;
-        for (int k = 0; k < 2; ++k) HIPC(dalloc(&c->GP[k], (size_t)NB * wmax));
-        c->GP[2] = nullptr;
+        for (int k = 0; k < 2; ++k) HIPC(m.dev(&c->GP[k], (size_t)NB * wmax));
     }
-    HIPC(dalloc(&c->feat, (size_t)NB * c->H)); HIPC(dalloc(&c->dfeat, (size_t)NB * c->H));
-    HIPC(dalloc(&c->hout, (size_t)NB * (c->A + 1))); HIPC(dalloc(&c->dY, (size_t)NB * (c->A + 1)));
-    if (c->lse) HIPC(dalloc(&c->d_val, (size_t)NB));
-    HIPC(dalloc(&c->d_lp, (size_t)NB * c->A));
+    HIPC(m.dev(&c->feat, (size_t)NB * c->H)); HIPC(m.dev(&c->dfeat, (size_t)NB * c->H));
+    HIPC(m.dev(&c->hout, (size_t)NB * (c->A + 1))); HIPC(m.dev(&c->dY, (size_t)NB * (c->A + 1)));
+    if (c->lse) HIPC(m.dev(&c->d_val, (size_t)NB));
+    HIPC(m.dev(&c->d_lp, (size_t)NB * c->A));
     const size_t gws = (size_t)8 << 20;
-    HIPC(dalloc(&c->gemm_ws, gws)); c->gemm_ws_floats = gws;
-    HIPC(dalloc(&c->col_ws, (size_t)64 * 4096));
-    HIPC(dalloc(&c->fs_val, 4));
+    HIPC(m.dev(&c->gemm_ws, gws)); c->gemm_ws_floats = gws;
+    HIPC(m.dev(&c->col_ws, (size_t)64 * 4096));
+    HIPC(m.dev(&c->fs_val, 4));
     {
         float h[256];
         for (int k = 0; k < 256; ++k) h[k] = (float)((double)k / 255.0);   // ScaledFloatFrame: obs / 255.0 in fp64, then fp32
-        HIPC(dalloc(&c->lut, 256));
+        HIPC(m.dev(&c->lut, 256));
         HIPC(hipMemcpy(c->lut, h, sizeof(h), hipMemcpyHostToDevice));
         std::vector<uint16_t> b = host_to_bf16(h, 256);      // the same table as bf16
-        HIPC(dalloc(&c->lut16, 256));
+        HIPC(m.dev(&c->lut16, 256));
         HIPC(hipMemcpy(c->lut16, b.data(), 512, hipMemcpyHostToDevice));
     }
-    HIPC(dalloc(&c->d_idx, (size_t)NB));
-    HIPC(dalloc(&c->loss_partial, (size_t)(loss_blocks(NB) + 1 + MI_MAX_SEG) * 32));
-    HIPC(dalloc(&c->loss_stats, 64));
-    c->log_cap = 4096; c->log_count = 0;
-    HIPC(dalloc(&c->loss_log, (size_t)c->log_cap * 8));
-    HIPC(dalloc(&c->stats_ring, (size_t)c->log_cap * 32)); HIPC(dalloc(&c->fs_ring, (size_t)c->log_cap)); HIPC(dalloc(&c->fs_parts, (size_t)MI_MAX_SEG * 8));
-    HIPC(dalloc(&c->sumsq, 2 + 128)); HIPC(dalloc(&c->gnorm, 2));
-    HIPC(dalloc(&c->d_u, (size_t)E));
-    HIPC(dalloc(&c->d_pack, (size_t)3 * E)); HIPC(dalloc(&c->d_rd, (size_t)2 * E));
+    HIPC(m.dev(&c->d_idx, (size_t)NB));
+    HIPC(m.dev(&c->loss_partial, (size_t)(loss_blocks(NB) + 1 + MI_MAX_SEG) * 32));
+    HIPC(m.dev(&c->loss_stats, 64));
+    HIPC(m.dev(&c->loss_log, (size_t)c->log_cap * 8));
+    HIPC(m.dev(&c->stats_ring, (size_t)c->log_cap * 32)); HIPC(m.dev(&c->fs_ring, (size_t)c->log_cap)); HIPC(m.dev(&c->fs_parts, (size_t)MI_MAX_SEG * 8));
+    HIPC(m.dev(&c->sumsq, 2 + 128)); HIPC(m.dev(&c->gnorm, 2));
+    HIPC(m.dev(&c->d_u, (size_t)E));
+    HIPC(m.dev(&c->d_pack, (size_t)3 * E)); HIPC(m.dev(&c->d_rd, (size_t)2 * E));
     // written / read by a RUNNING kernel while the host polls the ticket: fine-grained coherent mapping, whatever HIP_HOST_COHERENT says
     const unsigned hflags = hipHostMallocCoherent | hipHostMallocMapped;
-    HIPC(hipHostMalloc((void**)&c->h_pack, (size_t)3 * E * 4, hflags)); HIPC(hipHostMalloc((void**)&c->h_rd, (size_t)2 * E * 4, hflags));
-    HIPC(dalloc(&c->d_done_ctr, (size_t)16)); HIPC(hipHostMalloc((void**)&c->h_flag, 64, hflags)); memset(c->h_flag, 0, 64); c->roll_ticket = 0;
-    HIPC(dalloc(&c->s_act, (size_t)E)); HIPC(dalloc(&c->s_logp, (size_t)E)); HIPC(dalloc(&c->s_val, (size_t)E)); c->staged_valid = false;
+    HIPC(m.pinned(&c->h_pack, (size_t)3 * E * 4, hflags)); HIPC(m.pinned(&c->h_rd, (size_t)2 * E * 4, hflags));
+    HIPC(m.dev(&c->d_done_ctr, (size_t)16)); HIPC(m.pinned(&c->h_flag, 64, hflags)); memset(c->h_flag, 0, 64);
+    HIPC(m.dev(&c->s_act, (size_t)E)); HIPC(m.dev(&c->s_logp, (size_t)E)); HIPC(m.dev(&c->s_val, (size_t)E));
     for (int k = 0; k < mi_ctx::IDX_RING; ++k) {
-        HIPC(hipHostMalloc((void**)&c->h_idx_ring[k], (size_t)NB * sizeof(int32_t), hflags));      // coherent + mapped: a kernel reads it
-        HIPC(hipEventCreateWithFlags(&c->idx_ev[k], hipEventDisableTiming));
-        c->idx_used[k] = false;
+        HIPC(m.pinned(&c->h_idx_ring[k], (size_t)NB * sizeof(int32_t), hflags));      // coherent + mapped: a kernel reads it
+        HIPC(m.event(&c->idx_ev[k], hipEventDisableTiming));
     }
-    c->idx_next = 0; c->idx_ev_deferred = -1;
     c->h_f_floats = (size_t)4 * (E > 64 ? E : 64);
-    HIPC(hipHostMalloc((void**)&c->h_f, c->h_f_floats * sizeof(float)));
-    HIPC(hipHostMalloc((void**)&c->h_i, (size_t)E * sizeof(int32_t)));
-    c->comm = nullptr; c->comm_grad = nullptr; c->comm_world = 1; c->comm_rank = 0; c->comm_stream = nullptr; c->ev_ar_ready = c->ev_ar_done = nullptr;
-    c->ar_armed = c->ar_issued = c->ar_inflight = false; c->adv_all = nullptr;
-    c->fs_grad_coef = 0.f; c->fs_G = 0; c->rollout_tail = true; c->no_pull = false; c->copy_rate_bytes_per_us = getenv("MI355_COPY_GBPS") ? atof(getenv("MI355_COPY_GBPS")) * 1000.0 : 40000.0;
-    if (cfg->arch != MI_ARCH_IMPALA) { c->fs_colmax = nullptr; c->fs_arg = nullptr; c->fs_keys = c->fs_keys_local = nullptr; c->d_gpos = nullptr; c->h_gpos = nullptr; }
-    c->gpos_n = -1; c->fs_global_pending = c->fs_global_apply = false;
-    c->n_groups = 1; c->groups_live = false; c->main_stream = c->stream;
-    for (int g = 0; g < mi_ctx::MAX_GROUPS; ++g) { c->gw[g] = nullptr; c->gs[g] = nullptr; c->ev_fork[g] = c->ev_join[g] = nullptr; c->g_forked[g] = c->g_busy[g] = c->g_last[g] = c->g_dirty[g] = false; c->g_ticket[g] = 0; }
-    c->multirank = 0; c->pending_n = -1; c->sal_dc = nullptr; c->sal_dx = nullptr; c->sal_src = nullptr;
-    c->fc_wp = c->fc_wt = nullptr; c->fc_packed_valid = false;
-    if (c->bf) { HIPC(dalloc(&c->fc_wp, (size_t)c->H * 2048)); HIPC(dalloc(&c->fc_wt, (size_t)c->H * 2048)); }
-    c->banks = nullptr; c->d_bank_desc = nullptr; c->n_banks = 0; c->c1_bank = nullptr;
-    if (c->bf && c->cfg.arch == MI_ARCH_IMPALA) HIPC(dalloc(&c->c1_bank, (size_t)conv1_bank_elems()));
-    for (auto& L : c->convs) { L.bank_f = -1; L.bank_d = -1; }
+    HIPC(m.pinned(&c->h_f, c->h_f_floats * sizeof(float), hipHostMallocDefault));
+    HIPC(m.pinned(&c->h_i, (size_t)E * sizeof(int32_t), hipHostMallocDefault));
+    if (getenv("MI355_COPY_GBPS")) c->copy_rate_bytes_per_us = atof(getenv("MI355_COPY_GBPS")) * 1000.0;
     if (c->bf) {
+        HIPC(m.dev(&c->fc_wp, (size_t)c->H * 2048)); HIPC(m.dev(&c->fc_wt, (size_t)c->H * 2048));
+        HIPC(m.dev(&c->c1_bank, (size_t)conv1_bank_elems()));
         std::vector<BankDesc> desc;
         long long off = 0;
         for (auto& L : c->convs) {
@@ -354,23 +370,16 @@ int mi_create(const mi_config* cfg, mi_ctx** out) {
             L.bank_d = off; off += (long long)d.rows * d.ws; desc.push_back(d);
         }
         c->n_banks = (int)desc.size();
-        HIPC(dalloc(&c->banks, (size_t)off));
-        HIPC(hipMalloc((void**)&c->d_bank_desc, desc.size() * sizeof(BankDesc)));
+        HIPC(m.dev(&c->banks, (size_t)off));
+        HIPC(m.dev_raw(&c->d_bank_desc, desc.size() * sizeof(BankDesc)));
         HIPC(hipMemcpy(c->d_bank_desc, desc.data(), desc.size() * sizeof(BankDesc), hipMemcpyHostToDevice));
     }
-    c->gru_x = c->gru_dg = nullptr; c->sal_keep_x = c->bwd_from_dfeat = false;
-    c->gru_on = false; c->gru_wih = c->gru_whh = c->gru_bih = c->gru_bhh = c->h_state = c->h_masked = c->gru_gi = c->gru_gh = c->d_done = nullptr;
-    c->h_ring = c->h_rec_stage = nullptr; c->ev_rec = nullptr; for (bool& b : c->g_rec_ok) b = false;
-    c->gru_train = c->rec_last = false; c->gru_g = c->gru_m = c->gru_v = nullptr; c->gru_sumsq = nullptr;
-    c->rec_x = c->rec_gi = c->rec_sv = c->rec_dgi = c->rec_dgh = c->rec_hm = c->rec_mask = c->rec_h0 = nullptr;
     HIPC(hipDeviceSynchronize());
-    *out = c;
     return 0;
 }
 
-int mi_destroy(mi_ctx* c) {
-    if (!c) return 0;
-    mi_comm_destroy(c);
+// The one teardown, of a context mi_create could not finish as of a live one.
+static void ctx_release(mi_ctx* c) {
     for (int g = 0; g < mi_ctx::MAX_GROUPS; ++g)
         if (c->gw[g]) {
             GroupWorker* w = c->gw[g];
@@ -378,40 +387,22 @@ int mi_destroy(mi_ctx* c) {
             w->th.join(); delete w; c->gw[g] = nullptr;
         }
     for (int g = 0; g < mi_ctx::MAX_GROUPS; ++g) if (c->gs[g]) hipStreamSynchronize(c->gs[g]);
+    if (c->stream) hipStreamSynchronize(c->stream);
     prof_harvest(c);
-    hipStreamSynchronize(c->stream);
-    for (int g = 0; g < mi_ctx::MAX_GROUPS; ++g) if (c->gs[g]) { hipEventDestroy(c->ev_fork[g]); hipEventDestroy(c->ev_join[g]); c->gs[g] = nullptr; }
     g_lanes[c->cfg.device].give_back(c, lane_drop);      // (waited for above; the streams go when the last holder of the device returns its lanes)
-    for (hipEvent_t e : c->prof.pool) hipEventDestroy(e);
-    float* fl[] = {c->params, c->grads, c->adam_m, c->adam_v, c->rew, c->done, c->logp, c->adv, c->ret, c->value, c->obsf,
-                   c->feat, c->dfeat, c->hout, c->dY, c->GC, c->GP[0], c->GP[1], c->GP[2], c->slabs, c->gemm_ws, c->col_ws,
-                   c->fs_scratch, c->fs_val, c->lut, c->stage_obs, c->loss_partial, c->loss_stats, c->loss_log, c->gnorm,
-                   c->d_u, c->d_lp};
-    for (float* p : fl) if (p) hipFree(p);
-    if (c->cfg.arch == MI_ARCH_IMPALA)
-        for (int b = 0; b < 3; ++b) { Block& k = c->blk[b]; hipFree(k.C); hipFree(k.PI); hipFree(k.P0); hipFree(k.A1); hipFree(k.P1); hipFree(k.A2); hipFree(k.P2); }
-    for (float* p : c->mlp_act) if (p) hipFree(p);
-    if (c->frames) hipFree(c->frames);
-    if (c->stage_frames) hipFree(c->stage_frames);
-    hipFree(c->s_act); hipFree(c->s_logp); hipFree(c->s_val);
-    if (c->d_val) hipFree(c->d_val);
-    if (c->fc_wp) hipFree(c->fc_wp); if (c->fc_wt) hipFree(c->fc_wt);
-    if (c->banks) hipFree(c->banks); if (c->d_bank_desc) hipFree(c->d_bank_desc); if (c->c1_bank) hipFree(c->c1_bank);
-    hipFree(c->stats_ring); hipFree(c->fs_ring); hipFree(c->fs_parts); if (c->d_slab_desc) hipFree(c->d_slab_desc); if (c->sal_dc) hipFree(c->sal_dc); if (c->sal_dx) hipFree(c->sal_dx); hipFree(c->d_pack); hipFree(c->d_rd); hipHostFree(c->h_pack); hipHostFree(c->h_rd); hipFree(c->d_done_ctr); if (c->side_stream) hipStreamDestroy(c->side_stream); hipEventDestroy(c->ev_side_fork); hipEventDestroy(c->ev_side_join); hipHostFree(c->h_flag);
-    { float* gr[] = {c->gru_wih, c->gru_whh, c->gru_bih, c->gru_bhh, c->h_state, c->h_masked, c->gru_gi, c->gru_gh, c->d_done, c->gru_x, c->gru_dg}; for (float* q : gr) if (q) hipFree(q); }
-    if (c->h_ring) hipFree(c->h_ring); if (c->h_rec_stage) hipHostFree(c->h_rec_stage); if (c->ev_rec) hipEventDestroy(c->ev_rec);
-    { float* gt[] = {c->gru_g, c->gru_m, c->gru_v, c->rec_x, c->rec_gi, c->rec_sv, c->rec_dgi, c->rec_dgh, c->rec_hm, c->rec_mask, c->rec_h0}; for (float* q : gt) if (q) hipFree(q); }
-    if (c->gru_sumsq) hipFree(c->gru_sumsq);
-    if (c->ipl_idx2) { hipFree(c->ipl_idx2); hipFree(c->ipl_nv); hipFree(c->ipl_gnext); hipFree(c->ipl_pred); hipFree(c->ipl_rew); hipFree(c->ipl_partial); }
-    hipFree(c->act); hipFree(c->adv_stats); hipFree(c->d_idx); hipFree(c->sumsq);
-    if (c->fs_colmax) hipFree(c->fs_colmax); if (c->fs_arg) hipFree(c->fs_arg);
-    if (c->fs_keys) hipFree(c->fs_keys); if (c->fs_keys_local) hipFree(c->fs_keys_local); if (c->d_gpos) hipFree(c->d_gpos); if (c->h_gpos) hipHostFree(c->h_gpos);
-    for (int k = 0; k < mi_ctx::IDX_RING; ++k) { hipHostFree(c->h_idx_ring[k]); hipEventDestroy(c->idx_ev[k]); }
-    hipHostFree(c->h_f); hipHostFree(c->h_i);
+    mi_comm_destroy(c);
+    // Nothing is let go while anything on the device may still read it: the side stream, the null stream's fills and copies and
+    // streams of the caller's are not among the waits above.  (The hand-written teardown had this wait implicitly: its first
+    // release was a hipFree, which waits for the whole device, in front of every pinned buffer and event; the pool releases
+    // newest first, which are pinned buffers and events.)
+    hipDeviceSynchronize();
+    sae_release(c);
+    c->pool.release_all();
+    if (c->side_stream) hipStreamDestroy(c->side_stream);
     if (c->own_stream) hipStreamDestroy(c->stream);
     delete c;
-    return 0;
 }
+int mi_destroy(mi_ctx* c) { if (c) ctx_release(c); return 0; }
 
 void* mi_host_alloc(size_t bytes) {
     void* p = nullptr;
@@ -444,19 +435,19 @@ int mi_copy_params(mi_ctx* dst, mi_ctx* src) {
     ARG(dst->cfg.arch == src->cfg.arch && dst->n_params == src->n_params && dst->A == src->A && dst->H == src->H && dst->cfg.device == src->cfg.device,
         "contexts of different architecture / size / device");
     hipEvent_t ready = nullptr, done = nullptr;
-    HIPC(hipEventCreateWithFlags(&ready, hipEventDisableTiming)); HIPC(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+    DevPool evs(hip_pool());                                        // both events go on every return path (the runtime releases them once they have completed)
+    HIPC(evs.event(&ready, hipEventDisableTiming)); HIPC(evs.event(&done, hipEventDisableTiming));
     HIPC(hipEventRecord(ready, src->stream));                      // the optimizer step that wrote src's parameters
     HIPC(hipStreamWaitEvent(dst->stream, ready, 0));
     HIPC(hipMemcpyAsync(dst->params, src->params, (size_t)src->n_params * 4, hipMemcpyDeviceToDevice, dst->stream));
     if (src->gru_train) {          // a trained GRU is part of the policy: the twin acts with the weights the optimizer just wrote
-        if (!dst->gru_on) { hipEventDestroy(ready); hipEventDestroy(done); return fail(-1, "invalid argument: the source trains its GRU but the destination has none (mi_set_gru)"); }
+        if (!dst->gru_on) return fail(-1, "invalid argument: the source trains its GRU but the destination has none (mi_set_gru)");
         const GruTensors from = gru_tensors(src), to = gru_tensors(dst);
         for (int k = 0; k < 4; ++k) HIPC(hipMemcpyAsync(to.t[k].p, from.t[k].p, from.t[k].len * 4, hipMemcpyDeviceToDevice, dst->stream));
     }
     HIPC(hipEventRecord(done, dst->stream));
     HIPC(hipStreamWaitEvent(src->stream, done, 0));                // src's next optimizer step must not overtake the copy
     dst->fc_packed_valid = false;                                  // packed bf16 filter images are rebuilt before dst's next pass
-    HIPC(hipEventDestroy(ready)); HIPC(hipEventDestroy(done));     // (released by the runtime once they have completed)
     return 0;
 }
 int mi_get_grads(mi_ctx* c, float* flat, int64_t n) { ARG(c && flat, "null"); return download_flat(c, c->grads, flat, n); }
@@ -548,10 +539,11 @@ int mi_write_field(mi_ctx* c, int32_t f, const float* in, int64_t n) {
 
 // ------------------------------------------------------------------------------------------ profiler
 static hipEvent_t prof_event(mi_ctx* c) {
-    hipEvent_t e;
+    hipEvent_t e = nullptr;
     if (!c->prof.pool.empty()) { e = c->prof.pool.back(); c->prof.pool.pop_back(); return e; }
-    hipEventCreate(&e);
-    return e;
+    c->prof.made.emplace_back();                 // (a deque: the context's pool keeps the address of what it hands out)
+    c->pool.event(&c->prof.made.back(), hipEventDefault);
+    return c->prof.made.back();
 }
 static void prof_harvest(mi_ctx* c) {
     if (c->prof.pend.empty()) return;
@@ -1254,9 +1246,11 @@ int mi_rollout_groups(mi_ctx* c, int32_t n_groups) {
         return fail(-2, "no stream for an env group (hipStreamCreateWithPriority failed)");
     for (int g = 0; g < n_groups; ++g)
         if (!c->gs[g]) {
+            DevPool::Group both(c->pool);
+            HIPC(c->pool.event(&c->ev_fork[g], hipEventDisableTiming));
+            HIPC(c->pool.event(&c->ev_join[g], hipEventDisableTiming));
+            both.keep = true;
             c->gs[g] = (hipStream_t)lane[g]; c->gs_prio[g] = prio[g];
-            HIPC(hipEventCreateWithFlags(&c->ev_fork[g], hipEventDisableTiming));
-            HIPC(hipEventCreateWithFlags(&c->ev_join[g], hipEventDisableTiming));
             c->gw[g] = new GroupWorker();
             c->gw[g]->th = std::thread(group_worker_main, c, g);
         }
@@ -1385,7 +1379,7 @@ int mi_value_saliency(mi_ctx* c, const void* obs, size_t bytes, uint64_t seed, u
     InputSrc src{stage, nullptr, 0};
     c->prof.phase = 0;
     const bool rec = c->gru_on;
-    if (rec && !c->gru_x) { HIPC(dalloc(&c->gru_x, (size_t)E * c->H)); HIPC(dalloc(&c->gru_dg, (size_t)E * 3 * c->H)); }
+    if (rec && !c->gru_x) { DevPool::Group both(c->pool); HIPC(c->pool.dev(&c->gru_x, (size_t)E * c->H)); HIPC(c->pool.dev(&c->gru_dg, (size_t)E * 3 * c->H)); both.keep = true; }
     c->sal_keep_x = rec;
     net_forward(c, src, E, {.recurrent = rec, .train = true});          // recurrent: h' = GRU(embedder output, h (1 - done)) as a policy step does, heads on h'
     c->sal_keep_x = false;
@@ -1411,11 +1405,11 @@ int mi_value_saliency(mi_ctx* c, const void* obs, size_t bytes, uint64_t seed, u
     }
     ARG(c->sal_src, "backward did not reach the first layer");
     const size_t gfloats = impala ? (size_t)E * 64 * 64 * 3 : (size_t)E * c->cfg.obs_dim;
-    if (!c->sal_dx) HIPC(dalloc(&c->sal_dx, impala ? (size_t)c->NB * 64 * 64 * 3 : (size_t)c->NB * c->cfg.obs_dim));
+    if (!c->sal_dx) HIPC(c->pool.dev(&c->sal_dx, impala ? (size_t)c->NB * 64 * 64 * 3 : (size_t)c->NB * c->cfg.obs_dim));
     if (impala) {
         const void* dC = c->sal_src;
         if (c->bf) {                                       // the conv-output gradient is not materialised in bf16 mode: rebuild it from the pooled one
-            if (!c->sal_dc) HIPC(hipMalloc(&c->sal_dc, (size_t)c->NB * 64 * 64 * 16 * 2 + 256));
+            if (!c->sal_dc) HIPC(c->pool.dev_raw(&c->sal_dc, (size_t)c->NB * 64 * 64 * 16 * 2 + 256));
             launch_maxpool_bwd_bf16(c->sal_src, c->blk[0].PI, c->sal_dc, E, 64, 16, c->stream);
             dC = c->sal_dc;
         }
@@ -1446,9 +1440,11 @@ int mi_set_gru(mi_ctx* c, const float* w_ih, const float* w_hh, const float* b_i
     ARG(c && w_ih && w_hh && b_ih && b_hh, "null"); JOIN(c);
     const size_t H = c->H, E = c->E;
     if (!c->gru_wih) {
-        HIPC(dalloc(&c->gru_wih, 3 * H * H)); HIPC(dalloc(&c->gru_whh, 3 * H * H)); HIPC(dalloc(&c->gru_bih, 3 * H)); HIPC(dalloc(&c->gru_bhh, 3 * H));
-        HIPC(dalloc(&c->h_state, E * H)); HIPC(dalloc(&c->h_masked, E * H)); HIPC(dalloc(&c->gru_gi, E * 3 * H)); HIPC(dalloc(&c->gru_gh, E * 3 * H));
-        HIPC(dalloc(&c->d_done, E));
+        DevPool& m = c->pool; DevPool::Group all(m);
+        HIPC(m.dev(&c->gru_wih, 3 * H * H)); HIPC(m.dev(&c->gru_whh, 3 * H * H)); HIPC(m.dev(&c->gru_bih, 3 * H)); HIPC(m.dev(&c->gru_bhh, 3 * H));
+        HIPC(m.dev(&c->h_state, E * H)); HIPC(m.dev(&c->h_masked, E * H)); HIPC(m.dev(&c->gru_gi, E * 3 * H)); HIPC(m.dev(&c->gru_gh, E * 3 * H));
+        HIPC(m.dev(&c->d_done, E));
+        all.keep = true;
     }
     const GruTensors g = gru_tensors(c);
     const float* src[4] = {w_ih, w_hh, b_ih, b_hh};
@@ -1469,9 +1465,11 @@ int mi_rec_begin(mi_ctx* c, const float* hidden, const float* done) {
     ARG(c, "null"); JOIN(c); ARG(c->gru_on, "no GRU set: call mi_set_gru first");
     const size_t H = c->H, E = c->E;
     if (!c->h_ring) {                                     // only contexts that run grouped recurrent rollouts pay for the ring (67 MB at T = E = H = 256)
-        HIPC(dalloc(&c->h_ring, (size_t)(c->T + 1) * E * H));
-        HIPC(hipHostMalloc((void**)&c->h_rec_stage, (E * H + E) * 4, hipHostMallocDefault));
-        HIPC(hipEventCreateWithFlags(&c->ev_rec, hipEventDisableTiming));
+        DevPool& m = c->pool; DevPool::Group all(m);
+        HIPC(m.dev(&c->h_ring, (size_t)(c->T + 1) * E * H));
+        HIPC(m.pinned(&c->h_rec_stage, (E * H + E) * 4, hipHostMallocDefault));
+        HIPC(m.event(&c->ev_rec, hipEventDisableTiming));
+        all.keep = true;
     } else
         HIPC(hipEventSynchronize(c->ev_rec));             // the previous call's upload has left the staging buffer (long since, normally)
     if (hidden) {
@@ -1734,8 +1732,10 @@ int mi_minibatch_finish(mi_ctx* c) {
 static int ipl_alloc(mi_ctx* c) {
     if (c->ipl_idx2) return 0;
     const size_t NB = c->NB;
-    HIPC(dalloc(&c->ipl_idx2, NB)); HIPC(dalloc(&c->ipl_nv, NB)); HIPC(dalloc(&c->ipl_gnext, NB)); HIPC(dalloc(&c->ipl_pred, NB)); HIPC(dalloc(&c->ipl_rew, NB));
-    HIPC(dalloc(&c->ipl_partial, (size_t)ipl_blocks(c->NB) * ipl_partial_cols(c->A)));
+    DevPool& m = c->pool; DevPool::Group all(m);
+    HIPC(m.dev(&c->ipl_idx2, NB)); HIPC(m.dev(&c->ipl_nv, NB)); HIPC(m.dev(&c->ipl_gnext, NB)); HIPC(m.dev(&c->ipl_pred, NB)); HIPC(m.dev(&c->ipl_rew, NB));
+    HIPC(m.dev(&c->ipl_partial, (size_t)ipl_blocks(c->NB) * ipl_partial_cols(c->A)));
+    all.keep = true;
     return 0;
 }
 int mi_ipl_minibatch(mi_ctx* c, const int64_t* idx, int32_t n, int32_t n_global, const mi_ipl_hparams* hp) {
@@ -1830,10 +1830,12 @@ int mi_gru_train(mi_ctx* c, int32_t enabled) {
     ARG(!enabled || gru_seq_width_ok(c->H), "GRU training needs a width (out_dim) that is a multiple of 64 in [64, 512]");
     if (enabled && !c->gru_g) {
         const size_t G = (size_t)gru_count(c), NB = c->NB, H = c->H;
-        HIPC(dalloc(&c->gru_g, G)); HIPC(dalloc(&c->gru_m, G)); HIPC(dalloc(&c->gru_v, G)); HIPC(dalloc(&c->gru_sumsq, (size_t)256));
-        HIPC(dalloc(&c->rec_x, NB * H)); HIPC(dalloc(&c->rec_gi, NB * 3 * H)); HIPC(dalloc(&c->rec_sv, NB * 4 * H));
-        HIPC(dalloc(&c->rec_dgi, NB * 3 * H)); HIPC(dalloc(&c->rec_dgh, NB * 3 * H)); HIPC(dalloc(&c->rec_hm, NB * H));
-        HIPC(dalloc(&c->rec_mask, NB)); HIPC(dalloc(&c->rec_h0, NB * H));
+        DevPool& m = c->pool; DevPool::Group all(m);
+        HIPC(m.dev(&c->gru_g, G)); HIPC(m.dev(&c->gru_m, G)); HIPC(m.dev(&c->gru_v, G)); HIPC(m.dev(&c->gru_sumsq, (size_t)256));
+        HIPC(m.dev(&c->rec_x, NB * H)); HIPC(m.dev(&c->rec_gi, NB * 3 * H)); HIPC(m.dev(&c->rec_sv, NB * 4 * H));
+        HIPC(m.dev(&c->rec_dgi, NB * 3 * H)); HIPC(m.dev(&c->rec_dgh, NB * 3 * H)); HIPC(m.dev(&c->rec_hm, NB * H));
+        HIPC(m.dev(&c->rec_mask, NB)); HIPC(m.dev(&c->rec_h0, NB * H));
+        all.keep = true;
     }
     HIPC(hipStreamSynchronize(c->stream));
     c->gru_train = enabled != 0;
@@ -1951,6 +1953,7 @@ int mi_comm_init(mi_ctx* c, const void* id_bytes, size_t bytes, int32_t rank, in
     HIPC(hipSetDevice(c->cfg.device));
     ncclUniqueId id;
     memcpy(&id, id_bytes, sizeof id);
+    struct Undo { mi_ctx* c; bool keep = false; ~Undo() { if (!keep) mi_comm_destroy(c); } } undo{c};      // a failure below releases what it got
     NCCLC(ncclCommInitRank(&c->comm, world, id, rank));
     // The gradient regions travel on a side stream while the main stream may issue its own collectives (loss statistics, feature-
     // sparsity keys, advantage statistics).  One communicator driven from two streams has no defined order between the two streams'
@@ -1959,18 +1962,21 @@ int mi_comm_init(mi_ctx* c, const void* id_bytes, size_t bytes, int32_t rank, in
     NCCLC(ncclCommSplit(c->comm, 0, rank, &c->comm_grad, nullptr));
     c->comm_world = world; c->comm_rank = rank;
     HIPC(hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
-    HIPC(hipEventCreateWithFlags(&c->ev_ar_ready, hipEventDisableTiming));
-    HIPC(hipEventCreateWithFlags(&c->ev_ar_done, hipEventDisableTiming));
-    HIPC(dalloc(&c->adv_all, (size_t)3 * world + 4));
+    HIPC(c->comm_pool.event(&c->ev_ar_ready, hipEventDisableTiming));
+    HIPC(c->comm_pool.event(&c->ev_ar_done, hipEventDisableTiming));
+    HIPC(c->comm_pool.dev(&c->adv_all, (size_t)3 * world + 4));
+    undo.keep = true;
     return 0;
 }
-int mi_comm_destroy(mi_ctx* c) {
+int mi_comm_destroy(mi_ctx* c) {      // (also of a communicator mi_comm_init got only halfway through)
     if (!c || !c->comm) return 0;
-    hipStreamSynchronize(c->comm_stream); hipStreamSynchronize(c->stream);
+    if (c->comm_stream) hipStreamSynchronize(c->comm_stream);
+    hipStreamSynchronize(c->stream);
     if (c->comm_grad) { ncclCommDestroy(c->comm_grad); c->comm_grad = nullptr; }
     ncclCommDestroy(c->comm); c->comm = nullptr;
-    hipStreamDestroy(c->comm_stream); hipEventDestroy(c->ev_ar_ready); hipEventDestroy(c->ev_ar_done);
-    hipFree(c->adv_all); c->adv_all = nullptr; c->comm_world = 1; c->comm_rank = 0;
+    c->comm_pool.release_all();
+    if (c->comm_stream) { hipStreamDestroy(c->comm_stream); c->comm_stream = nullptr; }
+    c->comm_world = 1; c->comm_rank = 0;
     c->ar_armed = c->ar_issued = c->ar_inflight = false;
     return 0;
 }

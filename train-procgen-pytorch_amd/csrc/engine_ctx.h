@@ -3,6 +3,7 @@
 // plumbing, and the few engine.hip functions the op code calls.
 #pragma once
 #include "common.h"
+#include "devpool.h"
 #include "../../include/mi355ppo.h"
 #include <rccl/rccl.h>
 #include <math.h>
@@ -14,6 +15,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <deque>
 #include <mutex>
 #include <thread>
 
@@ -31,7 +33,7 @@ static inline int fail(int code, const std::string& msg) { g_err = msg; return c
 
 #define HIPC(x)                                                                                          \
     do {                                                                                                 \
-        hipError_t e_ = (x);                                                                             \
+        hipError_t e_ = (hipError_t)(x);      /* (the pool's calls return the backend's code as an int) */ \
         if (e_ != hipSuccess)                                                                            \
             return fail(-2, std::string(#x) + ": " + hipGetErrorString(e_) + " @" + std::to_string(__LINE__)); \
     } while (0)
@@ -49,8 +51,8 @@ struct TensorDesc {
     int kind, co, ci;
 };
 
-struct ConvLayer { ConvShape shape; int64_t w_off, b_off; int cin, cout, hw; long long bank_f, bank_d; };   // bank offsets (bf16 mode) or -1
-struct Block { float *C, *P0, *A1, *P1, *A2, *P2; uint8_t* PI; int cin, cout, hin; };   // activation buffers hold fp32 or bf16 (ctx.bf)
+struct ConvLayer { ConvShape shape; int64_t w_off, b_off; int cin, cout, hw; long long bank_f = -1, bank_d = -1; };   // bank offsets (bf16 mode) or -1
+struct Block { float *C = nullptr, *P0 = nullptr, *A1 = nullptr, *P1 = nullptr, *A2 = nullptr, *P2 = nullptr; uint8_t* PI = nullptr; int cin = 0, cout = 0, hin = 0; };   // activation buffers hold fp32 or bf16 (ctx.bf)
 struct Linear { int64_t w_off, b_off; int in, out; };
 
 // ---- live kernel timing (bench.py roofline leg)
@@ -63,109 +65,116 @@ struct Profiler {
     int period = 1, mb_count = 0;  // update phase: bracket every period-th minibatch (two event records per launch cost ~7 us of
     bool sample_now = true;        // stream time: 11 ms per hard-500 iteration when every launch is bracketed)
     std::vector<ProfPending> pend;
-    std::vector<hipEvent_t> pool;
+    std::vector<hipEvent_t> pool;      // idle events
+    std::deque<hipEvent_t> made;       // every event made so far (owned by the context's pool, like all its events)
     double ms[2][PC_COUNT] = {};
     long long launches[2][PC_COUNT] = {}, units[2][PC_COUNT] = {};
     double bytes[2][PC_COUNT] = {}, flops[2][PC_COUNT] = {};
 };
 
+MI_INTERNAL const DevPool::Backend* hip_pool();      // engine.hip: hipMalloc / hipHostMalloc / hipEventCreateWithFlags and their frees, counted
 struct mi_ctx {
     Profiler prof;
-    mi_config cfg;
-    hipStream_t stream;
-    bool own_stream;
-    int T, E, A, H, NB;
-    bool bf;              // IMPALA activations / activation gradients stored as bf16 (mi_config.precision == 1)
-    double es;            // bytes per activation element
-    int64_t n_params;
+    mi_config cfg = {};
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    int T = 0, E = 0, A = 0, H = 0, NB = 0;
+    bool bf = false;      // IMPALA activations / activation gradients stored as bf16 (mi_config.precision == 1)
+    double es = 4.0;      // bytes per activation element
+    int64_t n_params = 0;
     std::vector<TensorDesc> tensors;
-    float *params, *grads, *adam_m, *adam_v;
+    float *params = nullptr, *grads = nullptr, *adam_m = nullptr, *adam_v = nullptr;
     // rollout
-    uint8_t* frames;      // impala
-    float* obsf;          // mlp
-    size_t obs_bytes_per_env;
-    float *rew, *done, *logp, *adv, *ret, *value;
-    int32_t* act;
-    double* adv_stats;
+    uint8_t* frames = nullptr;      // impala
+    float* obsf = nullptr;          // mlp
+    size_t obs_bytes_per_env = 0;
+    float *rew = nullptr, *done = nullptr, *logp = nullptr, *adv = nullptr, *ret = nullptr, *value = nullptr;
+    int32_t* act = nullptr;
+    double* adv_stats = nullptr;
     // network
     std::vector<ConvLayer> convs;
     Block blk[3];
-    Linear fc;            // impala fc 2048->H (output_dim)
+    Linear fc = {};          // impala fc 2048->H (output_dim)
     std::vector<Linear> mlp;
     std::vector<float*> mlp_act;   // X0 (input), h1..hL
-    int64_t wh_off, bh_off;        // heads: (A+1) x H weights, (A+1) bias (device order)
-    float *feat, *hout, *dY, *dfeat, *GC, *GP[3];
+    int64_t wh_off = 0, bh_off = 0;        // heads: (A+1) x H weights, (A+1) bias (device order)
+    float *feat = nullptr, *hout = nullptr, *dY = nullptr, *dfeat = nullptr, *GC = nullptr, *GP[3] = {};
     int lse = 0; float* d_val = nullptr;                  // value_from_logits (common/policy.py:77-78); d_val: mi_forward's values [NB] in that mode
-    float* slabs; size_t slab_floats;
-    void* sal_dc; float* sal_dx; const float* sal_src;       // value saliency: conv-out gradient temp (bf16 mode), input gradient, where net_backward left block 1's gradient
-    long long slab_off[15]; SlabDesc h_slab_desc[15]; SlabDesc* d_slab_desc; int slab_desc_n, slab_desc_cached_n;   // per-layer slab regions; ONE reduce launch per backward pass
-    float *gemm_ws, *col_ws, *fs_scratch, *fs_val; size_t gemm_ws_floats;      // split-K / column-sum workspaces: per context
-    float* lut;
-    unsigned short* lut16;     // uint8 -> bf16(k/255) table (bf16 mode, block1.conv)
-    uint8_t* stage_frames; float* stage_obs;
-    int32_t* d_idx;
-    float *loss_partial, *loss_stats, *loss_log; int log_count, log_cap;
-    double* fs_parts;                                     // [MI_MAX_SEG][8] column-block sums of the feature-sparsity metric
-    float *stats_ring, *fs_ring; LossArgs ring_args;      // multirank mode 2: per-minibatch raw stats [log_cap][32] (+ rank-local fs), finalised after ONE all-reduce
-    double* sumsq; float* gnorm;
-    float* d_u; float* d_lp;
-    unsigned short* banks; BankDesc* d_bank_desc; int n_banks;   // bf16 mode: pre-packed conv filter banks
-    unsigned short* c1_bank;                                   // bf16 mode: block1.conv forward bank (conv1 kernels' LDS layout)
-    unsigned short *fc_wp, *fc_wt;            // bf16 mode: packed fc.weight images ([H][2048] and [2048][H])
-    bool fc_packed_valid;
-    float *d_pack, *h_pack, *h_rd, *d_rd;     // packed rollout read-back {act,logp,value} x E ; packed {rew,done} upload
-    unsigned *d_done_ctr, *h_flag, roll_ticket;   // rollout step: workgroup counter, host-visible completion ticket (heads_sample_kernel)
-    int32_t* s_act; float *s_logp, *s_val; bool staged_valid;
+    float* slabs = nullptr; size_t slab_floats = 0;
+    void* sal_dc = nullptr; float* sal_dx = nullptr; const float* sal_src = nullptr;       // value saliency: conv-out gradient temp (bf16 mode), input gradient, where net_backward left block 1's gradient
+    long long slab_off[15] = {}; SlabDesc h_slab_desc[15] = {}; SlabDesc* d_slab_desc = nullptr; int slab_desc_n = 0, slab_desc_cached_n = -1;   // per-layer slab regions; ONE reduce launch per backward pass
+    float *gemm_ws = nullptr, *col_ws = nullptr, *fs_scratch = nullptr, *fs_val = nullptr; size_t gemm_ws_floats = 0;      // split-K / column-sum workspaces: per context
+    float* lut = nullptr;
+    unsigned short* lut16 = nullptr;     // uint8 -> bf16(k/255) table (bf16 mode, block1.conv)
+    uint8_t* stage_frames = nullptr; float* stage_obs = nullptr;
+    int32_t* d_idx = nullptr;
+    float *loss_partial = nullptr, *loss_stats = nullptr, *loss_log = nullptr; int log_count = 0, log_cap = 4096;
+    double* fs_parts = nullptr;                                     // [MI_MAX_SEG][8] column-block sums of the feature-sparsity metric
+    float *stats_ring = nullptr, *fs_ring = nullptr; LossArgs ring_args = {};      // multirank mode 2: per-minibatch raw stats [log_cap][32] (+ rank-local fs), finalised after ONE all-reduce
+    double* sumsq = nullptr; float* gnorm = nullptr;
+    float* d_u = nullptr; float* d_lp = nullptr;
+    unsigned short* banks = nullptr; BankDesc* d_bank_desc = nullptr; int n_banks = 0;   // bf16 mode: pre-packed conv filter banks
+    unsigned short* c1_bank = nullptr;                                   // bf16 mode: block1.conv forward bank (conv1 kernels' LDS layout)
+    unsigned short *fc_wp = nullptr, *fc_wt = nullptr;            // bf16 mode: packed fc.weight images ([H][2048] and [2048][H])
+    bool fc_packed_valid = false;
+    float *d_pack = nullptr, *h_pack = nullptr, *h_rd = nullptr, *d_rd = nullptr;     // packed rollout read-back {act,logp,value} x E ; packed {rew,done} upload
+    unsigned *d_done_ctr = nullptr, *h_flag = nullptr, roll_ticket = 0;   // rollout step: workgroup counter, host-visible completion ticket (heads_sample_kernel)
+    int32_t* s_act = nullptr; float *s_logp = nullptr, *s_val = nullptr; bool staged_valid = false;
     // recurrent rollout (GRU cell, never trained)
-    bool gru_on; float *gru_wih, *gru_whh, *gru_bih, *gru_bhh, *h_state, *h_masked, *gru_gi, *gru_gh, *d_done;
-    float *gru_x, *gru_dg; bool sal_keep_x, bwd_from_dfeat;      // value saliency through the GRU: the cell's input (embedder output), d gates; net_backward starts at dfeat
+    bool gru_on = false; float *gru_wih = nullptr, *gru_whh = nullptr, *gru_bih = nullptr, *gru_bhh = nullptr, *h_state = nullptr, *h_masked = nullptr, *gru_gi = nullptr, *gru_gh = nullptr, *d_done = nullptr;
+    float *gru_x = nullptr, *gru_dg = nullptr; bool sal_keep_x = false, bwd_from_dfeat = false;      // value saliency through the GRU: the cell's input (embedder output), d gates; net_backward starts at dfeat
     // pinned host staging
     // index staging ring: a slot is rewritten only after the H2D copy that read it has completed
     static constexpr int IDX_RING = 32;
-    int32_t* h_idx_ring[IDX_RING]; hipEvent_t idx_ev[IDX_RING]; bool idx_used[IDX_RING]; int idx_next, idx_ev_deferred;
-    float* h_f; int32_t* h_i; size_t h_f_floats;
-    int multirank;
-    LossArgs pending; int pending_n;
+    int32_t* h_idx_ring[IDX_RING] = {}; hipEvent_t idx_ev[IDX_RING] = {}; bool idx_used[IDX_RING] = {}; int idx_next = 0, idx_ev_deferred = -1;
+    float* h_f = nullptr; int32_t* h_i = nullptr; size_t h_f_floats = 0;
+    int multirank = 0;
+    LossArgs pending = {}; int pending_n = -1;
     // pipelined rollout (mi_rollout_submit / mi_rollout_wait): contiguous env groups, each on its own stream with its own rows of the
     // activation buffers, so that one group's frame upload + forward runs beside the host's wait for another group's actions
     static constexpr int MAX_GROUPS = 4;
     // gs[g]: a lane borrowed from the process-wide registry (lanes.h, g_lanes in engine.hip), never a stream of the context's own
-    int n_groups; hipStream_t main_stream, gs[MAX_GROUPS]; int gs_prio[MAX_GROUPS]; hipEvent_t ev_fork[MAX_GROUPS], ev_join[MAX_GROUPS];
-    bool g_forked[MAX_GROUPS], g_busy[MAX_GROUPS], g_last[MAX_GROUPS], g_dirty[MAX_GROUPS]; unsigned g_ticket[MAX_GROUPS]; bool groups_live;
-    struct GroupWorker* gw[MAX_GROUPS];      // one host thread per group issues that group's copies + launches (a step is ~9 API calls = ~30 us of host time)
-    std::atomic<int64_t> copy_slot_ns{0}; double copy_rate_bytes_per_us;      // uploads of the env groups take turns on the PCIe link (group_issue)
-    std::unordered_map<const void*, bool> pull_ok; bool no_pull;      // frame buffers a kernel may read (mi_debug_flags bit 2: always DMA)
+    int n_groups = 1; hipStream_t main_stream = nullptr, gs[MAX_GROUPS] = {}; int gs_prio[MAX_GROUPS] = {}; hipEvent_t ev_fork[MAX_GROUPS] = {}, ev_join[MAX_GROUPS] = {};
+    bool g_forked[MAX_GROUPS] = {}, g_busy[MAX_GROUPS] = {}, g_last[MAX_GROUPS] = {}, g_dirty[MAX_GROUPS] = {}; unsigned g_ticket[MAX_GROUPS] = {}; bool groups_live = false;
+    struct GroupWorker* gw[MAX_GROUPS] = {};      // one host thread per group issues that group's copies + launches (a step is ~9 API calls = ~30 us of host time)
+    std::atomic<int64_t> copy_slot_ns{0}; double copy_rate_bytes_per_us = 40000.0;      // uploads of the env groups take turns on the PCIe link (group_issue)
+    std::unordered_map<const void*, bool> pull_ok; bool no_pull = false;      // frame buffers a kernel may read (mi_debug_flags bit 2: always DMA)
     // Side stream of a minibatch pass: the logged statistics (feature-sparsity metric, loss records) and embedder.fc's weight / bias
     // gradients are needed by nobody before the optimizer step, so they run beside the backward pass instead of in front of it
     // (seven small launches + fc_tn: ~65 us of kernels per 2.7 ms minibatch, of which the update gets ~15 us back -- 64.6 -> 64.2 ms per
     // iteration, same-box A/B by the debug flag: fc_tn and the column maxima are real work that now shares the machine with fc_dgrad).
     // Fork after heads_bwd, join in front of the slab sums.
-    hipStream_t side_stream; hipEvent_t ev_side_fork, ev_side_join;
-    bool side_on;               // mi_debug_flags bit 4 clears it (A/B tests)
-    struct SideJob { bool armed; LossArgs a; SegTab st; int mode; float* ring; float* fsr; float* log; } side;
-    bool rollout_tail;          // bf16 inference passes of <= 256 samples run blocks 2 + 3 as one launch (mi_debug_flags bit 0 clears it: A/B tests)
-    float *fs_colmax, fs_grad_coef; int *fs_arg, fs_G;      // feature-sparsity gradient (fs_coef != 0): column maxima / first arg-max rows of the minibatch
+    hipStream_t side_stream = nullptr; hipEvent_t ev_side_fork = nullptr, ev_side_join = nullptr;
+    bool side_on = true;           // mi_debug_flags bit 4 clears it (A/B tests)
+    struct SideJob { bool armed; LossArgs a; SegTab st; int mode; float* ring; float* fsr; float* log; } side = {};
+    bool rollout_tail = true;          // bf16 inference passes of <= 256 samples run blocks 2 + 3 as one launch (mi_debug_flags bit 0 clears it: A/B tests)
+    float *fs_colmax = nullptr, fs_grad_coef = 0.f; int *fs_arg = nullptr, fs_G = 0;      // feature-sparsity gradient (fs_coef != 0): column maxima / first arg-max rows of the minibatch
     // ... on more than one rank (multirank mode 1): per-column candidates for the max-all-reduce (MI_PTR_FS_KEYS), this rank's own copy, and
     // the global minibatch positions of the pending pass's rows (mi_minibatch_positions)
-    long long *fs_keys, *fs_keys_local; int32_t *d_gpos, *h_gpos; int gpos_n; bool fs_global_pending, fs_global_apply;
-    // data-parallel collectives (RCCL over xGMI), SURVEY 8(e): one communicator per context, a side stream for the gradient all-reduce
-    ncclComm_t comm, comm_grad; int comm_world, comm_rank; hipStream_t comm_stream; hipEvent_t ev_ar_ready, ev_ar_done;   // comm: main-stream collectives; comm_grad: the side stream's
-    bool ar_armed, ar_issued, ar_inflight; double* adv_all;
+    long long *fs_keys = nullptr, *fs_keys_local = nullptr; int32_t *d_gpos = nullptr, *h_gpos = nullptr; int gpos_n = -1; bool fs_global_pending = false, fs_global_apply = false;
+    // data-parallel collectives (RCCL over xGMI), SURVEY 8(e): one communicator per context, a side stream for the gradient all-reduce;
+    // mi_comm_init / mi_comm_destroy may be repeated on one context, so what they allocate has a pool of its own
+    ncclComm_t comm = nullptr, comm_grad = nullptr; int comm_world = 1, comm_rank = 0; hipStream_t comm_stream = nullptr; hipEvent_t ev_ar_ready = nullptr, ev_ar_done = nullptr;   // comm: main-stream collectives; comm_grad: the side stream's
+    bool ar_armed = false, ar_issued = false, ar_inflight = false; double* adv_all = nullptr;
     std::string net_err; std::mutex net_err_mu;   // set by the (void) network program on an unsupported launch (any thread); every entry point reports it as -4
     // recurrent policies on the pipelined rollout (mi_rec_begin, group_issue): hidden ring [T+1][E][H] -- slot t = the input hidden state of step t (slot 0 from
     // mi_rec_begin, slot t+1 written by step t's fused cell); pinned staging of mi_rec_begin's upload {hidden [E][H], done [E]} and the event
     // that frees it; g_rec_ok[g]: mi_rec_begin has run since group g last started a rollout (t == 0)
-    float *h_ring, *h_rec_stage; hipEvent_t ev_rec; bool g_rec_ok[MAX_GROUPS];
+    float *h_ring = nullptr, *h_rec_stage = nullptr; hipEvent_t ev_rec = nullptr; bool g_rec_ok[MAX_GROUPS] = {};
     // GRU training (mi_gru_train, mi_minibatch_rec: algo ppo-pure): gradients and Adam moments of the four GRU tensors as ONE vector
     // {w_ih, w_hh, b_ih, b_hh} beside the flat ones, the partial sums of the global gradient norm (128 flat + 128 GRU), and the buffers of a
     // recurrent minibatch pass, max_batch rows each: the embedder output x (the sequence forward overwrites feat with h_t), gi, the saved
     // gates, dgi / dgh, the masked input states, the masks 1 - done and the minibatch's initial states
-    bool gru_train, rec_last; float *gru_g, *gru_m, *gru_v; double* gru_sumsq;
-    float *rec_x, *rec_gi, *rec_sv, *rec_dgi, *rec_dgh, *rec_hm, *rec_mask, *rec_h0;
+    bool gru_train = false, rec_last = false; float *gru_g = nullptr, *gru_m = nullptr, *gru_v = nullptr; double* gru_sumsq = nullptr;
+    float *rec_x = nullptr, *rec_gi = nullptr, *rec_sv = nullptr, *rec_dgi = nullptr, *rec_dgh = nullptr, *rec_hm = nullptr, *rec_mask = nullptr, *rec_h0 = nullptr;
     // IPL (mi_ipl_minibatch; allocated by its first call, max_batch rows each): ring rows of obs[t + 1], next values, d loss / d nv, the last
     // minibatch's pred / reward, the loss kernel's fp64 block partials
     int32_t* ipl_idx2 = nullptr; float *ipl_nv = nullptr, *ipl_gnext = nullptr, *ipl_pred = nullptr, *ipl_rew = nullptr; double* ipl_partial = nullptr;
     int ipl_last_n = 0;
+    struct mi_sae* sae = nullptr;      // the sparse-autoencoder agent's state (sae.hip: mi_sae_create; released by mi_sae_destroy or mi_destroy)
+    // Every device buffer, pinned buffer and event above belongs to a pool (declared last: destroyed first, while the pointers it
+    // nulls still exist).  ctx_release is the one place that lets go of them.
+    DevPool pool{hip_pool()}, comm_pool{hip_pool()};
 };
 
 static inline char* obs_ring(mi_ctx* c) { return c->frames ? (char*)c->frames : (char*)c->obsf; }      // rollout observations [(T+1)][E]: uint8 frames or fp32 rows
@@ -173,6 +182,7 @@ static inline char* obs_ring(mi_ctx* c) { return c->frames ? (char*)c->frames : 
 // ------------------------------------------------------------------------------------------ engine.hip functions the op code calls
 MI_INTERNAL std::string net_err_take(mi_ctx* c);                 // (the network program also runs on the env-group worker threads: guarded)
 MI_INTERNAL void net_err_set(mi_ctx* c, const std::string& m);
+MI_INTERNAL void sae_release(mi_ctx* c);                         // (defined in sae.hip; mi_destroy releases a live SAE through it)
 MI_INTERNAL int join_groups(mi_ctx* c);
 MI_INTERNAL void to_device_layout(const TensorDesc& t, const float* ref, float* dev);
 MI_INTERNAL void to_ref_layout(const TensorDesc& t, const float* dev, float* ref);
@@ -186,13 +196,3 @@ MI_INTERNAL void net_forward(mi_ctx* c, const InputSrc& src, int n, const FwdOpt
 MI_INTERNAL void linear_fwd(mi_ctx* c, const float* X, int relu_x, const float* W, const float* b, float* Y, int n, int in, int out, int relu_out, int x_bf16 = 0);
 MI_INTERNAL void linear_dgrad(mi_ctx* c, const float* dY, const float* W, const float* mask, float* dX, int n, int in, int out, int x_bf16 = 0);
 MI_INTERNAL void linear_wgrad(mi_ctx* c, const float* dY, const float* X, int relu_x, float* gW, float* gb, int n, int in, int out, int x_bf16 = 0);
-
-template <typename T>
-static hipError_t dalloc(T** p, size_t count) {
-    hipError_t e = hipMalloc((void**)p, count * sizeof(T) + 256);
-    if (e == hipSuccess) e = hipMemset(*p, 0, count * sizeof(T) + 256);
-    // hipMemset is asynchronous on the NULL stream and the context's stream is non-blocking: without this wait a
-    // kernel launched right after (the op-level test hooks do that) can be overtaken by the zero fill
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    return e;
-}

@@ -500,7 +500,8 @@ int mi_op_gemm(mi_ctx* c, int32_t M, int32_t N, int32_t K, const float* A, int64
     ARG(c && A && B && C, "null"); JOIN(c);
     const size_t na = (size_t)((M - 1) * sam + (K - 1) * sak + 1), nb = (size_t)((K - 1) * sbk + (N - 1) * sbn + 1);
     float *da = nullptr, *db = nullptr, *dc = nullptr;
-    HIPC(dalloc(&da, na)); HIPC(dalloc(&db, nb)); HIPC(dalloc(&dc, (size_t)M * N));
+    DevPool m(hip_pool());
+    HIPC(m.dev(&da, na)); HIPC(m.dev(&db, nb)); HIPC(m.dev(&dc, (size_t)M * N));
     HIPC(hipMemcpy(da, A, na * 4, hipMemcpyHostToDevice)); HIPC(hipMemcpy(db, B, nb * 4, hipMemcpyHostToDevice));
     GemmArgs g{};
     g.ws = c->gemm_ws; g.ws_floats = c->gemm_ws_floats;
@@ -509,7 +510,6 @@ int mi_op_gemm(mi_ctx* c, int32_t M, int32_t N, int32_t K, const float* A, int64
     HIPC(hipGetLastError()); NETCHK(c);
     HIPC(hipStreamSynchronize(c->stream));
     HIPC(hipMemcpy(C, dc, (size_t)M * N * 4, hipMemcpyDeviceToHost));
-    hipFree(da); hipFree(db); hipFree(dc);
     return 0;
 }
 
@@ -644,12 +644,12 @@ __global__ void mfma_selftest_kernel(float* d) {
 int mi_selftest_mfma(mi_ctx* c, float* max_err) {
     ARG(c && max_err, "null"); JOIN(c);
     float* d = nullptr;
-    HIPC(dalloc(&d, 256));
+    DevPool m(hip_pool());
+    HIPC(m.dev(&d, 256));
     hipLaunchKernelGGL(mfma_selftest_kernel, dim3(1), dim3(64), 0, c->stream, d);
     HIPC(hipStreamSynchronize(c->stream));
     float h[256];
     HIPC(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
-    hipFree(d);
     float worst = 0.f;
     for (int m = 0; m < 16; ++m)
         for (int n = 0; n < 16; ++n) {

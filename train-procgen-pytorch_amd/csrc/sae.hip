@@ -29,29 +29,11 @@ struct mi_sae {
     float *kl_term = nullptr, *seed = nullptr, *log = nullptr, *gnorm = nullptr;
     int32_t* h_idx = nullptr; hipEvent_t ev_idx = nullptr; bool idx_pending = false;
     float* h_log = nullptr;
-    const float* owner_params = nullptr; int oT = 0, oE = 0, oA = 0;      // the owning context, as mi_sae_create saw it (sae_of)
     unsigned long long counter = 0;                             // Philox counter of the NEXT mi_sae_step (advances by E per call)
     std::vector<int64_t> map[2];                                // device index of host element i
+    // the context holds the state (mi_ctx::sae): mi_sae_create makes it, mi_sae_destroy or mi_destroy (sae_release) lets go of it
+    DevPool pool{hip_pool()};                                    // owns every buffer and the event above (declared last: destroyed first)
 };
-
-// The agent's state hangs beside the context, not inside it: the context's definition and its entry points (engine.hip, engine_ctx.h) are
-// the PPO path's and stay byte for byte what they were.  mi_sae_create registers the state under the context's address, mi_sae_destroy
-// (before mi_destroy) releases it.
-static std::mutex g_sae_mu;
-static std::unordered_map<const mi_ctx*, mi_sae*> g_sae;
-static void sae_release(mi_sae* s);
-// A context destroyed without mi_sae_destroy leaves its entry behind, and a later context may get the same address: an entry is this
-// context's only if the parameter buffer and the sizes are the ones mi_sae_create recorded; a stale one is released here.
-static mi_sae* sae_of(const mi_ctx* c) {
-    std::lock_guard<std::mutex> lk(g_sae_mu);
-    auto it = g_sae.find(c);
-    if (it == g_sae.end()) return nullptr;
-    mi_sae* s = it->second;
-    if (s->owner_params == c->params && s->oT == c->T && s->oE == c->E && s->oA == c->A) return s;
-    g_sae.erase(it);
-    sae_release(s);
-    return nullptr;
-}
 
 // ------------------------------------------------------------------------------------------ kernels
 // hidden = ReLU(block-3 output) (common/model.py:186-196), fp32, device column order
@@ -227,20 +209,20 @@ static inline float* sae_Wd(mi_sae* s) { return s->p[0] + (size_t)s->S * D + s->
 static inline float* sae_bd(mi_sae* s) { return s->p[0] + (size_t)2 * s->S * D + s->S; }
 // enc = relu(x W_e^T + b_e), n rows
 static void sae_encode(mi_ctx* c, const float* x, float* enc, int n) {
-    mi_sae* s = sae_of(c);
+    mi_sae* s = c->sae;
     sae_gemm(c, x, D, sae_We(s), 1, D, enc, n, s->S, D, sae_be(s), 1, nullptr);
 }
 static void sae_decode(mi_ctx* c, const float* enc, float* rec, int n) {
-    mi_sae* s = sae_of(c);
+    mi_sae* s = c->sae;
     sae_gemm(c, enc, s->S, sae_Wd(s), 1, s->S, rec, n, D, s->S, sae_bd(s), 0, nullptr);
 }
 static void sae_probe_fwd(mi_ctx* c, const float* enc, float* out, int n) {
-    mi_sae* s = sae_of(c);
+    mi_sae* s = c->sae;
     sae_gemm(c, enc, s->S, s->p[1], 1, s->S, out, n, c->A + 1, s->S, s->p[1] + (size_t)(c->A + 1) * s->S, 0, nullptr);
 }
 
 static void sae_build_maps(mi_ctx* c) {
-    mi_sae* s = sae_of(c);
+    mi_sae* s = c->sae;
     const int64_t S = s->S, A = c->A;
     auto dcol = [](int64_t h) { return (h % 64) * 32 + h / 64; };      // host column ch*64 + p -> device column p*32 + ch
     std::vector<int64_t>& a = s->map[0];
@@ -259,7 +241,7 @@ static void sae_build_maps(mi_ctx* c) {
     b[i++] = (A + 1) * S + A;                                           // fc_value.bias
 }
 static int sae_upload(mi_ctx* c, int which, float* dbuf, const float* flat, int64_t n) {
-    mi_sae* s = sae_of(c);
+    mi_sae* s = c->sae;
     ARG(flat, "null"); ARG(n == (which ? s->n_probe : s->n_sae), "flat vector length != mi_sae_param_count"); JOIN(c);
     std::vector<float> tmp(n);
     const std::vector<int64_t>& mp = s->map[which];
@@ -269,7 +251,7 @@ static int sae_upload(mi_ctx* c, int which, float* dbuf, const float* flat, int6
     return 0;
 }
 static int sae_download(mi_ctx* c, int which, const float* dbuf, float* flat, int64_t n) {
-    mi_sae* s = sae_of(c);
+    mi_sae* s = c->sae;
     ARG(flat, "null"); ARG(n == (which ? s->n_probe : s->n_sae), "flat vector length != mi_sae_param_count"); JOIN(c);
     std::vector<float> tmp(n);
     HIPC(hipMemcpyAsync(tmp.data(), dbuf, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -278,11 +260,11 @@ static int sae_download(mi_ctx* c, int which, const float* dbuf, float* flat, in
     for (int64_t i = 0; i < n; ++i) flat[i] = tmp[mp[i]];
     return 0;
 }
-#define SAE_CTX(c, which) ARG(c, "null"); mi_sae* const s = sae_of(c); ARG(s, "no SAE on this context: call mi_sae_create first"); ARG((which) == 0 || (which) == 1, "which must be 0 (SAE) or 1 (probe)")
+#define SAE_CTX(c, which) ARG(c, "null"); mi_sae* const s = c->sae; ARG(s, "no SAE on this context: call mi_sae_create first"); ARG((which) == 0 || (which) == 1, "which must be 0 (SAE) or 1 (probe)")
 
 // minibatch indices -> c->d_idx through the SAE's pinned buffer (rewritten only after the copy that read it has completed)
 static int sae_stage_idx(mi_ctx* c, const int64_t* idx, int n) {
-    mi_sae* s = sae_of(c);
+    mi_sae* s = c->sae;
     const int64_t N = (int64_t)c->T * c->E;
     for (int k = 0; k < n; ++k) ARG(idx[k] >= 0 && idx[k] < N, "minibatch index out of range [0, T*E)");
     if (s->idx_pending) { HIPC(hipEventSynchronize(s->ev_idx)); s->idx_pending = false; }
@@ -292,7 +274,7 @@ static int sae_stage_idx(mi_ctx* c, const int64_t* idx, int n) {
     return 0;
 }
 static int sae_read_log(mi_ctx* c, float* log_out) {
-    mi_sae* s = sae_of(c);
+    mi_sae* s = c->sae;
     HIPC(hipGetLastError()); NETCHK(c);
     if (log_out) {
         HIPC(hipMemcpyAsync(s->h_log, s->log, 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -302,58 +284,48 @@ static int sae_read_log(mi_ctx* c, float* log_out) {
     return 0;
 }
 
-static void sae_release(mi_sae* s) {
-    for (int w = 0; w < 2; ++w) { hipFree(s->p[w]); hipFree(s->g[w]); hipFree(s->m[w]); hipFree(s->v[w]); }
-    float* fl[] = {s->ring_h, s->ring_l, s->X, s->enc, s->rec, s->dEnc, s->pout, s->pdY, s->step_h, s->kl_term, s->seed, s->log, s->gnorm};
-    for (float* q : fl) if (q) hipFree(q);
-    if (s->col_part) hipFree(s->col_part); if (s->red_part) hipFree(s->red_part); if (s->sumsq) hipFree(s->sumsq);
-    if (s->h_idx) hipHostFree(s->h_idx); if (s->h_log) hipHostFree(s->h_log); if (s->ev_idx) hipEventDestroy(s->ev_idx);
-    delete s;
-}
-static void sae_free(mi_ctx* c) {
-    mi_sae* s = sae_of(c);
-    if (!s) return;
-    hipStreamSynchronize(c->stream);
-    { std::lock_guard<std::mutex> lk(g_sae_mu); g_sae.erase(c); }
-    sae_release(s);
+void sae_release(mi_ctx* c) {
+    if (!c->sae) return;
+    hipDeviceSynchronize();      // (not the context's stream alone: the pool lets go of the pinned buffers and the event first)
+    delete c->sae;
+    c->sae = nullptr;
 }
 
 // ------------------------------------------------------------------------------------------ C ABI
 int mi_sae_create(mi_ctx* c, int32_t sae_dim, float rho) {
     ARG(c, "null"); JOIN(c);
-    ARG(!sae_of(c), "this context already has an SAE");
+    ARG(!c->sae, "this context already has an SAE");
     ARG(c->cfg.arch == MI_ARCH_IMPALA, "the SAE agent needs an IMPALA context (encoded_dim / forward_to_pool exist only on ImpalaModel); arch mlp is not supported");
     ARG(!c->gru_on, "the SAE agent is non-recurrent: a context with a GRU set (recurrent policy) is not supported");
     ARG(c->comm_world <= 1 && c->multirank == 0, "the SAE agent is single-GPU: a multi-rank context (world size > 1) is not supported");
     ARG(c->n_groups <= 1, "the SAE agent runs serial rollout steps: a context with env groups (rollout_groups > 1) is not supported");
     ARG(sae_dim >= 64 && sae_dim <= 4096 && sae_dim % 64 == 0, "sae_dim must be a multiple of 64 in [64, 4096]");
-    mi_sae* s = new mi_sae();
-    s->owner_params = c->params; s->oT = c->T; s->oE = c->E; s->oA = c->A;
-    { std::lock_guard<std::mutex> lk(g_sae_mu); g_sae[c] = s; }
+    mi_sae* s = c->sae = new mi_sae();
     s->S = sae_dim; s->rho = rho;
     const size_t S = sae_dim, A = c->A, T = c->T, E = c->E, NB = c->NB;
     s->n_sae = (int64_t)(2 * S * D + S + D); s->n_probe = (int64_t)((A + 1) * S + A + 1);
     auto all = [&]() -> int {
+        DevPool& m = s->pool;
         for (int w = 0; w < 2; ++w) {
             const size_t n = w ? s->n_probe : s->n_sae;
-            HIPC(dalloc(&s->p[w], n)); HIPC(dalloc(&s->g[w], n)); HIPC(dalloc(&s->m[w], n)); HIPC(dalloc(&s->v[w], n));
+            HIPC(m.dev(&s->p[w], n)); HIPC(m.dev(&s->g[w], n)); HIPC(m.dev(&s->m[w], n)); HIPC(m.dev(&s->v[w], n));
         }
-        HIPC(dalloc(&s->ring_h, (T + 1) * E * D)); HIPC(dalloc(&s->ring_l, T * E * A));
-        HIPC(dalloc(&s->X, NB * D)); HIPC(dalloc(&s->rec, NB * D)); HIPC(dalloc(&s->enc, NB * S)); HIPC(dalloc(&s->dEnc, NB * S));
-        HIPC(dalloc(&s->pout, NB * (A + 1))); HIPC(dalloc(&s->pdY, NB * (A + 1))); HIPC(dalloc(&s->step_h, E * D));
-        HIPC(dalloc(&s->col_part, (size_t)COLSUM_GROUPS * S)); HIPC(dalloc(&s->red_part, (size_t)1024 * 5)); HIPC(dalloc(&s->sumsq, 128));
-        HIPC(dalloc(&s->kl_term, S)); HIPC(dalloc(&s->seed, S)); HIPC(dalloc(&s->log, 8)); HIPC(dalloc(&s->gnorm, 2));
-        HIPC(hipHostMalloc((void**)&s->h_idx, NB * sizeof(int32_t))); HIPC(hipHostMalloc((void**)&s->h_log, 8 * sizeof(float)));
-        HIPC(hipEventCreateWithFlags(&s->ev_idx, hipEventDisableTiming));
+        HIPC(m.dev(&s->ring_h, (T + 1) * E * D)); HIPC(m.dev(&s->ring_l, T * E * A));
+        HIPC(m.dev(&s->X, NB * D)); HIPC(m.dev(&s->rec, NB * D)); HIPC(m.dev(&s->enc, NB * S)); HIPC(m.dev(&s->dEnc, NB * S));
+        HIPC(m.dev(&s->pout, NB * (A + 1))); HIPC(m.dev(&s->pdY, NB * (A + 1))); HIPC(m.dev(&s->step_h, E * D));
+        HIPC(m.dev(&s->col_part, (size_t)COLSUM_GROUPS * S)); HIPC(m.dev(&s->red_part, (size_t)1024 * 5)); HIPC(m.dev(&s->sumsq, 128));
+        HIPC(m.dev(&s->kl_term, S)); HIPC(m.dev(&s->seed, S)); HIPC(m.dev(&s->log, 8)); HIPC(m.dev(&s->gnorm, 2));
+        HIPC(m.pinned(&s->h_idx, NB * sizeof(int32_t), hipHostMallocDefault)); HIPC(m.pinned(&s->h_log, 8 * sizeof(float), hipHostMallocDefault));
+        HIPC(m.event(&s->ev_idx, hipEventDisableTiming));
         return 0;
     };
-    if (int r = all()) { sae_free(c); return r; }
+    if (int r = all()) { sae_release(c); return r; }
     sae_build_maps(c);
     return 0;
 }
 
-int mi_sae_destroy(mi_ctx* c) { ARG(c, "null"); JOIN(c); sae_free(c); return 0; }
-int64_t mi_sae_param_count(mi_ctx* c, int32_t which) { mi_sae* s = c ? sae_of(c) : nullptr; return (s && (which == 0 || which == 1)) ? (which ? s->n_probe : s->n_sae) : -1; }
+int mi_sae_destroy(mi_ctx* c) { ARG(c, "null"); JOIN(c); sae_release(c); return 0; }
+int64_t mi_sae_param_count(mi_ctx* c, int32_t which) { mi_sae* s = c ? c->sae : nullptr; return (s && (which == 0 || which == 1)) ? (which ? s->n_probe : s->n_sae) : -1; }
 int mi_sae_set_params(mi_ctx* c, int32_t which, const float* flat, int64_t n) { SAE_CTX(c, which); return sae_upload(c, which, s->p[which], flat, n); }
 int mi_sae_get_params(mi_ctx* c, int32_t which, float* flat, int64_t n) { SAE_CTX(c, which); return sae_download(c, which, s->p[which], flat, n); }
 int mi_sae_get_grads(mi_ctx* c, int32_t which, float* flat, int64_t n) { SAE_CTX(c, which); return sae_download(c, which, s->g[which], flat, n); }
@@ -439,7 +411,7 @@ int mi_sae_step(mi_ctx* c, int32_t t, const void* obs, size_t bytes, int32_t act
 }
 
 static int sae_forward_rows(mi_ctx* c, const int64_t* idx, int n) {
-    mi_sae* s = sae_of(c);
+    mi_sae* s = c->sae;
     ARG(idx, "null idx"); ARG(n >= 1 && n <= c->NB, "n must be in [1, max_batch]");
     if (int r = sae_stage_idx(c, idx, n)) return r;
     const long long g4 = (long long)n * (D / 4);
