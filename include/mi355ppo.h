@@ -104,6 +104,40 @@ int mi_policy_step(mi_ctx* ctx, int32_t t, uint64_t seed, const float* u,
 int mi_rollout_step(mi_ctx* ctx, int32_t t, const float* rew_prev, const float* done_prev, uint64_t seed, const float* u,
                     int64_t* act_out, float* logp_out, float* value_out);
 
+/* ---- the device-resident cart-pole (opt-in; the host env is common/env/vec_envs.py CartPoleVec = the reference's
+ *      discrete_env/cartpole_pre_vec.py:20-262 on pre_vec_env.py:21-125): state, physics, termination, episode resets, reward and done
+ *      live in HBM, and mi_env_rollout enqueues a whole rollout with no host synchronisation.  On an MLP context with obs_dim == 9 and
+ *      n_actions == 2 only; anything else is refused with a message that names the field, and so are a context with a GRU set and a
+ *      second create on the same context.  The env's buffers belong to the context: mi_destroy frees them.
+ *      State: double [E][9] in CartPoleVec's column order {x, x_dot, theta, theta_dot, gravity, pole_length, cart_mass, pole_mass,
+ *      force_mag}, int32 n_steps [E] (steps of the running episode), int64 episode [E] (0 after create; every start of an episode adds 1).
+ *      A step is CartPoleVec.step in fp64 in the same operation order; an env ends beyond +-x_threshold / +-theta_threshold or when
+ *      n_steps reaches max_steps, and then starts episode + 1 at once: done is the step's termination flag, the observation the
+ *      post-reset state, the reward 1.  The thresholds arrive as doubles (the caller computes degrees * 2 pi / 360 as CartPoleVec does).
+ *      A fresh state is low + (high - low) * u per column, u = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53 from two words of Philox4x32-10
+ *      keyed by `seed` with the counter {env index, episode low word, episode high word, block}, block 0..4 giving columns 2 block and
+ *      2 block + 1 from words {0, 1} and {2, 3}.  This stream is the device env's own: CartPoleVec draws an (E, 9) numpy block whenever
+ *      any env ends, which is not reproduced.
+ *      mi_env_reset: every env starts a fresh episode; float(state) goes into observation slot 0.  Asynchronous.
+ *      mi_env_step: one env step on the caller's actions (0 / 1), results on the host (any output may be NULL), one synchronisation; it
+ *      goes through a staging slot and changes no ring (VecEnv.step, and the teacher-forcing hook of the tests).
+ *      mi_env_rollout: float(state) -> observation slot 0; for t in [0, T): the policy step on slot t exactly as
+ *      mi_policy_step(t, seed, NULL, NULL, NULL, NULL) enqueues it (same kernels, same Philox counters t * E + e), then the env step on
+ *      act[t] -> obs[t + 1], rew[t], done[t]; then the policy step on slot T (value[T] only).  All on the context's stream; returns
+ *      without synchronising (the rings are read with mi_read_field / mi_get_obs as after any rollout).
+ *      mi_env_get_state / mi_env_set_state: test and checkpoint hooks; any pointer may be NULL (that part is skipped). */
+typedef struct mi_cartpole_params {
+    double low[9], high[9];          /* start ranges per state column */
+    double x_threshold, theta_threshold;
+    int32_t max_steps;
+} mi_cartpole_params;
+int mi_env_cartpole_create(mi_ctx* ctx, const mi_cartpole_params* params, uint64_t seed);
+int mi_env_reset(mi_ctx* ctx);
+int mi_env_step(mi_ctx* ctx, const int64_t* act, float* obs_out /* E x 9 */, float* rew_out, float* done_out);
+int mi_env_rollout(mi_ctx* ctx, uint64_t seed);
+int mi_env_get_state(mi_ctx* ctx, double* state /* E x 9 */, int32_t* n_steps, int64_t* episode);
+int mi_env_set_state(mi_ctx* ctx, const double* state, const int32_t* n_steps, const int64_t* episode);
+
 /* ---- pipelined rollout: the same step as mi_rollout_step, per ENV GROUP and split into submit / wait, so that the frame upload and
  *      forward pass of one group run beside the host's env.step of another (agents/ppo.py:225-231 is strictly serial; an env's next
  *      observation depends on its own action only, so G contiguous groups of E/G envs form G independent chains).

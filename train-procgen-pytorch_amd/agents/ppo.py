@@ -14,7 +14,7 @@ import torch
 from common.misc_util import adjust_lr, adjust_lr_grok
 from common.model import as_device_obs
 from mi355.dist import Collective, DevicePointerTensor, update_plan
-from mi355.engine import Engine, PTR_FS_KEYS, PTR_GRADS, PTR_LOSS_STATS, PTR_STATS_RING
+from mi355.engine import Engine, F_DONE, F_LOGP, F_REW, F_VALUE, PTR_FS_KEYS, PTR_GRADS, PTR_LOSS_STATS, PTR_STATS_RING
 
 
 def _with_next(it):
@@ -96,6 +96,9 @@ class PPO(BaseAgent):
                                        precision=self.precision, value_from_logits=policy.logsumexp_logits_is_v)
             storage_valid.attach_engine(self.engine_valid)
             policy.attach_aux_engine(self.engine_valid)          # frozen GRU weights, now and after load_state_dict
+        for e, eng in ((env, self.engine), (env_valid, self.engine_valid)):
+            if getattr(e, "on_device", False) and eng is not None:     # a device-resident env lives in its lane's context (before the first reset())
+                e.attach_engine(eng)
         self.optimizer = DeviceAdam(policy, self.engine, learning_rate, eps=1e-5)
         self._grads_t = self._stats_t = self._ring_t = None
         # collectives: RCCL inside the library when the process group is "nccl" (one GPU per rank); torch.distributed on aliased
@@ -277,6 +280,8 @@ class PPO(BaseAgent):
 
     # ------------------------------------------------------------------ rollout + train
     def _collect(self, env, engine, storage, obs, hidden_state, done):
+        if getattr(env, "on_device", False):
+            return self._collect_device(env, engine, storage, obs, hidden_state, done)
         if self._can_pipeline(env):
             return self._collect_pipelined(env, engine, storage, obs, hidden_state, done)
         for _ in range(self.n_steps):
@@ -288,6 +293,34 @@ class PPO(BaseAgent):
         _, _, last_val, hidden_state = self._predict_into(engine, storage, self.n_steps, obs, hidden_state, done)
         storage.store_last(obs, hidden_state, last_val)
         return obs, hidden_state, done
+
+    def _collect_device(self, env, engine, storage, obs, hidden_state, done):
+        """The same T steps + bootstrap step for an env that lives on the device (common/env/vec_envs.py DeviceCartPole): ONE call
+        enqueues T + 1 policy steps and T env steps (mi_env_rollout; the policy steps are `_collect`'s kernels with its sampling
+        counters), and the host waits once, for the reward / done rings it mirrors for the logger.  `obs` is what the env's state on the
+        device already is (its reset() or the previous rollout returned it) and is not uploaded."""
+        from common.env.vec_envs import StepInfo
+        if self.policy.is_recurrent():
+            raise NotImplementedError("a device-resident env with a recurrent policy is not supported")
+        T = self.n_steps
+        if env.engine is not engine:                             # first use on this lane: the env is created in this engine's context
+            env.attach_engine(engine)
+            env.reset()
+        engine.env_rollout(self.seed * 1000003 + self._iter)
+        engine.read_field_into(F_REW, storage._rew)              # (T, E) each, straight into the pinned mirrors
+        engine.read_field_into(F_DONE, storage._done)
+        if self.detect_nan:
+            value, logp = engine.read_field(F_VALUE), engine.read_field(F_LOGP)
+            for t in np.nonzero(~(np.isfinite(value[:T]).all(1) & np.isfinite(logp).all(1)))[0][:1]:
+                raise RuntimeError(f"Found NaN / Inf in the policy outputs of rollout step {t}")
+            if not np.isfinite(value[T]).all():
+                raise RuntimeError(f"Found NaN / Inf in the policy outputs of rollout step {T}")
+        for t in range(T):
+            storage.info_batch.append(StepInfo(self.n_envs, {"env_reward": storage._rew[t]}))
+        storage._pending = None
+        storage.step = (storage.step + T) % T                    # where T store() calls leave it
+        storage._hidden[T] = hidden_state                        # store_last: value[T] and the observations are already in the device ring
+        return engine.get_obs(T), hidden_state, storage._done[T - 1].copy()
 
     def _collect_pipelined(self, env, engine, storage, obs, hidden_state, done):
         """The same T steps + bootstrap step with the env groups of `env.env_groups` as independent chains (mi_rollout_submit /

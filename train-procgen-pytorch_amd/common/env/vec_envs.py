@@ -4,6 +4,7 @@ common/env/procgen_wrappers.py:45-124.  Rollout collection stays on the host (no
 
 * CartPoleVec   -- the reference's 9-observation pre-vectorised cart-pole (discrete_env/cartpole_pre_vec.py) restated in numpy,
                    the plumbing config C1 (MLPModel(9, ...)).
+* DeviceCartPole -- the same env resident on the device (opt-in, train.py --device_env): the one env here whose dynamics are ours.
 * SyntheticFrames -- random uint8 64x64x3 frames, N(0,1) rewards, Bernoulli(0.01) dones: the synthetic
                    learner-side workload of SURVEY 8(d) / bench.py.
 * create_procgen_env -- the real engine if the `procgen` package is importable (it is not in the build image).
@@ -148,16 +149,76 @@ CARTPOLE_PARAM_RANGE = {"degrees": [12], "h_range": [2.4], "min_gravity": [9.8, 
                         "min_pole_mass": [0.1, .2], "max_pole_mass": [0.2, .4], "min_force_mag": [10.], "max_force_mag": [10.]}
 
 
-def create_cartpole(hyperparameters, is_valid=False, seed=0, n_envs=None):
+class DeviceCartPole:
+    """CartPoleVec with the env on the device (train.py --device_env; csrc/cartpole.hip, mi_env_* in include/mi355ppo.h): state,
+    physics, termination, episode resets, reward and done live in HBM next to the policy, so that the agent collects a whole rollout
+    with ONE call and no host round trip per step (agents/ppo.py `_collect_device`).  Same constructor arguments, spaces, ranges,
+    thresholds (the same fp64 bits) and step arithmetic (fp64, the same operation order) as CartPoleVec.
+
+    What differs is the random stream of the episode starts.  CartPoleVec draws a whole (n_envs, 9) block from numpy's PCG64 whenever ANY
+    env ends and keeps the ended rows; that is NOT reproduced.  Here the start of episode k of env e is low + (high - low) * u per column
+    with u a 53-bit uniform from Philox4x32-10 keyed by `seed`, counter {e, k low word, k high word, block}: a function of (seed, env,
+    episode) alone, whatever the other envs do.  Trajectories of the two classes therefore agree step for step until the first reset and
+    in distribution afterwards.
+
+    The env lives in an engine context: `attach_engine(engine)` (the agent does it) creates it there; reset() / step(act) then go through
+    mi_env_reset / mi_env_step, one synchronisation each, so the VecEnv protocol and the public predict / store loop still work.
+    Limits: the 9-observation MLP cart-pole, non-recurrent policies, one GPU."""
+    on_device = True
+
+    def __init__(self, n_envs, degrees=12, h_range=2.4, min_gravity=9.8, max_gravity=10.4, min_pole_length=0.5, max_pole_length=1.0,
+                 min_cart_mass=1.0, max_cart_mass=1.5, min_pole_mass=0.1, max_pole_mass=0.2, min_force_mag=10., max_force_mag=10.,
+                 max_steps=500, seed=0, **_ignored):
+        if n_envs < 2:
+            raise Exception("n_envs must be greater than or equal to 2")
+        self.n_envs = self.num_envs = n_envs
+        self.max_steps = max_steps
+        self.theta_threshold, self.x_threshold = degrees * 2 * np.pi / 360, h_range
+        self.low = np.array([-0.05] * 4 + [min_gravity, min_pole_length, min_cart_mass, min_pole_mass, min_force_mag])
+        self.high = np.array([0.05] * 4 + [max_gravity, max_pole_length, max_cart_mass, max_pole_mass, max_force_mag])
+        self.seed = int(seed)
+        self.observation_space = _Space(shape=(9,))
+        self.action_space = _Space(n=2)
+        self.engine = None
+
+    def attach_engine(self, engine):
+        """Create the env in `engine`'s context (an MLP engine with 9 observations, 2 actions and n_envs environments)."""
+        if self.engine is engine:
+            return
+        if engine.E != self.n_envs:
+            raise ValueError(f"engine has {engine.E} envs, the env {self.n_envs}")
+        engine.env_cartpole_create(self.low, self.high, self.x_threshold, self.theta_threshold, self.max_steps, self.seed)
+        self.engine = engine
+
+    def _eng(self):
+        if self.engine is None:
+            raise RuntimeError("DeviceCartPole is not attached to an engine yet: construct the agent with it (or call attach_engine) first")
+        return self.engine
+
+    def reset(self):
+        eng = self._eng()
+        eng.env_reset()
+        return eng.get_obs(0)
+
+    def step(self, act):
+        obs, rew, done = self._eng().env_step(act)
+        return obs, rew, done, StepInfo(self.n_envs, {"env_reward": rew})
+
+    def close(self):
+        pass
+
+
+def create_cartpole(hyperparameters, is_valid=False, seed=0, n_envs=None, device=False):
     """create_cartpole / create_pre_vec / assign_env_vars (cartpole_pre_vec.py:397-412, pre_vec_env.py:207-223, helper_pre_vec.py:52-66):
     the validation env draws its physics from the SECOND value of every range (heavier, longer, stronger gravity); a hyper-parameter
     `<name>` (training) or `<name>_v` (validation) overrides a range entry (config.yml `cartpole`: degrees_v 9, h_range_v 1.8);
-    max_steps may come from the hyper-parameters too."""
+    max_steps may come from the hyper-parameters too.  device=True: the same arguments build the device-resident DeviceCartPole."""
     suffix, i = ("_v", -1) if is_valid else ("", 0)
     kw = {k: hyperparameters.get(k + suffix, v[i]) for k, v in CARTPOLE_PARAM_RANGE.items()}
     if "max_steps" in hyperparameters:
         kw["max_steps"] = hyperparameters["max_steps"]
-    return CartPoleVec(n_envs if n_envs is not None else hyperparameters.get("n_envs", 32), seed=seed, **kw)
+    cls = DeviceCartPole if device else CartPoleVec
+    return cls(n_envs if n_envs is not None else hyperparameters.get("n_envs", 32), seed=seed, **kw)
 
 
 class SyntheticFrames:

@@ -1090,18 +1090,25 @@ static inline bool wait_ticket(const volatile unsigned* flag, unsigned want, Gon
     return false;
 }
 
-int mi_policy_step(mi_ctx* c, int32_t t, uint64_t seed, const float* u, int64_t* act_out, float* logp_out, float* value_out) {
-    ARG(c, "null"); JOIN(c); ARG(t >= 0 && t <= c->T, "t out of range");
+// the launches of a policy step on ring slot t (forward, sample; du: the sampler's uniforms on the device or null), nothing else
+static int issue_policy_step(mi_ctx* c, int32_t t, uint64_t seed, const float* du) {
     const int E = c->E;
     InputSrc src{obs_ring(c), nullptr, (long long)t * E};
-    const float* du;
-    if (int r = upload_u(c, u, c->stream, 0, E, &du)) return r;
     c->prof.phase = 0;
     net_forward(c, src, E, {.recurrent = true});
     const bool last = (t == c->T);
     launch_sample(c->hout, E, c->A, du, seed, (unsigned long long)t * E, last ? nullptr : c->act + (size_t)t * E,
                   last ? nullptr : c->logp + (size_t)t * E, c->value + (size_t)t * E, c->stream, c->lse);
     HIPC(hipGetLastError()); NETCHK(c);
+    return 0;
+}
+int mi_policy_step(mi_ctx* c, int32_t t, uint64_t seed, const float* u, int64_t* act_out, float* logp_out, float* value_out) {
+    ARG(c, "null"); JOIN(c); ARG(t >= 0 && t <= c->T, "t out of range");
+    const int E = c->E;
+    const float* du;
+    if (int r = upload_u(c, u, c->stream, 0, E, &du)) return r;
+    if (int r = issue_policy_step(c, t, seed, du)) return r;
+    const bool last = (t == c->T);
     if (!act_out && !logp_out && !value_out) { if (u) HIPC(hipStreamSynchronize(c->stream)); return 0; }
     const size_t o = (size_t)t * E;
     return read_back_staged(c, (act_out && !last) ? c->act + o : nullptr, (logp_out && !last) ? c->logp + o : nullptr, value_out ? c->value + o : nullptr, act_out, logp_out, value_out);
@@ -1132,6 +1139,86 @@ int mi_rollout_step(mi_ctx* c, int32_t t, const float* rew_prev, const float* do
     HIPC(hipGetLastError()); NETCHK(c);
     if (!wait_ticket(c->h_flag, c->roll_ticket, [&] { return hipStreamQuery(c->stream) != hipErrorNotReady; })) HIPC(hipStreamSynchronize(c->stream));
     unpack_step(c->h_pack, E, last, act_out, logp_out, value_out);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ device-resident cart-pole env
+// The serial rollout of the cart-pole sets is T + 1 round trips: policy step -> actions to the host -> CartPoleVec.step in numpy -> the
+// next observations up.  With the env on the device (cartpole.hip) a rollout is ONE call that enqueues T + 1 policy steps and T env
+// steps on the main stream and returns; the only host wait is the caller's read of the reward / done rings afterwards.
+int mi_env_cartpole_create(mi_ctx* c, const mi_cartpole_params* p, uint64_t seed) {
+    ARG(c && p, "null"); JOIN(c);
+    ARG(c->cfg.arch == MI_ARCH_MLP, "mi_env_cartpole_create: arch must be MI_ARCH_MLP");
+    ARG(c->cfg.obs_dim == 9, "mi_env_cartpole_create: obs_dim must be 9 (the cart-pole's nine state columns)");
+    ARG(c->cfg.n_actions == 2, "mi_env_cartpole_create: n_actions must be 2 (push left / push right)");
+    ARG(c->E >= 2, "mi_env_cartpole_create: n_envs must be at least 2");
+    ARG(!c->gru_on, "mi_env_cartpole_create: a recurrent context (mi_set_gru) is not supported");
+    ARG(!c->env_on, "mi_env_cartpole_create: this context already has an env");
+    ARG(p->max_steps >= 1, "mi_env_cartpole_create: max_steps must be at least 1");
+    for (int j = 0; j < 9; ++j) ARG(p->low[j] <= p->high[j], "mi_env_cartpole_create: low must not exceed high");      // (also refuses NaN)
+    const size_t E = c->E;
+    DevPool& m = c->pool; DevPool::Group all(m);
+    HIPC(m.dev(&c->env_state, E * 9)); HIPC(m.dev(&c->env_nsteps, E)); HIPC(m.dev(&c->env_episode, E));
+    HIPC(m.dev(&c->env_s_act, E)); HIPC(m.dev(&c->env_s_obs, E * 9)); HIPC(m.dev(&c->env_s_rew, E)); HIPC(m.dev(&c->env_s_done, E));
+    all.keep = true;
+    for (int j = 0; j < 9; ++j) { c->env_args.low[j] = p->low[j]; c->env_args.high[j] = p->high[j]; }
+    c->env_args.x_threshold = p->x_threshold; c->env_args.theta_threshold = p->theta_threshold; c->env_args.max_steps = p->max_steps;
+    c->env_seed = seed;
+    c->env_on = true;
+    return 0;
+}
+#define ENV(c) ARG((c)->env_on, "no env on this context (mi_env_cartpole_create)")
+int mi_env_reset(mi_ctx* c) {
+    ARG(c, "null"); JOIN(c); ENV(c);
+    launch_cartpole_reset(c->env_args, c->env_state, c->env_nsteps, c->env_episode, c->env_seed, c->obsf, c->E, c->stream);
+    HIPC(hipGetLastError());
+    return 0;
+}
+int mi_env_step(mi_ctx* c, const int64_t* act, float* obs_out, float* rew_out, float* done_out) {
+    ARG(c && act, "null"); JOIN(c); ENV(c);
+    const size_t E = c->E;
+    for (size_t e = 0; e < E; ++e) ARG(act[e] == 0 || act[e] == 1, "mi_env_step: every action must be 0 or 1");
+    HIPC(hipStreamSynchronize(c->stream));      // (h_i may still be the source / destination of an earlier call's copy)
+    for (size_t e = 0; e < E; ++e) c->h_i[e] = (int32_t)act[e];
+    HIPC(hipMemcpyAsync(c->env_s_act, c->h_i, E * 4, hipMemcpyHostToDevice, c->stream));
+    launch_cartpole_step(c->env_args, c->env_state, c->env_nsteps, c->env_episode, c->env_s_act, c->env_seed, c->env_s_obs, c->env_s_rew,
+                         c->env_s_done, c->E, c->stream);
+    HIPC(hipGetLastError());
+    if (obs_out) HIPC(hipMemcpyAsync(obs_out, c->env_s_obs, E * 9 * 4, hipMemcpyDeviceToHost, c->stream));
+    if (rew_out) HIPC(hipMemcpyAsync(rew_out, c->env_s_rew, E * 4, hipMemcpyDeviceToHost, c->stream));
+    if (done_out) HIPC(hipMemcpyAsync(done_out, c->env_s_done, E * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return 0;
+}
+int mi_env_rollout(mi_ctx* c, uint64_t seed) {
+    ARG(c, "null"); JOIN(c); ENV(c);
+    ARG(!c->gru_on, "mi_env_rollout: a recurrent context (mi_set_gru) is not supported");
+    const size_t E = c->E;
+    launch_cartpole_emit_obs(c->env_state, c->obsf, c->E, c->stream);
+    for (int t = 0; t < c->T; ++t) {
+        if (int r = issue_policy_step(c, t, seed, nullptr)) return r;
+        launch_cartpole_step(c->env_args, c->env_state, c->env_nsteps, c->env_episode, c->act + t * E, c->env_seed, c->obsf + (t + 1) * E * 9,
+                             c->rew + t * E, c->done + t * E, c->E, c->stream);
+    }
+    return issue_policy_step(c, c->T, seed, nullptr);
+}
+int mi_env_get_state(mi_ctx* c, double* state, int32_t* n_steps, int64_t* episode) {
+    ARG(c, "null"); JOIN(c); ENV(c);
+    const size_t E = c->E;
+    if (state) HIPC(hipMemcpyAsync(state, c->env_state, E * 9 * 8, hipMemcpyDeviceToHost, c->stream));
+    if (n_steps) HIPC(hipMemcpyAsync(n_steps, c->env_nsteps, E * 4, hipMemcpyDeviceToHost, c->stream));
+    if (episode) HIPC(hipMemcpyAsync(episode, c->env_episode, E * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return 0;
+}
+int mi_env_set_state(mi_ctx* c, const double* state, const int32_t* n_steps, const int64_t* episode) {
+    ARG(c, "null"); JOIN(c); ENV(c);
+    const size_t E = c->E;
+    if (n_steps) for (size_t e = 0; e < E; ++e) ARG(n_steps[e] >= 0, "mi_env_set_state: n_steps must not be negative");
+    if (state) HIPC(hipMemcpyAsync(c->env_state, state, E * 9 * 8, hipMemcpyHostToDevice, c->stream));
+    if (n_steps) HIPC(hipMemcpyAsync(c->env_nsteps, n_steps, E * 4, hipMemcpyHostToDevice, c->stream));
+    if (episode) HIPC(hipMemcpyAsync(c->env_episode, episode, E * 8, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));      // caller buffers may be pageable temporaries
     return 0;
 }
 

@@ -34,6 +34,11 @@ class _HParams(C.Structure):
                                          "entropy_multiplier", "fs_coef")]
 
 
+class _CartPoleParams(C.Structure):
+    _fields_ = [("low", C.c_double * 9), ("high", C.c_double * 9), ("x_threshold", C.c_double), ("theta_threshold", C.c_double),
+                ("max_steps", C.c_int32)]
+
+
 class _IplHParams(C.Structure):
     _fields_ = [("gamma", C.c_float), ("alpha", C.c_float), ("entropy_coef", C.c_float), ("flags", C.c_int32)]
 
@@ -54,7 +59,8 @@ EXPORTS = ("mi_last_error mi_create mi_destroy mi_sync mi_host_alloc mi_host_fre
            "mi_gru_train mi_minibatch_rec mi_get_gru mi_get_gru_grads mi_get_gru_adam_state mi_set_gru_adam_state mi_debug_gru_seq "
            "mi_sae_create mi_sae_destroy mi_sae_param_count mi_sae_set_params mi_sae_get_params mi_sae_get_grads mi_sae_set_adam_state mi_sae_get_adam_state mi_sae_put_ring "
            "mi_sae_get_hidden mi_sae_get_logits mi_sae_step mi_sae_minibatch mi_sae_probe_minibatch mi_sae_optimizer_step mi_sae_debug_forward "
-           "mi_ipl_minibatch mi_ipl_read_pred mi_predict_greedy mi_op_ipl_loss mi_op_ipl_greedy").split()
+           "mi_ipl_minibatch mi_ipl_read_pred mi_predict_greedy mi_op_ipl_loss mi_op_ipl_greedy "
+           "mi_env_cartpole_create mi_env_reset mi_env_step mi_env_rollout mi_env_get_state mi_env_set_state").split()
 
 
 def load_library():
@@ -252,6 +258,51 @@ class Engine:
     def write_field(self, field, arr):
         arr = _f32(arr).reshape(-1)
         self._chk(self.lib.mi_write_field(self._ctx, C.c_int32(field), _fp(arr), C.c_int64(arr.size)))
+
+    def read_field_into(self, field, out):
+        """read_field into a caller array (C-contiguous float32 of the field's size, e.g. a Storage's pinned mirror): no allocation."""
+        if out.dtype != np.float32 or not out.flags.c_contiguous:
+            raise EngineError("read_field_into needs a C-contiguous float32 array")
+        self._chk(self.lib.mi_read_field(self._ctx, C.c_int32(field), _fp(out), C.c_int64(out.size)))
+        return out
+
+    # ------------------------------------------------------------------ device-resident cart-pole env (mi_env_*)
+    def env_cartpole_create(self, low, high, x_threshold, theta_threshold, max_steps, seed=0):
+        low, high = np.asarray(low, np.float64).reshape(9), np.asarray(high, np.float64).reshape(9)
+        p = _CartPoleParams((C.c_double * 9)(*low), (C.c_double * 9)(*high), float(x_threshold), float(theta_threshold), int(max_steps))
+        self._chk(self.lib.mi_env_cartpole_create(self._ctx, C.byref(p), C.c_uint64(int(seed) & (2 ** 64 - 1))))
+
+    def env_reset(self):
+        """Every env starts a fresh episode; observation slot 0 holds float32(state).  Asynchronous."""
+        self._chk(self.lib.mi_env_reset(self._ctx))
+
+    def env_state(self):
+        """-> (state (E, 9) float64, n_steps (E,) int32, episode (E,) int64) as they are on the device."""
+        s, n, ep = np.empty((self.E, 9), np.float64), np.empty(self.E, np.int32), np.empty(self.E, np.int64)
+        self._chk(self.lib.mi_env_get_state(self._ctx, _fp(s), _fp(n), _fp(ep)))
+        return s, n, ep
+
+    def env_set_state(self, state=None, n_steps=None, episode=None):
+        s = None if state is None else np.ascontiguousarray(state, dtype=np.float64)
+        n = None if n_steps is None else np.ascontiguousarray(n_steps, dtype=np.int32)
+        ep = None if episode is None else np.ascontiguousarray(episode, dtype=np.int64)
+        for a, size, name in ((s, 9 * self.E, "state"), (n, self.E, "n_steps"), (ep, self.E, "episode")):
+            if a is not None and a.size != size:
+                raise EngineError(f"env_set_state: {name} must have {size} elements")
+        self._chk(self.lib.mi_env_set_state(self._ctx, _fp(s), _fp(n), _fp(ep)))
+
+    def env_step(self, act):
+        """One env step on caller actions -> (obs (E, 9), rew (E,), done (E,)) float32 on the host; the rings are not touched."""
+        act = np.ascontiguousarray(act, dtype=np.int64).reshape(-1)
+        if act.size != self.E:
+            raise EngineError(f"env_step: {act.size} actions for {self.E} envs")
+        obs, rew, done = np.empty((self.E, 9), np.float32), np.empty(self.E, np.float32), np.empty(self.E, np.float32)
+        self._chk(self.lib.mi_env_step(self._ctx, _fp(act), _fp(obs), _fp(rew), _fp(done)))
+        return obs, rew, done
+
+    def env_rollout(self, seed=0):
+        """The whole rollout -- T + 1 policy steps, T env steps -- enqueued on the engine's stream; returns without waiting."""
+        self._chk(self.lib.mi_env_rollout(self._ctx, C.c_uint64(seed)))
 
     # ------------------------------------------------------------------ policy
     def policy_step(self, t, seed=0, u=None, want_outputs=True):

@@ -11,7 +11,7 @@ there), the log directory layout logs/train/<env>/<exp>/<time>__seed_<seed> with
 format, `--model_file auto` (create_logdir_train, train.py:277-294: the single run directory under the experiment that holds
 model_*.pth is reused and its newest checkpoint loaded -- the reference finds that file and then still hands 'auto' to torch.load),
 `--detect_nan`.  Different on purpose: `--device` defaults to gpu and `cpu` is refused (there is no CPU fallback); config.yml is
-read relative to this file instead of the hard-coded GLOBAL_DIR of helper_local.py:28; new flags --precision, --rollout_groups."""
+read relative to this file instead of the hard-coded GLOBAL_DIR of helper_local.py:28; new flags --precision, --rollout_groups, --device_env."""
 import os
 import sys
 
@@ -122,6 +122,8 @@ def add_training_args(p):
                    help="IMPALA activation storage / matrix-core type: fp32 = parity mode (default), bf16 = BASELINE config 3 (what bench.py measures)")
     p.add_argument('--rollout_groups', type=int, default=0,
                    help="env groups of the pipelined rollout (one group's frame upload + forward beside the host's env.step of another); 0 = auto (from 128 envs per rank: 4, or 2 + 2 when a validation env runs beside the training env; else 2; a recurrent policy: 1); 1 = the reference's serial step; a recurrent policy is pipelined only with an explicit G >= 2")
+    p.add_argument('--device_env', action="store_true",
+                   help="cartpole* only: the env lives on the device (state, physics, resets, reward and done in HBM) and a whole rollout is one call with no host round trip per step; episode starts come from the device env's own Philox stream, not numpy's.  Non-recurrent MLP policies, one GPU, algo ppo / ppo-pure")
     p.add_argument('--x_entropy_coef', type=float, default=None)
     p.add_argument('--algo', type=str, default=None, choices=['ppo', 'ppo-pure', 'sae', 'IPL'],
                    help="overrides the set's `algo`: ppo = the reference's agents/ppo.py (a recurrent policy's GRU stays frozen), ppo-pure = agents/ppo_pure.py (a recurrent policy is trained through its GRU with BPTT; single GPU), sae = agents/sae.py (a sparse autoencoder on the block-3 features of the trained IMPALA policy given by --model_file, then a linear probe on its codes; single GPU, use --param_name sae), IPL = agents/IPL.py (non-recurrent, single GPU; sets hard-500-ipl and ipl_cartpole)")
@@ -171,7 +173,8 @@ def _one_env(env_name, n_envs, seed, A, args, hp, is_valid, ret_rms=None, num_th
     if env_name.startswith("cartpole") or env_name == "mountain_car":
         if env_name == "mountain_car":
             raise NotImplementedError("mountain_car: only the cart-pole numpy env is built on the host side")
-        return create_cartpole(hp, is_valid, seed=seed, n_envs=n_envs)        # 9 observations -> MLPModel(9, ...), BASELINE config 1
+        # 9 observations -> MLPModel(9, ...), BASELINE config 1; --device_env: the same env resident on the device (DeviceCartPole)
+        return create_cartpole(hp, is_valid, seed=seed, n_envs=n_envs, device=bool(getattr(args, "device_env", False)))
     return create_procgen_env(env_name=env_name, n_envs=n_envs, is_valid=is_valid, val_env_name=args.val_env_name,
                               start_level=args.start_level, num_levels=args.num_levels, distribution_mode=args.distribution_mode,
                               num_threads=num_threads or args.num_threads, paint_vel_info=hp.get("paint_vel_info", args.paint_vel_info),
@@ -222,6 +225,20 @@ def initialize_model(device, env, hp):
     return model, obs_shape, policy
 
 
+def check_device_env(env_name, hp, algo):
+    """--device_env covers the MLP 9-observation cart-pole with a non-recurrent policy on one GPU under algo ppo / ppo-pure."""
+    if not env_name.startswith("cartpole"):
+        raise NotImplementedError(f"--device_env with env_name {env_name} is not supported: only the cart-pole (cartpole*) has a device-resident env")
+    if hp.get("recurrent", False):
+        raise NotImplementedError("--device_env with recurrent: True is not supported: the device rollout runs no GRU step")
+    if int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        raise NotImplementedError(f"--device_env runs on a single GPU: WORLD_SIZE = {os.environ['WORLD_SIZE']} is not supported")
+    if algo == "IPL":
+        raise NotImplementedError("--device_env with algo: IPL is not supported: IPL's storage reads next-observation rows on the host")
+    if algo == "sae":
+        raise NotImplementedError("--device_env with algo: sae is not supported: the sparse-autoencoder agent acts on IMPALA frames")
+
+
 def train_ppo(args):
     hp = merge_hyperparameters(get_hyperparams(args.param_name), args)
     env_name = hp.get("env_name", args.env_name)
@@ -232,6 +249,8 @@ def train_ppo(args):
         raise NotImplementedError("algo: IPL_ICM is not supported (algo: IPL is)")
     if algo not in ("ppo", "ppo-pure", "sae", "IPL"):
         raise NotImplementedError("only algo: ppo, algo: ppo-pure, algo: sae and algo: IPL are accelerated")
+    if getattr(args, "device_env", False):                  # everything the device-resident env does not cover, by name, before any env exists
+        check_device_env(env_name, hp, algo)
     if algo == "IPL":                                       # everything outside the built scope, by name, before any engine exists
         hp["learned_gamma"] = bool(hp.get("learned_gamma", False)) or bool(getattr(args, "learned_gamma", False))
         ipl_check_supported(hp, use_greedy_env=bool(getattr(args, "use_greedy_env", False)))
@@ -276,7 +295,8 @@ def train_ppo(args):
     env = make_env(env_name, n_envs, args.seed + 2 * rank, A, args, hp)
     env_valid = make_env(env_name, n_envs, args.seed + 2 * rank + 1, A, args, hp, is_valid=True) if args.use_valid_env else None
     n_groups = len(getattr(env, "env_groups", ()))
-    print(f"rollout: {n_groups} pipelined env groups" if n_groups > 1 else "rollout: serial steps")
+    print(f"rollout: {n_groups} pipelined env groups" if n_groups > 1 else
+          "rollout: device-resident env, one call per rollout" if getattr(env, "on_device", False) else "rollout: serial steps")
     logdir, model_file = create_logdir_train(args.model_file, env_name, args.exp_name, args.seed, f'__rank_{rank}' if world > 1 and rank > 0 else '')
     np.save(os.path.join(logdir, "hyperparameters.npy"), hp)
     print(f'Logging to {logdir}')
