@@ -119,7 +119,7 @@ int mi_rollout_step(mi_ctx* ctx, int32_t t, const float* rew_prev, const float* 
  *      2 block + 1 from words {0, 1} and {2, 3}.  This stream is the device env's own: CartPoleVec draws an (E, 9) numpy block whenever
  *      any env ends, which is not reproduced.
  *      mi_env_reset: every env starts a fresh episode; float(state) goes into observation slot 0.  Asynchronous.
- *      mi_env_step: one env step on the caller's actions (0 / 1), results on the host (any output may be NULL), one synchronisation; it
+ *      mi_env_step: one env step on the caller's actions (0 / 1; the mountain car below: 0 / 1 / 2), results on the host (any output may be NULL), one synchronisation; it
  *      goes through a staging slot and changes no ring (VecEnv.step, and the teacher-forcing hook of the tests).
  *      mi_env_rollout: float(state) -> observation slot 0; for t in [0, T): the policy step on slot t exactly as
  *      mi_policy_step(t, seed, NULL, NULL, NULL, NULL) enqueues it (same kernels, same Philox counters t * E + e), then the env step on
@@ -132,10 +132,34 @@ typedef struct mi_cartpole_params {
     int32_t max_steps;
 } mi_cartpole_params;
 int mi_env_cartpole_create(mi_ctx* ctx, const mi_cartpole_params* params, uint64_t seed);
+/* ---- the device-resident mountain car (the host env is common/env/vec_envs.py MountainCarVec = the reference's
+ *      discrete_env/mountain_car_pre_vec.py:15-219 on pre_vec_env.py:21-125 and helper_pre_vec.py:4-38).  A context holds ONE env: the
+ *      create call fixes its kind, and mi_env_reset / _step / _rollout / _get_state / _set_state below dispatch on it; W, the state
+ *      width, is 9 for the cart-pole and 5 here, the legal actions 0 / 1 there and 0 / 1 / 2 here.  On an MLP context with obs_dim == 5
+ *      and n_actions == 3 only; the refusals are the cart-pole's, by field name.
+ *      State: double [E][5] = {position, velocity, gravity, right_boundary, goal_position}; n_steps and episode as for the cart-pole.
+ *      A step is MountainCarVec.step in fp64 in the same operation order (contraction off): v += (a - 1) * force + cos(3 p) * (-gravity),
+ *      clipped to +-max_speed; p += v, clipped to [left_boundary, right_boundary]; v = 0 where p == left_boundary and v < 0; the env
+ *      ends where p >= goal_position and v >= goal_velocity, or when n_steps reaches max_steps, and then starts episode + 1 at once.
+ *      The reward is float(-1) with sparse_rewards, else float(sin(3 p) * 0.45 + 0.55 - 1) of the post-step, pre-reset position; done is
+ *      the step's flag, the observation float(the post-reset state).
+ *      A fresh state is low + (high - low) * u per column with the cart-pole's u, from Philox4x32-10 keyed by `seed` with the counter
+ *      {env index, episode low word, episode high word, 3 * attempt + b}, b = 0..2 giving columns 2 b and 2 b + 1 from words {0, 1} and
+ *      {2, 3}.  Attempts 0, 1, ... are drawn until !(goal_position > right_boundary) (StartSpace.sample's condition).  The loop is
+ *      bounded: after 32 rejected attempts the last draw is kept with goal_position = right_boundary.  The caller (MountainCarVec /
+ *      DeviceMountainCar) refuses range sets that accept a draw with probability below 1/2, so the fallback is taken with probability at
+ *      most 2^-32 per reset.  The velocity column has low == high == 0 and comes out exactly 0.  As for the cart-pole the stream is the
+ *      device env's own: MountainCarVec's numpy block draws are not reproduced. */
+typedef struct mi_mountain_car_params {
+    double low[5], high[5];          /* start ranges per state column */
+    double left_boundary, max_speed, force, goal_velocity;
+    int32_t max_steps, sparse_rewards;
+} mi_mountain_car_params;
+int mi_env_mountain_car_create(mi_ctx* ctx, const mi_mountain_car_params* params, uint64_t seed);
 int mi_env_reset(mi_ctx* ctx);
-int mi_env_step(mi_ctx* ctx, const int64_t* act, float* obs_out /* E x 9 */, float* rew_out, float* done_out);
+int mi_env_step(mi_ctx* ctx, const int64_t* act, float* obs_out /* E x W */, float* rew_out, float* done_out);
 int mi_env_rollout(mi_ctx* ctx, uint64_t seed);
-int mi_env_get_state(mi_ctx* ctx, double* state /* E x 9 */, int32_t* n_steps, int64_t* episode);
+int mi_env_get_state(mi_ctx* ctx, double* state /* E x W */, int32_t* n_steps, int64_t* episode);
 int mi_env_set_state(mi_ctx* ctx, const double* state, const int32_t* n_steps, const int64_t* episode);
 
 /* ---- pipelined rollout: the same step as mi_rollout_step, per ENV GROUP and split into submit / wait, so that the frame upload and

@@ -4,7 +4,10 @@ common/env/procgen_wrappers.py:45-124.  Rollout collection stays on the host (no
 
 * CartPoleVec   -- the reference's 9-observation pre-vectorised cart-pole (discrete_env/cartpole_pre_vec.py) restated in numpy,
                    the plumbing config C1 (MLPModel(9, ...)).
-* DeviceCartPole -- the same env resident on the device (opt-in, train.py --device_env): the one env here whose dynamics are ours.
+* DeviceCartPole -- the same env resident on the device (opt-in, train.py --device_env).
+* MountainCarVec -- the reference's 5-observation pre-vectorised mountain car (discrete_env/mountain_car_pre_vec.py) restated in numpy
+                   and pinned to the reference's own class by a trajectory fixture (MLPModel(5, ...), 3 actions).
+* DeviceMountainCar -- the same env resident on the device (opt-in, train.py --device_env).
 * SyntheticFrames -- random uint8 64x64x3 frames, N(0,1) rewards, Bernoulli(0.01) dones: the synthetic
                    learner-side workload of SURVEY 8(d) / bench.py.
 * create_procgen_env -- the real engine if the `procgen` package is importable (it is not in the build image).
@@ -149,7 +152,40 @@ CARTPOLE_PARAM_RANGE = {"degrees": [12], "h_range": [2.4], "min_gravity": [9.8, 
                         "min_pole_mass": [0.1, .2], "max_pole_mass": [0.2, .4], "min_force_mag": [10.], "max_force_mag": [10.]}
 
 
-class DeviceCartPole:
+class _DeviceEnv:
+    """What the device-resident envs share: the env lives in an engine context.  `attach_engine(engine)` (the agent does it) creates it
+    there through the subclass's `_create`; reset() / step(act) then go through mi_env_reset / mi_env_step, one synchronisation each."""
+    on_device = True
+    engine = None
+
+    def attach_engine(self, engine):
+        """Create the env in `engine`'s context (an MLP engine with this env's observation width, action count and n_envs environments)."""
+        if self.engine is engine:
+            return
+        if engine.E != self.n_envs:
+            raise ValueError(f"engine has {engine.E} envs, the env {self.n_envs}")
+        self._create(engine)
+        self.engine = engine
+
+    def _eng(self):
+        if self.engine is None:
+            raise RuntimeError(f"{type(self).__name__} is not attached to an engine yet: construct the agent with it (or call attach_engine) first")
+        return self.engine
+
+    def reset(self):
+        eng = self._eng()
+        eng.env_reset()
+        return eng.get_obs(0)
+
+    def step(self, act):
+        obs, rew, done = self._eng().env_step(act)
+        return obs, rew, done, StepInfo(self.n_envs, {"env_reward": rew})
+
+    def close(self):
+        pass
+
+
+class DeviceCartPole(_DeviceEnv):
     """CartPoleVec with the env on the device (train.py --device_env; csrc/cartpole.hip, mi_env_* in include/mi355ppo.h): state,
     physics, termination, episode resets, reward and done live in HBM next to the policy, so that the agent collects a whole rollout
     with ONE call and no host round trip per step (agents/ppo.py `_collect_device`).  Same constructor arguments, spaces, ranges,
@@ -164,7 +200,6 @@ class DeviceCartPole:
     The env lives in an engine context: `attach_engine(engine)` (the agent does it) creates it there; reset() / step(act) then go through
     mi_env_reset / mi_env_step, one synchronisation each, so the VecEnv protocol and the public predict / store loop still work.
     Limits: the 9-observation MLP cart-pole, non-recurrent policies, one GPU."""
-    on_device = True
 
     def __init__(self, n_envs, degrees=12, h_range=2.4, min_gravity=9.8, max_gravity=10.4, min_pole_length=0.5, max_pole_length=1.0,
                  min_cart_mass=1.0, max_cart_mass=1.5, min_pole_mass=0.1, max_pole_mass=0.2, min_force_mag=10., max_force_mag=10.,
@@ -181,31 +216,8 @@ class DeviceCartPole:
         self.action_space = _Space(n=2)
         self.engine = None
 
-    def attach_engine(self, engine):
-        """Create the env in `engine`'s context (an MLP engine with 9 observations, 2 actions and n_envs environments)."""
-        if self.engine is engine:
-            return
-        if engine.E != self.n_envs:
-            raise ValueError(f"engine has {engine.E} envs, the env {self.n_envs}")
+    def _create(self, engine):
         engine.env_cartpole_create(self.low, self.high, self.x_threshold, self.theta_threshold, self.max_steps, self.seed)
-        self.engine = engine
-
-    def _eng(self):
-        if self.engine is None:
-            raise RuntimeError("DeviceCartPole is not attached to an engine yet: construct the agent with it (or call attach_engine) first")
-        return self.engine
-
-    def reset(self):
-        eng = self._eng()
-        eng.env_reset()
-        return eng.get_obs(0)
-
-    def step(self, act):
-        obs, rew, done = self._eng().env_step(act)
-        return obs, rew, done, StepInfo(self.n_envs, {"env_reward": rew})
-
-    def close(self):
-        pass
 
 
 def create_cartpole(hyperparameters, is_valid=False, seed=0, n_envs=None, device=False):
@@ -218,6 +230,162 @@ def create_cartpole(hyperparameters, is_valid=False, seed=0, n_envs=None, device
     if "max_steps" in hyperparameters:
         kw["max_steps"] = hyperparameters["max_steps"]
     cls = DeviceCartPole if device else CartPoleVec
+    return cls(n_envs if n_envs is not None else hyperparameters.get("n_envs", 32), seed=seed, **kw)
+
+
+def mountain_car_acceptance(min_goal_position, max_goal_position, min_right_boundary, max_right_boundary):
+    """P(goal_position <= right_boundary) for independent uniforms goal_position ~ U[min_goal, max_goal], right_boundary ~ U[min_right,
+    max_right]: the probability that the start space accepts a draw.  With F the distribution function of goal_position and H its
+    antiderivative (0 below min_goal, a parabola up to max_goal, a line of slope 1 beyond), it is the mean of F over the boundary's
+    range, (H(max_right) - H(min_right)) / (max_right - min_right); a range of width 0 is a point."""
+    a, b, c, d = float(min_goal_position), float(max_goal_position), float(min_right_boundary), float(max_right_boundary)
+    if b == a:
+        F, H = (lambda r: 1.0 if r >= a else 0.0), (lambda r: max(r - a, 0.0))
+    else:
+        F = lambda r: min(max((r - a) / (b - a), 0.0), 1.0)
+        H = lambda r: 0.0 if r <= a else (r - a) ** 2 / (2 * (b - a)) if r <= b else (b - a) / 2 + (r - b)
+    return F(c) if d == c else (H(d) - H(c)) / (d - c)
+
+
+def _mountain_car_setup(self, n_envs, goal_velocity, left_boundary, min_start_position, max_start_position, max_speed, min_goal_position,
+                        max_goal_position, min_gravity, max_gravity, min_right_boundary, max_right_boundary, force, max_steps, sparse_rewards, seed):
+    """The constructor part that MountainCarVec and DeviceMountainCar share: the reference's three range assertions
+    (mountain_car_pre_vec.py:141-146), the start ranges per state column (:158-159) and the scalars of the step."""
+    assert min_start_position >= left_boundary, f"min_start_position ({min_start_position}) must be >= left_boundary ({left_boundary})"
+    assert max_start_position <= min_right_boundary, f"max_start_position ({max_start_position}) must be <= min_right_boundary ({min_right_boundary})"
+    assert max_goal_position <= max_right_boundary, f"max_goal_position ({max_goal_position}) must be <= max_right_boundary ({max_right_boundary})"
+    if n_envs < 2:
+        raise Exception("n_envs must be greater than or equal to 2")
+    accept = mountain_car_acceptance(min_goal_position, max_goal_position, min_right_boundary, max_right_boundary)
+    if not accept >= 0.5:
+        raise ValueError(f"mountain_car: the start space accepts a draw (goal_position <= right_boundary) with probability {accept:.4g} < 1/2 "
+                         f"for min_goal_position {min_goal_position}, max_goal_position {max_goal_position}, min_right_boundary "
+                         f"{min_right_boundary}, max_right_boundary {max_right_boundary}: the rejection sampling would run long or for ever")
+    self.n_envs = self.num_envs = n_envs
+    self.max_steps, self.sparse_rewards, self.seed = max_steps, bool(sparse_rewards), int(seed)
+    self.goal_velocity, self.left_boundary, self.max_speed, self.force = goal_velocity, left_boundary, max_speed, force
+    self.low = np.array([min_start_position, 0, min_gravity, min_right_boundary, min_goal_position], dtype=np.float64)
+    self.high = np.array([max_start_position, 0, max_gravity, max_right_boundary, max_goal_position], dtype=np.float64)
+    self.observation_space = _Space(shape=(5,))
+    self.action_space = _Space(n=3)
+
+
+class MountainCarVec:
+    """The reference's pre-vectorised mountain car (discrete_env/mountain_car_pre_vec.py:15-219 on discrete_env/pre_vec_env.py:21-125 and
+    helper_pre_vec.py:4-38), restated in numpy float64: the env of the `mountain_car` hyper-parameter set.  Observation = the 5-column state
+
+        [position, velocity, gravity, right_boundary, goal_position]
+
+    -- the two dynamic variables plus the three parameters an episode was drawn with; 3 actions (push left / none / push right).  A step
+    (:194-209): v += (a - 1) * force + cos(3 p) * (-gravity), clipped to +-max_speed; p += v, clipped to [left_boundary, right_boundary];
+    v = 0 where the car sits on the left wall with v < 0; terminated where p >= goal_position and v >= goal_velocity; truncation at
+    max_steps (pre_vec_env.py:84-86).  Reward -1 with sparse_rewards, else the height sin(3 p) * 0.45 + 0.55 - 1 of the post-step,
+    pre-reset position; info = {'env_reward': reward}.  When ANY env ends a whole block is drawn and only the ended rows take their
+    values, and `done` is the `terminated` array AFTER the reset.
+
+    Episode starts are StartSpace.sample with its condition (helper_pre_vec.py:28-38): (10 n, 5) uniforms, rows with goal_position >
+    right_boundary dropped, further (10 n, 5) blocks while fewer than n rows remain, the first n kept.  The generator is numpy's
+    default_rng(seed) -- what gymnasium's seeding.np_random(seed) constructs -- and is consumed exactly as the reference consumes it,
+    including the draw its constructor makes through reset(seed=seed) before the caller's own reset().  Parity is PINNED:
+    tests/golden/g17_mountain_car.npz holds trajectories of the reference's own class (tests/golden/make_golden_mountain_car.py) and
+    tests/test_mountain_car_host.py reproduces them bit for bit.
+
+    One addition: a range set whose draws are accepted with probability below 1/2 (`mountain_car_acceptance`) is refused at
+    construction; the reference would loop long or for ever on it."""
+
+    def __init__(self, n_envs=2, goal_velocity=0, left_boundary=-1.2, min_start_position=-0.6, max_start_position=-0.4, max_speed=0.07,
+                 min_goal_position=0.5, max_goal_position=3, min_gravity=0.001, max_gravity=0.0025, min_right_boundary=0.6,
+                 max_right_boundary=5, force=0.001, max_steps=500, sparse_rewards=True, seed=0, **_ignored):
+        _mountain_car_setup(self, n_envs, goal_velocity, left_boundary, min_start_position, max_start_position, max_speed, min_goal_position,
+                            max_goal_position, min_gravity, max_gravity, min_right_boundary, max_right_boundary, force, max_steps,
+                            sparse_rewards, seed)
+        self.rng = np.random.default_rng(seed)
+        self.reward = np.full(n_envs, -1.0)
+        self.info = StepInfo(n_envs, {"env_reward": self.reward})
+        self.state = np.zeros((n_envs, 5))
+        self.reset()                                     # the reference's constructor ends in reset(seed=seed): one sample is consumed here
+
+    def _sample(self):
+        n = self.n_envs
+        x = self.rng.uniform(low=self.low, high=self.high, size=(n * 10, 5))
+        x = x[(x[:, 4] > x[:, 3]) == False]              # noqa: E712 (the reference's expression: a NaN row would be kept)
+        while len(x) < n:
+            z = self.rng.uniform(low=self.low, high=self.high, size=(n * 10, 5))
+            x = np.vstack((x, z[(z[:, 4] > z[:, 3]) == False]))      # noqa: E712
+        return x[:n]
+
+    def _set(self):
+        fresh = self._sample()
+        self.state[self.terminated] = fresh[self.terminated]
+        self.n_steps[self.terminated] = 0
+        return self.state
+
+    def reset(self):
+        self.terminated = np.full(self.n_envs, True)
+        self.n_steps = np.zeros(self.n_envs)
+        return self._set()
+
+    def step(self, act):
+        act = np.asarray(act)
+        assert act.size == self.n_envs and np.all(act < 3)
+        p, v, g, rb, gp = self.state.T
+        v = v + ((act.reshape(-1) - 1) * self.force + np.cos(3 * p) * (-g))
+        v = np.clip(v, -self.max_speed, self.max_speed)
+        p = np.clip(p + v, self.left_boundary, rb)
+        v[(p == self.left_boundary) & (v < 0)] = 0
+        self.terminated = (p >= gp) & (v >= self.goal_velocity)
+        self.state = np.vstack((p, v, g, rb, gp)).T
+        if not self.sparse_rewards:
+            self.reward = np.sin(3 * p) * 0.45 + 0.55 - 1
+            self.info = StepInfo(self.n_envs, {"env_reward": self.reward})
+        self.n_steps += 1
+        self.terminated[self.n_steps >= self.max_steps] = True
+        if np.any(self.terminated):
+            self._set()
+        return self.state, self.reward, self.terminated, self.info
+
+    def close(self):
+        pass
+
+
+class DeviceMountainCar(_DeviceEnv):
+    """MountainCarVec with the env on the device (train.py --device_env; csrc/mountain_car.hip, mi_env_* in include/mi355ppo.h): same
+    constructor arguments, assertions, spaces, start ranges and scalars (the same fp64 bits) and the same step arithmetic in fp64 in
+    the same operation order.  As for DeviceCartPole the stream of the episode starts is the device env's own: the start of episode k of
+    env e comes from Philox4x32-10 keyed by `seed`, counter {e, k low word, k high word, 3 * attempt + block}; attempts 0, 1, ... are
+    drawn until goal_position <= right_boundary, and after 32 rejected attempts the last draw is kept with goal_position =
+    right_boundary (probability at most 2^-32 per reset under the acceptance rule of the constructor).  MountainCarVec's numpy block
+    draws are NOT reproduced: the two classes agree step for step until the first reset and in distribution afterwards.
+    Limits: the 5-observation MLP mountain car, non-recurrent policies, one GPU."""
+
+    def __init__(self, n_envs=2, goal_velocity=0, left_boundary=-1.2, min_start_position=-0.6, max_start_position=-0.4, max_speed=0.07,
+                 min_goal_position=0.5, max_goal_position=3, min_gravity=0.001, max_gravity=0.0025, min_right_boundary=0.6,
+                 max_right_boundary=5, force=0.001, max_steps=500, sparse_rewards=True, seed=0, **_ignored):
+        _mountain_car_setup(self, n_envs, goal_velocity, left_boundary, min_start_position, max_start_position, max_speed, min_goal_position,
+                            max_goal_position, min_gravity, max_gravity, min_right_boundary, max_right_boundary, force, max_steps,
+                            sparse_rewards, seed)
+
+    def _create(self, engine):
+        engine.env_mountain_car_create(self.low, self.high, self.left_boundary, self.max_speed, self.force, self.goal_velocity, self.max_steps,
+                                       self.sparse_rewards, self.seed)
+
+
+# create_mountain_car (discrete_env/mountain_car_pre_vec.py:312-328): [training value, validation value] of every constructor argument
+MOUNTAIN_CAR_PARAM_RANGE = {"goal_velocity": [0], "left_boundary": [-1.2], "min_right_boundary": [0.6, 1.], "max_right_boundary": [1., 5.],
+                            "max_speed": [0.07], "min_goal_position": [0, 0.6], "max_goal_position": [0.6, 3], "force": [0.001],
+                            "min_gravity": [0.001, 0.0015], "max_gravity": [0.0015, 0.0025], "sparse_rewards": [True]}
+
+
+def create_mountain_car(hyperparameters, is_valid=False, seed=0, n_envs=None, device=False):
+    """create_mountain_car / create_pre_vec / assign_env_vars: as create_cartpole -- the validation env takes the SECOND value of every
+    range (goal and right wall further out, stronger gravity; about 21 % of its start draws are rejected), a hyper-parameter `<name>`
+    (training) or `<name>_v` (validation) overrides a range entry, sparse_rewards among them; max_steps may come from the
+    hyper-parameters too.  device=True: the same arguments build the device-resident DeviceMountainCar."""
+    suffix, i = ("_v", -1) if is_valid else ("", 0)
+    kw = {k: hyperparameters.get(k + suffix, v[i]) for k, v in MOUNTAIN_CAR_PARAM_RANGE.items()}
+    if "max_steps" in hyperparameters:
+        kw["max_steps"] = hyperparameters["max_steps"]
+    cls = DeviceMountainCar if device else MountainCarVec
     return cls(n_envs if n_envs is not None else hyperparameters.get("n_envs", 32), seed=seed, **kw)
 
 

@@ -5,10 +5,6 @@
 #include "common.h"
 #include "policy_math.h"
 
-// 53-bit uniform in [0, 1) from two Philox words: every operation is exact in fp64
-__device__ __forceinline__ double cartpole_u53(uint32_t w0, uint32_t w1) {
-    return ((double)(w0 >> 5) * 67108864.0 + (double)(w1 >> 6)) * (1.0 / 9007199254740992.0);
-}
 // The start of episode `episode` of env e: low + (high - low) * u per column (start_space, cartpole_pre_vec.py:163-171).  The stream is
 // the device env's own: Philox4x32-10 keyed by the env's seed, counter {e, episode lo, episode hi, block}, block 0..4 = two uniforms each
 // (18 words needed, 20 drawn).  CartPoleVec draws a whole (E, 9) numpy block whenever any env ends; that is not reproduced.
@@ -19,8 +15,8 @@ __device__ __forceinline__ void cartpole_fresh(const CartPoleArgs& p, unsigned l
         uint32_t c[4] = {(uint32_t)e, (uint32_t)(unsigned long long)episode, (uint32_t)((unsigned long long)episode >> 32), (uint32_t)b};
         uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
         philox4x32_10(c, k);
-        s[2 * b] = p.low[2 * b] + (p.high[2 * b] - p.low[2 * b]) * cartpole_u53(c[0], c[1]);
-        if (2 * b + 1 < 9) s[2 * b + 1] = p.low[2 * b + 1] + (p.high[2 * b + 1] - p.low[2 * b + 1]) * cartpole_u53(c[2], c[3]);
+        s[2 * b] = p.low[2 * b] + (p.high[2 * b] - p.low[2 * b]) * philox_u53(c[0], c[1]);
+        if (2 * b + 1 < 9) s[2 * b + 1] = p.low[2 * b + 1] + (p.high[2 * b + 1] - p.low[2 * b + 1]) * philox_u53(c[2], c[3]);
     }
 }
 __device__ __forceinline__ void cartpole_store(const double* s, double* state_row, float* obs_row) {

@@ -171,9 +171,11 @@ struct mi_ctx {
     // minibatch's pred / reward, the loss kernel's fp64 block partials
     int32_t* ipl_idx2 = nullptr; float *ipl_nv = nullptr, *ipl_gnext = nullptr, *ipl_pred = nullptr, *ipl_rew = nullptr; double* ipl_partial = nullptr;
     int ipl_last_n = 0;
-    // device-resident cart-pole (mi_env_cartpole_create; cartpole.hip): state [E][9] fp64, steps of the running episode, episode number;
-    // the staging slot of mi_env_step {actions, next observation, reward, done}, which leaves the rings alone
-    bool env_on = false; CartPoleArgs env_args = {}; unsigned long long env_seed = 0;
+    // device-resident env (mi_env_cartpole_create, cartpole.hip: env_width 9, 2 actions; mi_env_mountain_car_create, mountain_car.hip:
+    // env_width 5, 3 actions): state [E][env_width] fp64, steps of the running episode, episode number; the staging slot of mi_env_step
+    // {actions, next observation, reward, done}, which leaves the rings alone
+    bool env_on = false; EnvKind env_kind = ENV_CARTPOLE; int env_width = 0;
+    CartPoleArgs env_args = {}; MountainCarArgs env_mc = {}; unsigned long long env_seed = 0;
     double* env_state = nullptr; int32_t* env_nsteps = nullptr; long long* env_episode = nullptr;
     int32_t* env_s_act = nullptr; float *env_s_obs = nullptr, *env_s_rew = nullptr, *env_s_done = nullptr;
     struct mi_sae* sae = nullptr;     // the sparse-autoencoder agent's state (sae.hip: mi_sae_create; released by mi_sae_destroy or mi_destroy)

@@ -52,3 +52,7 @@ __device__ __forceinline__ float philox_uniform(unsigned long long seed, unsigne
     philox4x32_10(c, k);
     return (float)(c[0] >> 8) * (1.0f / 16777216.0f);     // [0,1), 24 bits
 }
+// 53-bit uniform in [0, 1) from two Philox words (the episode starts of the device-resident envs): every operation is exact in fp64
+__device__ __forceinline__ double philox_u53(uint32_t w0, uint32_t w1) {
+    return ((double)(w0 >> 5) * 67108864.0 + (double)(w1 >> 6)) * (1.0 / 9007199254740992.0);
+}

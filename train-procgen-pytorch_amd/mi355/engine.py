@@ -39,6 +39,11 @@ class _CartPoleParams(C.Structure):
                 ("max_steps", C.c_int32)]
 
 
+class _MountainCarParams(C.Structure):
+    _fields_ = [("low", C.c_double * 5), ("high", C.c_double * 5), ("left_boundary", C.c_double), ("max_speed", C.c_double),
+                ("force", C.c_double), ("goal_velocity", C.c_double), ("max_steps", C.c_int32), ("sparse_rewards", C.c_int32)]
+
+
 class _IplHParams(C.Structure):
     _fields_ = [("gamma", C.c_float), ("alpha", C.c_float), ("entropy_coef", C.c_float), ("flags", C.c_int32)]
 
@@ -60,7 +65,7 @@ EXPORTS = ("mi_last_error mi_create mi_destroy mi_sync mi_host_alloc mi_host_fre
            "mi_sae_create mi_sae_destroy mi_sae_param_count mi_sae_set_params mi_sae_get_params mi_sae_get_grads mi_sae_set_adam_state mi_sae_get_adam_state mi_sae_put_ring "
            "mi_sae_get_hidden mi_sae_get_logits mi_sae_step mi_sae_minibatch mi_sae_probe_minibatch mi_sae_optimizer_step mi_sae_debug_forward "
            "mi_ipl_minibatch mi_ipl_read_pred mi_predict_greedy mi_op_ipl_loss mi_op_ipl_greedy "
-           "mi_env_cartpole_create mi_env_reset mi_env_step mi_env_rollout mi_env_get_state mi_env_set_state").split()
+           "mi_env_cartpole_create mi_env_mountain_car_create mi_env_reset mi_env_step mi_env_rollout mi_env_get_state mi_env_set_state").split()
 
 
 def load_library():
@@ -266,19 +271,29 @@ class Engine:
         self._chk(self.lib.mi_read_field(self._ctx, C.c_int32(field), _fp(out), C.c_int64(out.size)))
         return out
 
-    # ------------------------------------------------------------------ device-resident cart-pole env (mi_env_*)
+    # ------------------------------------------------------------------ device-resident envs (mi_env_*): cart-pole, mountain car
+    _env_width = 0          # columns of the env's state = the observation width: set by the create call (9 cart-pole, 5 mountain car)
+
     def env_cartpole_create(self, low, high, x_threshold, theta_threshold, max_steps, seed=0):
         low, high = np.asarray(low, np.float64).reshape(9), np.asarray(high, np.float64).reshape(9)
         p = _CartPoleParams((C.c_double * 9)(*low), (C.c_double * 9)(*high), float(x_threshold), float(theta_threshold), int(max_steps))
         self._chk(self.lib.mi_env_cartpole_create(self._ctx, C.byref(p), C.c_uint64(int(seed) & (2 ** 64 - 1))))
+        self._env_width = 9
+
+    def env_mountain_car_create(self, low, high, left_boundary, max_speed, force, goal_velocity, max_steps, sparse_rewards=True, seed=0):
+        low, high = np.asarray(low, np.float64).reshape(5), np.asarray(high, np.float64).reshape(5)
+        p = _MountainCarParams((C.c_double * 5)(*low), (C.c_double * 5)(*high), float(left_boundary), float(max_speed), float(force),
+                               float(goal_velocity), int(max_steps), int(bool(sparse_rewards)))
+        self._chk(self.lib.mi_env_mountain_car_create(self._ctx, C.byref(p), C.c_uint64(int(seed) & (2 ** 64 - 1))))
+        self._env_width = 5
 
     def env_reset(self):
         """Every env starts a fresh episode; observation slot 0 holds float32(state).  Asynchronous."""
         self._chk(self.lib.mi_env_reset(self._ctx))
 
     def env_state(self):
-        """-> (state (E, 9) float64, n_steps (E,) int32, episode (E,) int64) as they are on the device."""
-        s, n, ep = np.empty((self.E, 9), np.float64), np.empty(self.E, np.int32), np.empty(self.E, np.int64)
+        """-> (state (E, W) float64, n_steps (E,) int32, episode (E,) int64) as they are on the device; W = the created env's state width."""
+        s, n, ep = np.empty((self.E, self._env_width or 1), np.float64), np.empty(self.E, np.int32), np.empty(self.E, np.int64)
         self._chk(self.lib.mi_env_get_state(self._ctx, _fp(s), _fp(n), _fp(ep)))
         return s, n, ep
 
@@ -286,17 +301,17 @@ class Engine:
         s = None if state is None else np.ascontiguousarray(state, dtype=np.float64)
         n = None if n_steps is None else np.ascontiguousarray(n_steps, dtype=np.int32)
         ep = None if episode is None else np.ascontiguousarray(episode, dtype=np.int64)
-        for a, size, name in ((s, 9 * self.E, "state"), (n, self.E, "n_steps"), (ep, self.E, "episode")):
+        for a, size, name in ((s, (self._env_width or 1) * self.E, "state"), (n, self.E, "n_steps"), (ep, self.E, "episode")):
             if a is not None and a.size != size:
                 raise EngineError(f"env_set_state: {name} must have {size} elements")
         self._chk(self.lib.mi_env_set_state(self._ctx, _fp(s), _fp(n), _fp(ep)))
 
     def env_step(self, act):
-        """One env step on caller actions -> (obs (E, 9), rew (E,), done (E,)) float32 on the host; the rings are not touched."""
+        """One env step on caller actions -> (obs (E, W), rew (E,), done (E,)) float32 on the host; the rings are not touched."""
         act = np.ascontiguousarray(act, dtype=np.int64).reshape(-1)
         if act.size != self.E:
             raise EngineError(f"env_step: {act.size} actions for {self.E} envs")
-        obs, rew, done = np.empty((self.E, 9), np.float32), np.empty(self.E, np.float32), np.empty(self.E, np.float32)
+        obs, rew, done = np.empty((self.E, self._env_width or 1), np.float32), np.empty(self.E, np.float32), np.empty(self.E, np.float32)
         self._chk(self.lib.mi_env_step(self._ctx, _fp(act), _fp(obs), _fp(rew), _fp(done)))
         return obs, rew, done
 

@@ -11,7 +11,10 @@ there), the log directory layout logs/train/<env>/<exp>/<time>__seed_<seed> with
 format, `--model_file auto` (create_logdir_train, train.py:277-294: the single run directory under the experiment that holds
 model_*.pth is reused and its newest checkpoint loaded -- the reference finds that file and then still hands 'auto' to torch.load),
 `--detect_nan`.  Different on purpose: `--device` defaults to gpu and `cpu` is refused (there is no CPU fallback); config.yml is
-read relative to this file instead of the hard-coded GLOBAL_DIR of helper_local.py:28; new flags --precision, --rollout_groups, --device_env."""
+read relative to this file instead of the hard-coded GLOBAL_DIR of helper_local.py:28; new flags --precision, --rollout_groups, --device_env.
+`--env_name cartpole*` and `--env_name mountain_car` run the numpy restatements of the reference's pre-vectorised envs (CartPoleVec,
+MountainCarVec) with the serial step; `--device_env` keeps either env on the device (DeviceCartPole, DeviceMountainCar).  A --device_env
+run is not the host run's trajectory past the first episode reset: episode starts come from the device env's own Philox stream."""
 import os
 import sys
 
@@ -36,7 +39,7 @@ from agents.ppo import PPO
 from agents.ppo_pure import PPOPure
 from agents.sae import SAE, check_supported as sae_check_supported
 from agents.ipl import IPL, check_supported as ipl_check_supported
-from common.env.vec_envs import EnvGroups, SyntheticFrames, create_cartpole, create_procgen_env
+from common.env.vec_envs import EnvGroups, SyntheticFrames, create_cartpole, create_mountain_car, create_procgen_env
 from common.logger import Logger, SimpleLogger
 from common.misc_util import set_global_seeds
 from common.model import ImpalaModel, MLPModel
@@ -123,7 +126,7 @@ def add_training_args(p):
     p.add_argument('--rollout_groups', type=int, default=0,
                    help="env groups of the pipelined rollout (one group's frame upload + forward beside the host's env.step of another); 0 = auto (from 128 envs per rank: 4, or 2 + 2 when a validation env runs beside the training env; else 2; a recurrent policy: 1); 1 = the reference's serial step; a recurrent policy is pipelined only with an explicit G >= 2")
     p.add_argument('--device_env', action="store_true",
-                   help="cartpole* only: the env lives on the device (state, physics, resets, reward and done in HBM) and a whole rollout is one call with no host round trip per step; episode starts come from the device env's own Philox stream, not numpy's.  Non-recurrent MLP policies, one GPU, algo ppo / ppo-pure")
+                   help="cartpole* and mountain_car only: the env lives on the device (state, physics, resets, reward and done in HBM) and a whole rollout is one call with no host round trip per step; episode starts come from the device env's own Philox stream, not numpy's.  Non-recurrent MLP policies, one GPU, algo ppo / ppo-pure")
     p.add_argument('--x_entropy_coef', type=float, default=None)
     p.add_argument('--algo', type=str, default=None, choices=['ppo', 'ppo-pure', 'sae', 'IPL'],
                    help="overrides the set's `algo`: ppo = the reference's agents/ppo.py (a recurrent policy's GRU stays frozen), ppo-pure = agents/ppo_pure.py (a recurrent policy is trained through its GRU with BPTT; single GPU), sae = agents/sae.py (a sparse autoencoder on the block-3 features of the trained IMPALA policy given by --model_file, then a linear probe on its codes; single GPU, use --param_name sae), IPL = agents/IPL.py (non-recurrent, single GPU; sets hard-500-ipl and ipl_cartpole)")
@@ -170,9 +173,10 @@ def create_logdir_train(model_file, env_name, exp_name, seed, rank_suffix=""):
 def _one_env(env_name, n_envs, seed, A, args, hp, is_valid, ret_rms=None, num_threads=None):
     if env_name == "synthetic":
         return SyntheticFrames(n_envs, A, seed)
-    if env_name.startswith("cartpole") or env_name == "mountain_car":
-        if env_name == "mountain_car":
-            raise NotImplementedError("mountain_car: only the cart-pole numpy env is built on the host side")
+    if env_name == "mountain_car":
+        # 5 observations, 3 actions -> MLPModel(5, ...); --device_env: the same env resident on the device (DeviceMountainCar)
+        return create_mountain_car(hp, is_valid, seed=seed, n_envs=n_envs, device=bool(getattr(args, "device_env", False)))
+    if env_name.startswith("cartpole"):
         # 9 observations -> MLPModel(9, ...), BASELINE config 1; --device_env: the same env resident on the device (DeviceCartPole)
         return create_cartpole(hp, is_valid, seed=seed, n_envs=n_envs, device=bool(getattr(args, "device_env", False)))
     return create_procgen_env(env_name=env_name, n_envs=n_envs, is_valid=is_valid, val_env_name=args.val_env_name,
@@ -200,7 +204,7 @@ def make_env(env_name, n_envs, seed, A, args, hp, is_valid=False):
     if G <= 0:
         # auto: 4 chains keep the GPU's stream slots busy; with a validation env the agent runs both rollouts as lanes of one loop, 2 + 2
         G = (2 if getattr(args, "use_valid_env", False) else 4) if n_envs >= 128 and n_envs % 8 == 0 else 2
-    if G == 1 or n_envs % G or (n_envs // G) % 2 or env_name.startswith("cartpole"):
+    if G == 1 or n_envs % G or (n_envs // G) % 2 or env_name.startswith("cartpole") or env_name == "mountain_car":
         return _one_env(env_name, n_envs, seed, A, args, hp, is_valid)
     rms = None
     if env_name != "synthetic" and hp.get("normalize_rew", True):
@@ -226,9 +230,10 @@ def initialize_model(device, env, hp):
 
 
 def check_device_env(env_name, hp, algo):
-    """--device_env covers the MLP 9-observation cart-pole with a non-recurrent policy on one GPU under algo ppo / ppo-pure."""
-    if not env_name.startswith("cartpole"):
-        raise NotImplementedError(f"--device_env with env_name {env_name} is not supported: only the cart-pole (cartpole*) has a device-resident env")
+    """--device_env covers the MLP 9-observation cart-pole and the MLP 5-observation mountain car with a non-recurrent policy on one GPU
+    under algo ppo / ppo-pure."""
+    if not (env_name.startswith("cartpole") or env_name == "mountain_car"):
+        raise NotImplementedError(f"--device_env with env_name {env_name} is not supported: only the cart-pole (cartpole*) and mountain_car have a device-resident env")
     if hp.get("recurrent", False):
         raise NotImplementedError("--device_env with recurrent: True is not supported: the device rollout runs no GRU step")
     if int(os.environ.get("WORLD_SIZE", 1)) > 1:
