@@ -443,6 +443,26 @@ int mi_op_gemm(mi_ctx* ctx, int32_t M, int32_t N, int32_t K, const float* A, int
  * Outputs are poisoned and followed by canary bands as in mi_op_resblock. */
 int mi_op_fc_bf16(mi_ctx* ctx, int32_t mode, int32_t n, int32_t D, const float* x, const float* W, const float* b, const float* dy,
                   float* out, float* out_b);
+/* op-level: the fixed-order sums behind every weight and bias gradient (csrc/reduce.hip) on caller data through the production launchers,
+ * any context.  The targets are in / out (the kernels accumulate) and sit in poisoned, canary-banded buffers as in mi_op_resblock.
+ * mode 0: launch_reduce_slabs.  src [a = nslab][b = slab_len] (src_len = a * b); dst_w [n_w] += the sums of elements [0, n_w), dst_b [n_b] +=
+ *         those of [n_w, n_w + n_b); elements past n_w + n_b are dropped.  dst_b is NULL exactly when n_b = 0 (the column sum's use).
+ * mode 1: launch_reduce_all_slabs, n_desc (<= 64) layers in one launch.  desc: n_desc x {src_off, w_off, b_off, nslab, slab_len, n_w} (int64;
+ *         offsets, slab_len and n_w multiples of 4); src = the slab workspace (src_len floats), dst_w = one flat gradient vector of n_w floats:
+ *         layer k adds its first n_w[k] sums at w_off[k] and the other slab_len[k] - n_w[k] at b_off[k].  a, b, ld, dst_b, n_b unused.
+ * mode 2: launch_colsum_acc.  src = dY [a = M][ld], dst_w = db [n_w = b = N] += the column sums of the first N columns; the workspace is
+ *         exactly the engine's 64 x 4096 floats.  N > 4096 is refused by the launcher (-4) before anything is launched. */
+int mi_op_reduce(mi_ctx* ctx, int32_t mode, const float* src, int64_t src_len, int32_t a, int32_t b, int32_t ld, const int64_t* desc,
+                 int32_t n_desc, float* dst_w, int64_t n_w, float* dst_b, int32_t n_b);
+/* op-level: the optimizer tail on caller vectors -- partial sums of squares, then clip + Adam + zero_grad, with the host scalars from the
+ * code mi_optimizer_step and mi_sae_optimizer_step use.  p, g, m, v [n] in / out; *gnorm_out = the unclipped gradient norm.
+ * variant 0: one vector, 128 partial sums (mi_optimizer_step).  variant 1: a second vector p2, g2, m2, v2 [n2 >= 4] under the same norm (256
+ * partial sums), stepped in four pieces [off5[k], off5[k + 1]) with 0 = off5[0] < .. < off5[4] = n2 (mi_optimizer_step after mi_gru_train).
+ * variant 2: the SAE agent's kernel with torch's own constants (mi_sae_optimizer_step).  The second vector is NULL / 0 outside variant 1. */
+int mi_op_adam(mi_ctx* ctx, int32_t variant, int64_t n, float* p, float* g, float* m, float* v, int64_t n2, float* p2, float* g2, float* m2,
+               float* v2, const int64_t* off5, float lr, float max_norm, int32_t step, float* gnorm_out);
+/* op-level: the cross-rank merge of R (<= 4096) advantage statistics {count, mean, M2} (fp64) -> stats3_out, as mi_adv_normalize_global runs it */
+int mi_op_adv_merge(mi_ctx* ctx, const double* all, int32_t R, double* stats3_out);
 int mi_selftest_mfma(mi_ctx* ctx, float* max_err);
 /* what the last mi_minibatch left in the activation buffers (first n samples), fp32 NHWC: which = 8 * block + k, k = 0 pooled map,
  * 1 res1.conv1 out, 2 res1 out, 3 res2.conv1 out, 4 block out, 5 max-pool arg-max (window position ky*3+kx); which = 100: features

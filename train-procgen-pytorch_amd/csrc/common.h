@@ -150,7 +150,9 @@ struct SlabDesc { long long src_off, w_off, b_off; int nslab, slab_len, n_w; };
 void launch_reduce_all_slabs(const float* ws, float* grads, const SlabDesc* d_desc, int n_desc, int max_slab_len, hipStream_t st);
 void launch_reduce_slabs(const float* partial, int nslab, int slab_len, float* dst_w, int n_w, float* dst_b, int n_b,
                          hipStream_t st);
-void launch_colsum_acc(const float* dY, int M, int N, int ld, float* db, float* col_ws /* >= 64 x 4096 floats */, hipStream_t st);
+// N <= COLSUM_MAX_N: up to 64 rows of N partial sums go through col_ws; a wider N is refused (mi_launch_fail) and nothing is launched
+constexpr int COLSUM_MAX_N = 4096;
+void launch_colsum_acc(const float* dY, int M, int N, int ld, float* db, float* col_ws /* 64 x COLSUM_MAX_N floats */, hipStream_t st);
 
 // ---------------------------------------------------------------- heads.hip: policy / value heads, action sampling
 void launch_heads_fwd(const float* feat, const float* Wh, const float* bh, float* hout, int n, int O /* <= 16 outputs, H == 256 */, hipStream_t st);
@@ -266,6 +268,9 @@ void launch_adam(float* p, float* g, float* m, float* v, long long n, const doub
                  float beta1, float beta2, float eps, float step_size_scale, float bc2_sqrt, float* gnorm_out,
                  hipStream_t st);
 void launch_sumsq_partials(const float* g, long long n, double* part /* 128 doubles */, hipStream_t st);
+// sae.hip's Adam with torch's own constants (w1 / w2 = (float)(1.0 - beta)); sumsq: the 128 partial sums of launch_sumsq_partials
+void launch_sae_adam(float* p, float* g, float* m, float* v, long long n, const double* sumsq, float max_norm, float w1, float beta2, float w2,
+                     float eps, float step_size, float bc2_sqrt, float* gnorm_out, hipStream_t st);
 
 // ---------------------------------------------------------------- gru_cell.hip: the GRU cell of a rollout step
 void launch_mask_rows(const float* h, const float* done, float* out, int n, int H, hipStream_t st);   // out = h * (1 - done[row])

@@ -245,7 +245,9 @@ int mi_create(const mi_config* cfg, mi_ctx** out) {
     ARG(cfg->precision == 0 || cfg->precision == 1, "precision must be 0 (fp32) or 1 (bf16 activations)");
     ARG(cfg->value_from_logits == 0 || cfg->value_from_logits == 1, "value_from_logits must be 0 (fc_value head) or 1 (logsumexp of the logits)");
     if (cfg->arch == MI_ARCH_MLP) ARG(cfg->obs_dim >= 1 && cfg->mlp_depth >= 2 && cfg->mlp_width >= 1 && cfg->out_dim >= 1, "mlp dims");
-    if (cfg->arch == MI_ARCH_IMPALA)          // out_dim 0: unset by a C caller, the reference's default 256
+    // every linear layer's bias gradient is a column sum over its output width (linear_wgrad -> launch_colsum_acc, COLSUM_MAX_N columns)
+    if (cfg->arch == MI_ARCH_MLP) ARG(cfg->mlp_width <= COLSUM_MAX_N && cfg->out_dim <= COLSUM_MAX_N, "mlp_width and the MLP's out_dim must be at most 4096 (the bias gradients' column-sum workspace)");
+    if (cfg->arch == MI_ARCH_IMPALA)         // out_dim 0: unset by a C caller, the reference's default 256
         ARG(cfg->out_dim == 0 || (cfg->out_dim >= 64 && cfg->out_dim <= 512 && cfg->out_dim % 64 == 0),
             "impala out_dim (output_dim) must be a multiple of 64 in [64, 512]");
     int ndev = 0;
@@ -325,7 +327,7 @@ static int ctx_build(mi_ctx* c) {
     HIPC(m.dev(&c->d_lp, (size_t)NB * c->A));
     const size_t gws = (size_t)8 << 20;
     HIPC(m.dev(&c->gemm_ws, gws)); c->gemm_ws_floats = gws;
-    HIPC(m.dev(&c->col_ws, (size_t)64 * 4096));
+    HIPC(m.dev(&c->col_ws, (size_t)64 * COLSUM_MAX_N));
     HIPC(m.dev(&c->fs_val, 4));
     {
         float h[256];
@@ -1909,9 +1911,7 @@ int mi_ipl_read_pred(mi_ctx* c, float* pred_out, float* rew_out, int32_t n) {
 
 int mi_optimizer_step(mi_ctx* c, float lr, float max_norm, int32_t step, float* gnorm_out) {
     ARG(c, "null"); JOIN(c); ARG(step >= 1, "adam_step is 1-based");
-    const double b1 = 0.9, b2 = 0.999;
-    const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
-    const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+    const AdamScalars a = adam_scalars(lr, step);
     if (c->ar_inflight) { HIPC(hipStreamWaitEvent(c->stream, c->ev_ar_done, 0)); c->ar_inflight = false; }
     c->ar_issued = false; c->ar_armed = false;
     if (c->gru_train) {
@@ -1920,15 +1920,15 @@ int mi_optimizer_step(mi_ctx* c, float lr, float max_norm, int32_t step, float* 
         const GruTensors g = gru_tensors(c);
         launch_sumsq_partials(c->grads, c->n_params, c->gru_sumsq, c->stream);
         launch_sumsq_partials(c->gru_g, (long long)gru_count(c), c->gru_sumsq + 128, c->stream);
-        launch_adam(c->params, c->grads, c->adam_m, c->adam_v, c->n_params, c->gru_sumsq, 256, max_norm, lr, (float)b1, (float)b2, 1e-5f,
-                    step_size, bc2_sqrt, c->gnorm, c->stream);
+        launch_adam(c->params, c->grads, c->adam_m, c->adam_v, c->n_params, c->gru_sumsq, 256, max_norm, lr, a.beta1, a.beta2, a.eps,
+                    a.step_size, a.bc2_sqrt, c->gnorm, c->stream);
         for (int k = 0; k < 4; ++k)
-            launch_adam(g.t[k].p, c->gru_g + g.t[k].off, c->gru_m + g.t[k].off, c->gru_v + g.t[k].off, (long long)g.t[k].len, c->gru_sumsq, 256, max_norm, lr, (float)b1,
-                        (float)b2, 1e-5f, step_size, bc2_sqrt, nullptr, c->stream);
+            launch_adam(g.t[k].p, c->gru_g + g.t[k].off, c->gru_m + g.t[k].off, c->gru_v + g.t[k].off, (long long)g.t[k].len, c->gru_sumsq, 256, max_norm, lr, a.beta1,
+                        a.beta2, a.eps, a.step_size, a.bc2_sqrt, nullptr, c->stream);
     } else {
     launch_sumsq_partials(c->grads, c->n_params, c->sumsq + 2, c->stream);          // 128 partial sums; the Adam kernel's waves add them up themselves
-    launch_adam(c->params, c->grads, c->adam_m, c->adam_v, c->n_params, c->sumsq + 2, 128, max_norm, lr, (float)b1, (float)b2, 1e-5f,
-                step_size, bc2_sqrt, c->gnorm, c->stream);
+    launch_adam(c->params, c->grads, c->adam_m, c->adam_v, c->n_params, c->sumsq + 2, 128, max_norm, lr, a.beta1, a.beta2, a.eps,
+                a.step_size, a.bc2_sqrt, c->gnorm, c->stream);
     }
     c->fc_packed_valid = false;
     HIPC(hipGetLastError()); NETCHK(c);

@@ -203,3 +203,12 @@ MI_INTERNAL void net_forward(mi_ctx* c, const InputSrc& src, int n, const FwdOpt
 MI_INTERNAL void linear_fwd(mi_ctx* c, const float* X, int relu_x, const float* W, const float* b, float* Y, int n, int in, int out, int relu_out, int x_bf16 = 0);
 MI_INTERNAL void linear_dgrad(mi_ctx* c, const float* dY, const float* W, const float* mask, float* dX, int n, int in, int out, int x_bf16 = 0);
 MI_INTERNAL void linear_wgrad(mi_ctx* c, const float* dY, const float* X, int relu_x, float* gW, float* gb, int n, int in, int out, int x_bf16 = 0);
+
+// The host scalars of one Adam step (lr, 1-based step): the one place they are computed, for mi_optimizer_step, mi_sae_optimizer_step and
+// the op-level hook mi_op_adam alike.  beta1 / beta2 go to adam_kernel (which forms 1 - beta in fp32), w1 / w2 to sae_adam_kernel.
+struct AdamScalars { float beta1, beta2, w1, w2, eps, step_size, bc2_sqrt; };
+static inline AdamScalars adam_scalars(float lr, int step) {
+    const double b1 = 0.9, b2 = 0.999;
+    const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
+    return AdamScalars{(float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), 1e-5f, (float)((double)lr / bc1), (float)sqrt(bc2)};
+}

@@ -578,6 +578,125 @@ int mi_op_fc_bf16(mi_ctx* c, int32_t mode, int32_t n, int32_t D, const float* x,
     return 0;
 }
 
+// The fixed-order sums of reduce.hip on caller data through the production launchers; independent of the context's sizes.  Every
+// accumulation target is an OpMem::out buffer that starts from the caller's values, so an element written past its end trips a band.
+//   mode 0: launch_reduce_slabs(src [a = nslab][b = slab_len], dst_w [n_w], dst_b [n_b] or null with n_b = 0)
+//   mode 1: launch_reduce_all_slabs over n_desc layers, desc = n_desc x {src_off, w_off, b_off, nslab, slab_len, n_w} (SlabDesc's fields as
+//           int64), src = the slab workspace of src_len floats, dst_w = one flat gradient vector of n_w floats
+//   mode 2: launch_colsum_acc(src = dY [a = M][ld], N = b, dst_w = db [N]) with a workspace of exactly the engine's 64 x 4096 floats,
+//           poisoned; the launcher refuses N > 4096 and then nothing is launched
+int mi_op_reduce(mi_ctx* c, int32_t mode, const float* src, int64_t src_len, int32_t a, int32_t b, int32_t ld, const int64_t* desc, int32_t n_desc,
+                 float* dst_w, int64_t n_w, float* dst_b, int32_t n_b) {
+    ARG(c && src && dst_w, "null"); JOIN(c);
+    ARG(mode >= 0 && mode <= 2, "mode");
+    ARG(src_len >= 1 && src_len <= ((int64_t)1 << 28) && n_w >= 1 && n_w <= ((int64_t)1 << 28), "src_len and n_w must be in [1, 2^28]");
+    const std::string hook = "mi_op_reduce mode " + std::to_string(mode);
+    OpMem m(hook.c_str(), c->stream);
+    float *dsrc = nullptr, *dw = nullptr, *db = nullptr;
+    if (mode == 0) {
+        ARG(a >= 1 && b >= 1 && (int64_t)a * b == src_len, "mode 0: src is [nslab][slab_len]");
+        ARG(n_b >= 0 && n_w + n_b <= b && (n_b == 0) == (dst_b == nullptr), "mode 0: n_w + n_b <= slab_len; dst_b null exactly when n_b == 0");
+    } else if (mode == 1) {
+        ARG(desc && n_desc >= 1 && n_desc <= 64, "mode 1: 1 to 64 layers");
+        for (int k = 0; k < n_desc; ++k) {
+            const int64_t* d = desc + 6 * k;
+            ARG(d[3] >= 1 && d[3] <= (1 << 20) && d[4] >= 4 && d[4] <= (1 << 24) && d[5] >= 0 && d[5] <= d[4], "mode 1: nslab / slab_len / n_w");
+            ARG(!(d[0] & 3) && !(d[1] & 3) && !(d[2] & 3) && !(d[4] & 3) && !(d[5] & 3), "mode 1: offsets, slab_len and n_w must be multiples of 4");
+            ARG(d[0] >= 0 && d[0] + d[3] * d[4] <= src_len, "mode 1: a layer's slabs end past src");
+            ARG(d[1] >= 0 && d[1] + d[5] <= n_w && d[2] >= 0 && d[2] + (d[4] - d[5]) <= n_w, "mode 1: a layer's gradients end past the flat vector");
+        }
+    } else {
+        ARG(a >= 1 && b >= 1 && ld >= b && (int64_t)a * ld == src_len && n_w == b, "mode 2: src is [M][ld] with ld >= N, dst_w is [N]");
+    }
+    if (int r = upload(m, src, (size_t)src_len * 4, (void**)&dsrc)) return r;
+    HIPC(m.out(&dw, (size_t)n_w * 4, mode == 1 ? "the flat gradient vector" : mode == 0 ? "dst_w" : "db"));
+    if (dst_b) HIPC(m.out(&db, (size_t)n_b * 4, "dst_b"));
+    HIPC(hipStreamSynchronize(c->stream));          // (the fills run on the context's stream, the copies on the null stream)
+    HIPC(hipMemcpy(dw, dst_w, (size_t)n_w * 4, hipMemcpyHostToDevice));
+    if (dst_b) HIPC(hipMemcpy(db, dst_b, (size_t)n_b * 4, hipMemcpyHostToDevice));
+    if (mode == 0) {
+        launch_reduce_slabs(dsrc, a, b, dw, (int)n_w, db, n_b, c->stream);
+    } else if (mode == 1) {
+        std::vector<SlabDesc> h(n_desc);
+        int max_len = 0;
+        for (int k = 0; k < n_desc; ++k) {
+            const int64_t* d = desc + 6 * k;
+            h[k] = SlabDesc{(long long)d[0], (long long)d[1], (long long)d[2], (int)d[3], (int)d[4], (int)d[5]};
+            max_len = std::max(max_len, (int)d[4]);
+        }
+        SlabDesc* dd = nullptr;
+        if (int r = upload(m, h.data(), sizeof(SlabDesc) * n_desc, (void**)&dd)) return r;
+        launch_reduce_all_slabs(dsrc, dw, dd, n_desc, max_len, c->stream);
+    } else {
+        float* col_ws = nullptr;
+        HIPC(m.out(&col_ws, (size_t)64 * COLSUM_MAX_N * 4, "the column-sum workspace"));
+        launch_colsum_acc(dsrc, a, b, ld, dw, col_ws, c->stream);
+    }
+    if (int r = op_finish(c, m)) return r;
+    HIPC(hipMemcpy(dst_w, dw, (size_t)n_w * 4, hipMemcpyDeviceToHost));
+    if (dst_b) HIPC(hipMemcpy(dst_b, db, (size_t)n_b * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The optimizer tail on caller vectors, as mi_optimizer_step / mi_sae_optimizer_step launch it: the partial sums of squares, then Adam
+// with the host scalars of adam_scalars.  p, g, m, v [n] are in / out; *gnorm_out = the unclipped norm.
+//   variant 0: one vector, 128 partial sums (the plain PPO path)
+//   variant 1: a second vector p2, g2, m2, v2 [n2] shares the norm -- 256 partial sums -- and takes Adam in four pieces
+//              [off[k], off[k + 1]) with 0 = off[0] < .. < off[4] = n2: the gru_train branch of mi_optimizer_step
+//   variant 2: sae_adam_kernel (torch's own constants) on one vector
+int mi_op_adam(mi_ctx* c, int32_t variant, int64_t n, float* p, float* g, float* mm, float* v, int64_t n2, float* p2, float* g2, float* m2,
+               float* v2, const int64_t* off5, float lr, float max_norm, int32_t step, float* gnorm_out) {
+    ARG(c && p && g && mm && v && gnorm_out, "null"); JOIN(c);
+    ARG(variant >= 0 && variant <= 2, "variant");
+    ARG(n >= 1 && n <= ((int64_t)1 << 28) && step >= 1, "n must be in [1, 2^28], step is 1-based");
+    const bool two = variant == 1;
+    if (two) {
+        ARG(p2 && g2 && m2 && v2 && off5 && n2 >= 4 && n2 <= ((int64_t)1 << 28), "variant 1: the second vector (n2 in [4, 2^28]) and its five offsets");
+        ARG(off5[0] == 0 && off5[4] == n2 && off5[0] < off5[1] && off5[1] < off5[2] && off5[2] < off5[3] && off5[3] < off5[4], "variant 1: 0 = off[0] < .. < off[4] = n2");
+    }
+    const std::string hook = "mi_op_adam variant " + std::to_string(variant);
+    OpMem m(hook.c_str(), c->stream);
+    static const char* names[8] = {"p", "g", "m", "v", "p2", "g2", "m2", "v2"};
+    float* host[8] = {p, g, mm, v, p2, g2, m2, v2};
+    float* d[8] = {};
+    const int nv = two ? 8 : 4;
+    for (int k = 0; k < nv; ++k) HIPC(m.out(&d[k], (size_t)(k < 4 ? n : n2) * 4, names[k]));
+    double* part = nullptr; float* gn = nullptr;
+    HIPC(m.out(&part, (size_t)(two ? 256 : 128) * 8, "the partial sums of squares")); HIPC(m.out(&gn, 4, "the norm"));
+    HIPC(hipStreamSynchronize(c->stream));          // (the fills run on the context's stream, the copies on the null stream)
+    for (int k = 0; k < nv; ++k) HIPC(hipMemcpy(d[k], host[k], (size_t)(k < 4 ? n : n2) * 4, hipMemcpyHostToDevice));
+    const AdamScalars a = adam_scalars(lr, step);
+    launch_sumsq_partials(d[1], n, part, c->stream);
+    if (variant == 2) {
+        launch_sae_adam(d[0], d[1], d[2], d[3], n, part, max_norm, a.w1, a.beta2, a.w2, a.eps, a.step_size, a.bc2_sqrt, gn, c->stream);
+    } else if (!two) {
+        launch_adam(d[0], d[1], d[2], d[3], n, part, 128, max_norm, lr, a.beta1, a.beta2, a.eps, a.step_size, a.bc2_sqrt, gn, c->stream);
+    } else {
+        launch_sumsq_partials(d[5], n2, part + 128, c->stream);
+        launch_adam(d[0], d[1], d[2], d[3], n, part, 256, max_norm, lr, a.beta1, a.beta2, a.eps, a.step_size, a.bc2_sqrt, gn, c->stream);
+        for (int k = 0; k < 4; ++k)
+            launch_adam(d[4] + off5[k], d[5] + off5[k], d[6] + off5[k], d[7] + off5[k], (long long)(off5[k + 1] - off5[k]), part, 256, max_norm, lr, a.beta1,
+                        a.beta2, a.eps, a.step_size, a.bc2_sqrt, nullptr, c->stream);
+    }
+    if (int r = op_finish(c, m)) return r;
+    for (int k = 0; k < nv; ++k) HIPC(hipMemcpy(host[k], d[k], (size_t)(k < 4 ? n : n2) * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(gnorm_out, gn, 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// launch_advnorm_merge on R caller triples {count, mean, M2} -> the merged triple
+int mi_op_adv_merge(mi_ctx* c, const double* all, int32_t R, double* stats3_out) {
+    ARG(c && all && stats3_out, "null"); JOIN(c); ARG(R >= 1 && R <= 4096, "R must be in [1, 4096]");
+    OpMem m("mi_op_adv_merge", c->stream);
+    double *dall = nullptr, *ds = nullptr;
+    if (int r = upload(m, all, (size_t)R * 24, (void**)&dall)) return r;
+    HIPC(m.out(&ds, 24, "the merged statistics"));
+    launch_advnorm_merge(dall, R, ds, c->stream);
+    if (int r = op_finish(c, m)) return r;
+    HIPC(hipMemcpy(stats3_out, ds, 24, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // The IPL kernels alone (ipl.hip) on caller arrays: what mi_ipl_minibatch launches between its network passes
 int mi_op_ipl_loss(mi_ctx* c, int32_t n, int32_t A, const float* hout, const float* nv_raw, const int32_t* act, const float* rew,
                    const float* done, const mi_ipl_hparams* hp, float* rec8_out, float* dY_out, float* gnext_out, float* pred_out) {

@@ -62,19 +62,33 @@ __global__ void advnorm_apply_kernel(float* adv, int n, const double* stats3) {
     const float sd = (float)sqrt(stats3[2] / (stats3[0] - 1.0));
     adv[k] = (adv[k] - mean) / (sd + 1e-8f);
 }
-// Chan et al. merge of R ranks' {count, mean, M2} triples (fp64) into stats3 -- the device side of mi355/dist.py::merge_adv_stats
+// Merge of R ranks' {count, mean, M2} triples (fp64) into stats3 -- the device side of mi355/dist.py::merge_adv_stats, same operations
+// in the same order (no contraction), so the two agree bit for bit.  Two passes around a pivot, the first non-empty rank's mean:
+//   mean = pivot + shift, shift = sum_r c_r (mu_r - pivot) / n;   M2 = sum_r s_r + c_r ((mu_r - pivot) - shift)^2
+// The differences of nearby means are exact, and an error of the merged mean reaches M2 only in second order (sum_r c_r (mu_r - mean)
+// = 0), where the pairwise recurrence mean += d c / tot rounds a running mean of full magnitude at every rank and carries that into
+// every later d: 2.3e-14 of an M2 of 0.1 for eight ranks at mean 1000, sd 0.01, against 3e-15 here (tests/test_gpu_optim_ops.py).
 __global__ void advnorm_merge_kernel(const double* all, int R, double* stats3) {
+#pragma clang fp contract(off)
     if (threadIdx.x || blockIdx.x) return;
-    double n = 0.0, mean = 0.0, m2 = 0.0;
+    double n = 0.0, pivot = 0.0, acc = 0.0;
+    bool have = false;
+    for (int r = 0; r < R; ++r) {
+        const double c = all[3 * r], mu = all[3 * r + 1];
+        if (c == 0.0) continue;
+        if (!have) { pivot = mu; have = true; }
+        n = n + c;
+        acc = acc + c * (mu - pivot);
+    }
+    const double shift = have ? acc / n : 0.0;
+    double m2 = 0.0;
     for (int r = 0; r < R; ++r) {
         const double c = all[3 * r], mu = all[3 * r + 1], s = all[3 * r + 2];
         if (c == 0.0) continue;
-        const double tot = n + c, d = mu - mean;
-        mean = mean + d * c / tot;
-        m2 = m2 + s + d * d * n * c / tot;
-        n = tot;
+        const double d = (mu - pivot) - shift;
+        m2 = (m2 + s) + (c * d) * d;
     }
-    stats3[0] = n; stats3[1] = mean; stats3[2] = m2;
+    stats3[0] = n; stats3[1] = pivot + shift; stats3[2] = m2;
 }
 void launch_advnorm_merge(const double* all, int R, double* stats3, hipStream_t st) {
     hipLaunchKernelGGL(advnorm_merge_kernel, dim3(1), dim3(64), 0, st, all, R, stats3);

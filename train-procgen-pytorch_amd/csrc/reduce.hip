@@ -80,7 +80,9 @@ __global__ void colsum_partial_kernel(const float* dY, int M, int N, int ld, flo
 }
 void launch_colsum_acc(const float* dY, int M, int N, int ld, float* db, float* col_ws, hipStream_t st) {
     if (M <= 0) return;
-    const int gy = (M >= 4096 && N <= 1024) ? 64 : 16;         // workspace: 64 x 4096 floats (engine.hip)
+    // the partial sums are gy*4 rows of N floats: 64 x N past the workspace's end from N = 4097 on
+    if (N > COLSUM_MAX_N) { mi_launch_fail("column sum: N must be at most 4096 (the 64 x 4096 partial-sum workspace)"); return; }
+    const int gy = (M >= 4096 && N <= 1024) ? 64 : 16;         // workspace: 64 x COLSUM_MAX_N floats (engine.hip)
     hipLaunchKernelGGL(colsum_partial_kernel, dim3((N + 63) / 64, gy), dim3(256), 0, st, dY, M, N, ld, col_ws);
     launch_reduce_slabs(col_ws, gy * 4, N, db, N, nullptr, 0, st);
 }

@@ -192,6 +192,11 @@ __global__ __launch_bounds__(256) void sae_adam_kernel(float* p, float* g, float
     m[k] = mk; v[k] = vk;
     g[k] = 0.f;                                          // optimizer.zero_grad()
 }
+void launch_sae_adam(float* p, float* g, float* m, float* v, long long n, const double* sumsq, float max_norm, float w1, float beta2, float w2,
+                     float eps, float step_size, float bc2_sqrt, float* gnorm_out, hipStream_t st) {
+    hipLaunchKernelGGL(sae_adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, g, m, v, n, sumsq, max_norm, w1, beta2, w2, eps,
+                       step_size, bc2_sqrt, gnorm_out);
+}
 
 // ------------------------------------------------------------------------------------------ host helpers
 static void sae_gemm(mi_ctx* c, const float* A, long long sam, const float* B, long long sbk, long long sbn, float* C, int M, int N, int K,
@@ -471,12 +476,11 @@ int mi_sae_probe_minibatch(mi_ctx* c, const int64_t* idx, int32_t n, float* log_
 // mi_optimizer_step's partial-sum kernel for the norm, sae_adam_kernel for the step
 int mi_sae_optimizer_step(mi_ctx* c, int32_t which, float lr, float max_norm, int32_t step, float* gnorm_out) {
     SAE_CTX(c, which); JOIN(c); ARG(step >= 1, "adam_step is 1-based");
-    const double b1 = 0.9, b2 = 0.999;
-    const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
+    const AdamScalars a = adam_scalars(lr, step);
     const long long n = which ? s->n_probe : s->n_sae;
     launch_sumsq_partials(s->g[which], n, s->sumsq, c->stream);
-    hipLaunchKernelGGL(sae_adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, s->p[which], s->g[which], s->m[which], s->v[which], n,
-                       (const double*)s->sumsq, max_norm, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), 1e-5f, (float)((double)lr / bc1), (float)sqrt(bc2), s->gnorm);
+    launch_sae_adam(s->p[which], s->g[which], s->m[which], s->v[which], n, s->sumsq, max_norm, a.w1, a.beta2, a.w2, a.eps, a.step_size, a.bc2_sqrt,
+                    s->gnorm, c->stream);
     HIPC(hipGetLastError()); NETCHK(c);
     if (gnorm_out) {
         HIPC(hipMemcpyAsync(s->h_log + 4, s->gnorm, 4, hipMemcpyDeviceToHost, c->stream));

@@ -29,18 +29,23 @@ def shard_indices(chunk, n_envs_global, rank, world, with_positions=False):
 
 
 def merge_adv_stats(stats_list):
-    """Chan et al. parallel merge of per-rank {count, mean, M2} (fp64) -> global triple, from which
-    mean and the unbiased std of common/storage.py:79 follow."""
-    n, mean, m2 = 0.0, 0.0, 0.0
-    for c, mu, s in stats_list:
-        if c == 0:
-            continue
-        tot = n + c
-        d = mu - mean
-        mean = mean + d * c / tot
-        m2 = m2 + s + d * d * n * c / tot
-        n = tot
-    return np.array([n, mean, m2], dtype=np.float64)
+    """Merge of per-rank {count, mean, M2} (fp64) -> global triple, from which mean and the unbiased std of
+    common/storage.py:79 follow.  Two passes around a pivot (the first non-empty rank's mean): mean = pivot + shift with
+    shift = sum c (mu - pivot) / n, M2 = sum s + c ((mu - pivot) - shift)^2 -- the operations and order of
+    advnorm_merge_kernel (csrc/estimates.hip, which says why not the pairwise recurrence), so the two agree bit for bit."""
+    live = [(float(c), float(mu), float(s)) for c, mu, s in stats_list if c != 0]
+    if not live:
+        return np.zeros(3, dtype=np.float64)
+    pivot, n, acc = live[0][1], 0.0, 0.0
+    for c, mu, _ in live:
+        n = n + c
+        acc = acc + c * (mu - pivot)
+    shift = acc / n
+    m2 = 0.0
+    for c, mu, s in live:
+        d = (mu - pivot) - shift
+        m2 = (m2 + s) + (c * d) * d
+    return np.array([n, pivot + shift, m2], dtype=np.float64)
 
 
 def update_plan(chunks, rank, world, n_envs_global, grad_accumulation_steps, merge, stats_per_minibatch, max_batch, max_segments=16,

@@ -60,7 +60,7 @@ EXPORTS = ("mi_last_error mi_create mi_destroy mi_sync mi_host_alloc mi_host_fre
            "mi_get_params mi_copy_params mi_get_grads mi_set_adam_state mi_get_adam_state mi_put_obs mi_get_obs mi_put_step "
            "mi_put_policy_outputs mi_read_field mi_write_field mi_policy_step mi_rollout_step mi_rollout_groups mi_rollout_lane_info mi_rollout_submit mi_rollout_wait mi_predict_staged mi_value_saliency mi_commit_staged mi_set_gru mi_rec_state mi_get_hidden mi_rec_begin mi_get_hidden_ring mi_forward_rec mi_forward mi_compute_estimates "
            "mi_adv_stats mi_adv_apply mi_minibatch mi_minibatch_multi mi_optimizer_step mi_loss_log_read mi_device_ptr "
-           "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_op_fc_bf16 mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_gru_step mi_debug_step_latency mi_debug_lane_probe mi_debug_live_resources "
+           "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_op_fc_bf16 mi_op_reduce mi_op_adam mi_op_adv_merge mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_gru_step mi_debug_step_latency mi_debug_lane_probe mi_debug_live_resources "
            "mi_gru_train mi_minibatch_rec mi_get_gru mi_get_gru_grads mi_get_gru_adam_state mi_set_gru_adam_state mi_debug_gru_seq "
            "mi_sae_create mi_sae_destroy mi_sae_param_count mi_sae_set_params mi_sae_get_params mi_sae_get_grads mi_sae_set_adam_state mi_sae_get_adam_state mi_sae_put_ring "
            "mi_sae_get_hidden mi_sae_get_logits mi_sae_step mi_sae_minibatch mi_sae_probe_minibatch mi_sae_optimizer_step mi_sae_debug_forward "
@@ -834,6 +834,54 @@ class Engine:
         self._chk(self.lib.mi_op_fc_bf16(self._ctx, C.c_int32(mode), C.c_int32(n), C.c_int32(D), _fp(x), _fp(W), _fp(b), _fp(dy), _fp(out),
                                          _fp(out_b)))
         return (out, out_b) if mode == 3 else out
+
+    def _op_reduce(self, mode, src, a, b, ld, desc, dst_w, dst_b):
+        src, w = _f32(src).reshape(-1), np.array(dst_w, dtype=np.float32, order="C").reshape(-1)
+        bb = None if dst_b is None else np.array(dst_b, dtype=np.float32, order="C").reshape(-1)
+        desc = None if desc is None else np.ascontiguousarray(desc, dtype=np.int64).reshape(-1, 6)
+        self._chk(self.lib.mi_op_reduce(self._ctx, C.c_int32(mode), _fp(src), C.c_int64(src.size), C.c_int32(a), C.c_int32(b), C.c_int32(ld),
+                                        _fp(desc), C.c_int32(0 if desc is None else desc.shape[0]), _fp(w), C.c_int64(w.size), _fp(bb),
+                                        C.c_int32(0 if bb is None else bb.size)))
+        return w, bb
+
+    def op_reduce_slabs(self, partial, dst_w, dst_b=None):
+        """launch_reduce_slabs on partial (nslab, slab_len) (mi_op_reduce mode 0) -> (dst_w + the sums of the first len(dst_w) elements,
+        dst_b + those of the next len(dst_b), or None); elements past both are dropped."""
+        partial = _f32(partial)
+        return self._op_reduce(0, partial, partial.shape[0], partial.shape[1], 0, None, dst_w, dst_b)
+
+    def op_reduce_all_slabs(self, ws, desc, grads):
+        """launch_reduce_all_slabs (mi_op_reduce mode 1): desc rows {src_off, w_off, b_off, nslab, slab_len, n_w}, ws the flat slab
+        workspace, grads the flat gradient vector -> grads + every layer's sums."""
+        return self._op_reduce(1, ws, 0, 0, 0, desc, grads, None)[0]
+
+    def op_colsum(self, dY, N, db):
+        """launch_colsum_acc on dY (M, ld) (mi_op_reduce mode 2) -> db + the column sums of the first N columns."""
+        dY = _f32(dY)
+        return self._op_reduce(2, dY, dY.shape[0], N, dY.shape[1], None, db, None)[0]
+
+    def op_adam(self, variant, p, g, m, v, lr, max_norm, step, second=None, offsets=None):
+        """The optimizer tail on caller vectors (mi_op_adam) -> (p', g', m', v', norm); variant 0 the PPO path, 2 the SAE agent's kernel,
+        1 with second = (p2, g2, m2, v2) under the same norm, stepped in the four pieces offsets[k]:offsets[k + 1] ->
+        (p', g', m', v', norm, (p2', g2', m2', v2'))."""
+        a = [np.array(x, dtype=np.float32, order="C").reshape(-1) for x in (p, g, m, v)]
+        s = [None] * 4 if second is None else [np.array(x, dtype=np.float32, order="C").reshape(-1) for x in second]
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        if any(x.size != a[0].size for x in a) or (second is not None and (any(x.size != s[0].size for x in s) or off is None or off.size != 5)):
+            raise EngineError("op_adam: p, g, m, v must have one length; the second vector needs five offsets")
+        gn = C.c_float(0)
+        self._chk(self.lib.mi_op_adam(self._ctx, C.c_int32(variant), C.c_int64(a[0].size), *[_fp(x) for x in a],
+                                      C.c_int64(0 if second is None else s[0].size), *[_fp(x) for x in s], _fp(off), C.c_float(lr),
+                                      C.c_float(max_norm), C.c_int32(step), C.byref(gn)))
+        norm = np.float32(gn.value)
+        return (*a, norm) if second is None else (*a, norm, tuple(s))
+
+    def op_adv_merge(self, stats_list):
+        """launch_advnorm_merge on R triples {count, mean, M2} (mi_op_adv_merge) -> the merged triple (float64)."""
+        a = np.ascontiguousarray(stats_list, dtype=np.float64).reshape(-1, 3)
+        out = np.empty(3, np.float64)
+        self._chk(self.lib.mi_op_adv_merge(self._ctx, _fp(a), C.c_int32(a.shape[0]), _fp(out)))
+        return out
 
     def debug_read(self, which, n):
         """Activation tensor `which` (see include/mi355ppo.h mi_debug_read) of the last minibatch pass, first n samples, fp32 NHWC."""
