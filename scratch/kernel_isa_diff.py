@@ -1,6 +1,6 @@
 """Kernel-by-kernel comparison of the device assembly of two source states, host only (no GPU needed).
 
-    python scratch/kernel_isa_diff.py REV [expected-removal ...]
+    python scratch/kernel_isa_diff.py REV [expected-removal ...] [--added expected-addition ...] [--pair OLD=NEW ...]
 
 Compiles every csrc/*.hip of the working tree and of git revision REV to gfx950 assembly (isa_mix.compile_to_asm: the flags of that
 state's csrc/Makefile, plus the extra flags of a file's own rule in it, e.g. conv.o's; REV's sources and headers are unpacked into a
@@ -9,8 +9,14 @@ temporary directory).  Each listing is cut into kernels by mangled name -- the b
 .Ltmp<n>, .Lfunc_end<f>, .LJTI<f>_<n>) is normalised, so a kernel that merely moved to another file compares equal.
 
 Prints one line per kernel: `same`, `differs`, `only in REV` or `only in tree` (with the file(s) that hold it), and exits non-zero
-unless every kernel is `same` or is `only in REV` and matches an expected-removal argument (a substring of the mangled name).  A
-kernel emitted by two files of one state is reported as an error.  It is a plain text comparison: it knows nothing about instructions.
+unless every kernel is `same`, or is `only in REV` and matches an expected-removal argument, or is `only in tree` and matches an
+expected-addition argument (each a substring of the mangled name; with none given, every `only in tree` fails).  A kernel
+emitted by two files of one state is reported as an error.  That is a plain text comparison: it knows nothing about instructions.
+
+`--pair OLD=NEW` (substrings that each name one kernel, OLD in REV and NEW in the tree) compares a rewritten kernel with the one it
+replaces: identical text, or else the instruction count, the mnemonic histogram without the _e32 / _e64 encoding suffix,
+next_free_vgpr, next_free_sgpr and private_segment_fixed_size (which must be 0) of both.  A pair that is neither identical nor equal in
+all of these fails the run.  profiles/device_env_skeleton_isa.txt is the output for the commit that put the device envs on one skeleton.
 
 profiles/misc_split_isa.txt is its output for the commit that split csrc/misc.hip, against that commit's parent.
 """
@@ -60,6 +66,40 @@ def kernels_of(text):
     return out
 
 
+def profile(text):
+    """(instruction count, {mnemonic without _e32 / _e64: count}, {descriptor field: value}) of one normalised kernel text."""
+    body, _, desc = text.partition(".amdhsa_kernel")
+    hist = {}
+    for line in body.split("\n"):
+        w = line.split()
+        if not w or w[0].startswith(".") or w[0].endswith(":"):
+            continue
+        m = re.sub(r"_e(32|64)$", "", w[0])
+        hist[m] = hist.get(m, 0) + 1
+    fields = dict(re.findall(r"\.amdhsa_(next_free_vgpr|next_free_sgpr|private_segment_fixed_size)\s+(\S+)", desc))
+    return sum(hist.values()), hist, fields
+
+
+def compare_pair(spec, old, new):
+    """Prints the comparison of one --pair; -> True if the new kernel meets the bar."""
+    o_sub, _, n_sub = spec.partition("=")
+    o, n = [k for k in old if o_sub in k], [k for k in new if n_sub in k]
+    if len(o) != 1 or len(n) != 1:
+        print("pair %s: names %d kernels in REV and %d in the tree (one each is needed)" % (spec, len(o), len(n)))
+        return False
+    print("pair %s -> %s" % (o[0], n[0]))
+    if old[o[0]][0].replace(o[0], "K") == new[n[0]][0].replace(n[0], "K"):
+        print("    identical text")
+        return True
+    (co, ho, fo), (cn, hn, fn) = profile(old[o[0]][0]), profile(new[n[0]][0])
+    print("    instructions %d -> %d" % (co, cn))
+    delta = ["%s %d -> %d" % (m, ho.get(m, 0), hn.get(m, 0)) for m in sorted(set(ho) | set(hn)) if ho.get(m, 0) != hn.get(m, 0)]
+    print("    mnemonic histogram (without _e32 / _e64): " + ("same, %d mnemonics" % len(ho) if not delta else "DIFFERS: " + "; ".join(delta)))
+    for k in ("next_free_vgpr", "next_free_sgpr", "private_segment_fixed_size"):
+        print("    %s %s -> %s" % (k, fo.get(k), fn.get(k)))
+    return co == cn and not delta and fo == fn and fn.get("private_segment_fixed_size") == "0"
+
+
 def state(csrc, label):
     """{name: (text, [files])} over every .hip of one checkout's csrc/."""
     srcs = sorted(glob.glob(os.path.join(csrc, "*.hip")))
@@ -80,7 +120,13 @@ def state(csrc, label):
 def main():
     if len(sys.argv) < 2 or sys.argv[1].startswith("-"):
         sys.exit(__doc__)
-    rev, expected = sys.argv[1], sys.argv[2:]
+    rev, expected, added, pairs = sys.argv[1], [], [], []
+    into = expected
+    for a in sys.argv[2:]:
+        if a in ("--added", "--pair"):
+            into = added if a == "--added" else pairs
+        else:
+            into.append(a)
     with tempfile.TemporaryDirectory() as tmp:
         tar = subprocess.run(["git", "-C", ROOT, "archive", rev, REL, "include"], stdout=subprocess.PIPE, check=True).stdout
         subprocess.run(["tar", "-x", "-C", tmp], input=tar, check=True)
@@ -98,12 +144,14 @@ def main():
         else:
             verdict, where = "only in tree", new[name][1][0]
         count[verdict] = count.get(verdict, 0) + 1
-        if verdict in ("differs", "only in tree") or (verdict == "only in REV" and not any(e in name for e in expected)):
+        if (verdict == "differs" or (verdict == "only in REV" and not any(e in name for e in expected))
+                or (verdict == "only in tree" and not any(e in name for e in added))):
             bad += 1
         print("%-12s %s  (%s)" % (verdict, name, where))
     for d in dup_old + dup_new:
         print("error: " + d)
     print("# " + ", ".join("%d %s" % (count[k], k) for k in ("same", "differs", "only in REV", "only in tree") if k in count))
+    bad += sum(not compare_pair(p, old, new) for p in pairs)
     sys.exit(1 if bad or dup_old or dup_new else 0)
 
 

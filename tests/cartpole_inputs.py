@@ -8,7 +8,7 @@ from oracle.philox import philox4x32_10
 
 
 def philox_u53(seed, env, episode):
-    """The nine 53-bit uniforms of the start of episode `episode` of env `env` (csrc/cartpole.hip): Philox4x32-10 keyed by the 64-bit
+    """The nine 53-bit uniforms of the start of episode `episode` of env `env` (csrc/env_device.hip): Philox4x32-10 keyed by the 64-bit
     seed, counter {env, episode low word, episode high word, block}, block 0..4; output words {0, 1} and {2, 3} of block b give the
     uniforms of columns 2b and 2b + 1 as ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53 (18 words used, 20 drawn).  env, episode: ints or int
     arrays of one shape -> (n, 9) float64 in [0, 1)."""

@@ -42,7 +42,7 @@ def one_step_case(sparse=True):
 
 
 def philox_u53(seed, env, episode, attempt):
-    """The five 53-bit uniforms of attempt `attempt` at the start of episode `episode` of env `env` (csrc/mountain_car.hip):
+    """The five 53-bit uniforms of attempt `attempt` at the start of episode `episode` of env `env` (csrc/env_device.hip):
     Philox4x32-10 keyed by the 64-bit seed, counter {env, episode low word, episode high word, 3 * attempt + b}, b = 0..2; output words
     {0, 1} and {2, 3} of block b give the uniforms of columns 2b and 2b + 1 as ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53 (10 words used, 12
     drawn).  env, episode, attempt: ints or int arrays of one shape -> (n, 5) float64 in [0, 1)."""

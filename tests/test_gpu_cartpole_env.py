@@ -1,4 +1,4 @@
-"""The device-resident cart-pole (csrc/cartpole.hip, mi_env_* in include/mi355ppo.h, common/env/vec_envs.py DeviceCartPole, train.py
+"""The device-resident cart-pole (csrc/env_device.hip, mi_env_* in include/mi355ppo.h, common/env/vec_envs.py DeviceCartPole, train.py
 --device_env) against CartPoleVec, the project's float64 restatement of the reference env, and against a CPU replay that drives
 CartPoleVec.step with the numpy restatement of the device env's Philox reset stream (tests/cartpole_inputs.py).
 

@@ -1,4 +1,4 @@
-"""The device-resident mountain car (csrc/mountain_car.hip, mi_env_* in include/mi355ppo.h, common/env/vec_envs.py DeviceMountainCar,
+"""The device-resident mountain car (csrc/env_device.hip, mi_env_* in include/mi355ppo.h, common/env/vec_envs.py DeviceMountainCar,
 train.py --device_env) against the reference's own class through the fixture tests/golden/g17_mountain_car.npz, and against a CPU replay
 that drives MountainCarVec.step with the numpy restatement of the device env's Philox reset stream (tests/mountain_car_inputs.py).
 

@@ -12,6 +12,9 @@ common/env/procgen_wrappers.py:45-124.  Rollout collection stays on the host (no
                    learner-side workload of SURVEY 8(d) / bench.py.
 * create_procgen_env -- the real engine if the `procgen` package is importable (it is not in the build image).
 """
+from fnmatch import fnmatchcase
+from typing import Callable, NamedTuple
+
 import numpy as np
 
 
@@ -74,6 +77,21 @@ class StepInfo:
         return (self[i] for i in range(self.n))
 
 
+def _cartpole_setup(self, n_envs, degrees, h_range, min_gravity, max_gravity, min_pole_length, max_pole_length, min_cart_mass, max_cart_mass,
+                    min_pole_mass, max_pole_mass, min_force_mag, max_force_mag, max_steps, seed):
+    """The constructor part that CartPoleVec and DeviceCartPole share: the thresholds (cartpole_pre_vec.py:131-132) and the start ranges
+    per state column (:163-171)."""
+    if n_envs < 2:
+        raise Exception("n_envs must be greater than or equal to 2")
+    self.n_envs = self.num_envs = n_envs
+    self.max_steps, self.seed = max_steps, int(seed)
+    self.theta_threshold, self.x_threshold = degrees * 2 * np.pi / 360, h_range
+    self.low = np.array([-0.05] * 4 + [min_gravity, min_pole_length, min_cart_mass, min_pole_mass, min_force_mag])
+    self.high = np.array([0.05] * 4 + [max_gravity, max_pole_length, max_cart_mass, max_pole_mass, max_force_mag])
+    self.observation_space = _Space(shape=(9,))
+    self.action_space = _Space(n=2)
+
+
 class CartPoleVec:
     """The reference's pre-vectorised cart-pole (discrete_env/cartpole_pre_vec.py:20-205 on discrete_env/pre_vec_env.py:21-125),
     restated in numpy: BASELINE config 1's env.  Observation = the 9-column state (cartpole_pre_vec.py:136-149, 197-208)
@@ -95,16 +113,9 @@ class CartPoleVec:
     def __init__(self, n_envs, degrees=12, h_range=2.4, min_gravity=9.8, max_gravity=10.4, min_pole_length=0.5, max_pole_length=1.0,
                  min_cart_mass=1.0, max_cart_mass=1.5, min_pole_mass=0.1, max_pole_mass=0.2, min_force_mag=10., max_force_mag=10.,
                  max_steps=500, seed=0, **_ignored):
-        if n_envs < 2:
-            raise Exception("n_envs must be greater than or equal to 2")
-        self.n_envs = self.num_envs = n_envs
-        self.max_steps = max_steps
-        self.theta_threshold, self.x_threshold = degrees * 2 * np.pi / 360, h_range
-        self.low = np.array([-0.05] * 4 + [min_gravity, min_pole_length, min_cart_mass, min_pole_mass, min_force_mag])
-        self.high = np.array([0.05] * 4 + [max_gravity, max_pole_length, max_cart_mass, max_pole_mass, max_force_mag])
+        _cartpole_setup(self, n_envs, degrees, h_range, min_gravity, max_gravity, min_pole_length, max_pole_length, min_cart_mass, max_cart_mass,
+                        min_pole_mass, max_pole_mass, min_force_mag, max_force_mag, max_steps, seed)
         self.rng = np.random.default_rng(seed)
-        self.observation_space = _Space(shape=(9,))
-        self.action_space = _Space(n=2)
         self.reward = np.ones(n_envs)
         self.info = StepInfo(n_envs, {"env_reward": self.reward})
         self.state = np.zeros((n_envs, 9))
@@ -144,6 +155,18 @@ class CartPoleVec:
 
     def close(self):
         pass
+
+
+def _create_pre_vec(ranges, host_cls, device_cls, hyperparameters, is_valid, seed, n_envs, device):
+    """create_pre_vec / assign_env_vars (pre_vec_env.py:207-223, helper_pre_vec.py:52-66) behind create_cartpole and create_mountain_car:
+    `ranges` holds [training value, validation value] of every constructor argument; a hyper-parameter `<name>` (training) or `<name>_v`
+    (validation) overrides an entry, and max_steps may come from the hyper-parameters too.  device: build device_cls, not host_cls."""
+    suffix, i = ("_v", -1) if is_valid else ("", 0)
+    kw = {k: hyperparameters.get(k + suffix, v[i]) for k, v in ranges.items()}
+    if "max_steps" in hyperparameters:
+        kw["max_steps"] = hyperparameters["max_steps"]
+    cls = device_cls if device else host_cls
+    return cls(n_envs if n_envs is not None else hyperparameters.get("n_envs", 32), seed=seed, **kw)
 
 
 # create_cartpole (discrete_env/cartpole_pre_vec.py:397-412): [training value, validation value] of every constructor argument
@@ -186,7 +209,7 @@ class _DeviceEnv:
 
 
 class DeviceCartPole(_DeviceEnv):
-    """CartPoleVec with the env on the device (train.py --device_env; csrc/cartpole.hip, mi_env_* in include/mi355ppo.h): state,
+    """CartPoleVec with the env on the device (train.py --device_env; csrc/env_device.hip `CartPole`, mi_env_* in include/mi355ppo.h): state,
     physics, termination, episode resets, reward and done live in HBM next to the policy, so that the agent collects a whole rollout
     with ONE call and no host round trip per step (agents/ppo.py `_collect_device`).  Same constructor arguments, spaces, ranges,
     thresholds (the same fp64 bits) and step arithmetic (fp64, the same operation order) as CartPoleVec.
@@ -204,17 +227,8 @@ class DeviceCartPole(_DeviceEnv):
     def __init__(self, n_envs, degrees=12, h_range=2.4, min_gravity=9.8, max_gravity=10.4, min_pole_length=0.5, max_pole_length=1.0,
                  min_cart_mass=1.0, max_cart_mass=1.5, min_pole_mass=0.1, max_pole_mass=0.2, min_force_mag=10., max_force_mag=10.,
                  max_steps=500, seed=0, **_ignored):
-        if n_envs < 2:
-            raise Exception("n_envs must be greater than or equal to 2")
-        self.n_envs = self.num_envs = n_envs
-        self.max_steps = max_steps
-        self.theta_threshold, self.x_threshold = degrees * 2 * np.pi / 360, h_range
-        self.low = np.array([-0.05] * 4 + [min_gravity, min_pole_length, min_cart_mass, min_pole_mass, min_force_mag])
-        self.high = np.array([0.05] * 4 + [max_gravity, max_pole_length, max_cart_mass, max_pole_mass, max_force_mag])
-        self.seed = int(seed)
-        self.observation_space = _Space(shape=(9,))
-        self.action_space = _Space(n=2)
-        self.engine = None
+        _cartpole_setup(self, n_envs, degrees, h_range, min_gravity, max_gravity, min_pole_length, max_pole_length, min_cart_mass, max_cart_mass,
+                        min_pole_mass, max_pole_mass, min_force_mag, max_force_mag, max_steps, seed)
 
     def _create(self, engine):
         engine.env_cartpole_create(self.low, self.high, self.x_threshold, self.theta_threshold, self.max_steps, self.seed)
@@ -225,12 +239,7 @@ def create_cartpole(hyperparameters, is_valid=False, seed=0, n_envs=None, device
     the validation env draws its physics from the SECOND value of every range (heavier, longer, stronger gravity); a hyper-parameter
     `<name>` (training) or `<name>_v` (validation) overrides a range entry (config.yml `cartpole`: degrees_v 9, h_range_v 1.8);
     max_steps may come from the hyper-parameters too.  device=True: the same arguments build the device-resident DeviceCartPole."""
-    suffix, i = ("_v", -1) if is_valid else ("", 0)
-    kw = {k: hyperparameters.get(k + suffix, v[i]) for k, v in CARTPOLE_PARAM_RANGE.items()}
-    if "max_steps" in hyperparameters:
-        kw["max_steps"] = hyperparameters["max_steps"]
-    cls = DeviceCartPole if device else CartPoleVec
-    return cls(n_envs if n_envs is not None else hyperparameters.get("n_envs", 32), seed=seed, **kw)
+    return _create_pre_vec(CARTPOLE_PARAM_RANGE, CartPoleVec, DeviceCartPole, hyperparameters, is_valid, seed, n_envs, device)
 
 
 def mountain_car_acceptance(min_goal_position, max_goal_position, min_right_boundary, max_right_boundary):
@@ -349,7 +358,7 @@ class MountainCarVec:
 
 
 class DeviceMountainCar(_DeviceEnv):
-    """MountainCarVec with the env on the device (train.py --device_env; csrc/mountain_car.hip, mi_env_* in include/mi355ppo.h): same
+    """MountainCarVec with the env on the device (train.py --device_env; csrc/env_device.hip `MountainCar`, mi_env_* in include/mi355ppo.h): same
     constructor arguments, assertions, spaces, start ranges and scalars (the same fp64 bits) and the same step arithmetic in fp64 in
     the same operation order.  As for DeviceCartPole the stream of the episode starts is the device env's own: the start of episode k of
     env e comes from Philox4x32-10 keyed by `seed`, counter {e, k low word, k high word, 3 * attempt + block}; attempts 0, 1, ... are
@@ -381,12 +390,33 @@ def create_mountain_car(hyperparameters, is_valid=False, seed=0, n_envs=None, de
     range (goal and right wall further out, stronger gravity; about 21 % of its start draws are rejected), a hyper-parameter `<name>`
     (training) or `<name>_v` (validation) overrides a range entry, sparse_rewards among them; max_steps may come from the
     hyper-parameters too.  device=True: the same arguments build the device-resident DeviceMountainCar."""
-    suffix, i = ("_v", -1) if is_valid else ("", 0)
-    kw = {k: hyperparameters.get(k + suffix, v[i]) for k, v in MOUNTAIN_CAR_PARAM_RANGE.items()}
-    if "max_steps" in hyperparameters:
-        kw["max_steps"] = hyperparameters["max_steps"]
-    cls = DeviceMountainCar if device else MountainCarVec
-    return cls(n_envs if n_envs is not None else hyperparameters.get("n_envs", 32), seed=seed, **kw)
+    return _create_pre_vec(MOUNTAIN_CAR_PARAM_RANGE, MountainCarVec, DeviceMountainCar, hyperparameters, is_valid, seed, n_envs, device)
+
+
+class VectorEnv(NamedTuple):
+    """One pre-vectorised env of train.py: `label` is how refusals name it, `create` its create_* function, the two classes its host
+    and device-resident forms."""
+    label: str
+    create: Callable
+    host_cls: type
+    device_cls: type
+
+
+# env-name pattern (fnmatch: `cartpole*` = every name that starts with cartpole) -> the env.  train.py's env construction, its exclusion
+# of these envs from the env groups and its --device_env check all read this table, so a further env is one entry here.
+VECTOR_ENVS = {"cartpole*": VectorEnv("the cart-pole (cartpole*)", create_cartpole, CartPoleVec, DeviceCartPole),
+               "mountain_car": VectorEnv("mountain_car", create_mountain_car, MountainCarVec, DeviceMountainCar)}
+
+
+def vector_env(env_name):
+    """The VECTOR_ENVS entry of an env name, or None (synthetic frames, Procgen)."""
+    return next((v for pattern, v in VECTOR_ENVS.items() if fnmatchcase(env_name, pattern)), None)
+
+
+def device_env_labels():
+    """`the cart-pole (cartpole*) and mountain_car`: the envs that have a device-resident form, for messages."""
+    labels = [v.label for v in VECTOR_ENVS.values()]
+    return ", ".join(labels[:-1]) + " and " + labels[-1]
 
 
 class SyntheticFrames:

@@ -244,25 +244,6 @@ void launch_advnorm_merge(const double* all, int R, double* stats3, hipStream_t 
 void launch_advnorm_stats(const float* adv, int n, double* stats3, hipStream_t st);   // stats3 = {count, mean, M2}
 void launch_advnorm_apply(float* adv, int n, const double* stats3, hipStream_t st);
 
-// ---------------------------------------------------------------- cartpole.hip: the device-resident cart-pole env
-struct CartPoleArgs { double low[9], high[9], x_threshold, theta_threshold; int max_steps; };
-// one env step of all E envs on the actions act[E]: advances state / n_steps / episode, writes the next observation (E x 9), reward and done (E)
-void launch_cartpole_step(const CartPoleArgs& p, double* state, int32_t* n_steps, long long* episode, const int32_t* act,
-                          unsigned long long seed, float* obs_next, float* rew, float* done, int E, hipStream_t st);
-void launch_cartpole_reset(const CartPoleArgs& p, double* state, int32_t* n_steps, long long* episode, unsigned long long seed, float* obs,
-                           int E, hipStream_t st);
-void launch_cartpole_emit_obs(const double* state, float* obs, int E, hipStream_t st);
-
-// ---------------------------------------------------------------- mountain_car.hip: the device-resident mountain-car env
-struct MountainCarArgs { double low[5], high[5], left_boundary, max_speed, force, goal_velocity; int max_steps, sparse_rewards; };
-// as the cart-pole's three, on state E x 5 and actions in {0, 1, 2}
-void launch_mountain_car_step(const MountainCarArgs& p, double* state, int32_t* n_steps, long long* episode, const int32_t* act,
-                              unsigned long long seed, float* obs_next, float* rew, float* done, int E, hipStream_t st);
-void launch_mountain_car_reset(const MountainCarArgs& p, double* state, int32_t* n_steps, long long* episode, unsigned long long seed,
-                               float* obs, int E, hipStream_t st);
-void launch_mountain_car_emit_obs(const double* state, float* obs, int E, hipStream_t st);
-enum EnvKind { ENV_CARTPOLE, ENV_MOUNTAIN_CAR };       // which device-resident env a context holds (mi_env_* dispatch on it)
-
 // ---------------------------------------------------------------- optim.hip: gradient norm + Adam
 void launch_adam(float* p, float* g, float* m, float* v, long long n, const double* sumsq /* the sum, or npart partial sums */, int npart, float max_norm, float lr,
                  float beta1, float beta2, float eps, float step_size_scale, float bc2_sqrt, float* gnorm_out,

@@ -1093,7 +1093,7 @@ static inline bool wait_ticket(const volatile unsigned* flag, unsigned want, Gon
 }
 
 // the launches of a policy step on ring slot t (forward, sample; du: the sampler's uniforms on the device or null), nothing else
-static int issue_policy_step(mi_ctx* c, int32_t t, uint64_t seed, const float* du) {
+int issue_policy_step(mi_ctx* c, int32_t t, uint64_t seed, const float* du) {
     const int E = c->E;
     InputSrc src{obs_ring(c), nullptr, (long long)t * E};
     c->prof.phase = 0;
@@ -1144,120 +1144,6 @@ int mi_rollout_step(mi_ctx* c, int32_t t, const float* rew_prev, const float* do
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------ device-resident envs (cart-pole, mountain car)
-// The serial rollout of the cart-pole / mountain-car sets is T + 1 round trips: policy step -> actions to the host -> the numpy env's
-// step -> the next observations up.  With the env on the device (cartpole.hip, mountain_car.hip) a rollout is ONE call that enqueues
-// T + 1 policy steps and T env steps on the main stream and returns; the only host wait is the caller's read of the reward / done rings
-// afterwards.  A context holds at most one env; its kind, state width and action count are set by the create call and every other
-// mi_env_* entry dispatches on them.
-
-// the env's buffers (the same seven allocations whatever the kind) and the fields every mi_env_* entry reads
-static int env_attach(mi_ctx* c, EnvKind kind, int width, uint64_t seed) {
-    const size_t E = c->E;
-    DevPool& m = c->pool; DevPool::Group all(m);
-    HIPC(m.dev(&c->env_state, E * width)); HIPC(m.dev(&c->env_nsteps, E)); HIPC(m.dev(&c->env_episode, E));
-    HIPC(m.dev(&c->env_s_act, E)); HIPC(m.dev(&c->env_s_obs, E * width)); HIPC(m.dev(&c->env_s_rew, E)); HIPC(m.dev(&c->env_s_done, E));
-    all.keep = true;
-    c->env_kind = kind; c->env_width = width;
-    c->env_seed = seed;
-    c->env_on = true;
-    return 0;
-}
-int mi_env_cartpole_create(mi_ctx* c, const mi_cartpole_params* p, uint64_t seed) {
-    ARG(c && p, "null"); JOIN(c);
-    ARG(c->cfg.arch == MI_ARCH_MLP, "mi_env_cartpole_create: arch must be MI_ARCH_MLP");
-    ARG(c->cfg.obs_dim == 9, "mi_env_cartpole_create: obs_dim must be 9 (the cart-pole's nine state columns)");
-    ARG(c->cfg.n_actions == 2, "mi_env_cartpole_create: n_actions must be 2 (push left / push right)");
-    ARG(c->E >= 2, "mi_env_cartpole_create: n_envs must be at least 2");
-    ARG(!c->gru_on, "mi_env_cartpole_create: a recurrent context (mi_set_gru) is not supported");
-    ARG(!c->env_on, "mi_env_cartpole_create: this context already has an env");
-    ARG(p->max_steps >= 1, "mi_env_cartpole_create: max_steps must be at least 1");
-    for (int j = 0; j < 9; ++j) ARG(p->low[j] <= p->high[j], "mi_env_cartpole_create: low must not exceed high");      // (also refuses NaN)
-    for (int j = 0; j < 9; ++j) { c->env_args.low[j] = p->low[j]; c->env_args.high[j] = p->high[j]; }
-    c->env_args.x_threshold = p->x_threshold; c->env_args.theta_threshold = p->theta_threshold; c->env_args.max_steps = p->max_steps;
-    return env_attach(c, ENV_CARTPOLE, 9, seed);
-}
-int mi_env_mountain_car_create(mi_ctx* c, const mi_mountain_car_params* p, uint64_t seed) {
-    ARG(c && p, "null"); JOIN(c);
-    ARG(c->cfg.arch == MI_ARCH_MLP, "mi_env_mountain_car_create: arch must be MI_ARCH_MLP");
-    ARG(c->cfg.obs_dim == 5, "mi_env_mountain_car_create: obs_dim must be 5 (the mountain car's five state columns)");
-    ARG(c->cfg.n_actions == 3, "mi_env_mountain_car_create: n_actions must be 3 (push left / none / push right)");
-    ARG(c->E >= 2, "mi_env_mountain_car_create: n_envs must be at least 2");
-    ARG(!c->gru_on, "mi_env_mountain_car_create: a recurrent context (mi_set_gru) is not supported");
-    ARG(!c->env_on, "mi_env_mountain_car_create: this context already has an env");
-    ARG(p->max_steps >= 1, "mi_env_mountain_car_create: max_steps must be at least 1");
-    for (int j = 0; j < 5; ++j) ARG(p->low[j] <= p->high[j], "mi_env_mountain_car_create: low must not exceed high");  // (also refuses NaN)
-    ARG(p->max_speed >= 0, "mi_env_mountain_car_create: max_speed must not be negative");
-    // (the start loop is bounded on the device whatever the ranges; the host's acceptance rule makes its fallback a 2^-32 event)
-    for (int j = 0; j < 5; ++j) { c->env_mc.low[j] = p->low[j]; c->env_mc.high[j] = p->high[j]; }
-    c->env_mc.left_boundary = p->left_boundary; c->env_mc.max_speed = p->max_speed; c->env_mc.force = p->force;
-    c->env_mc.goal_velocity = p->goal_velocity; c->env_mc.max_steps = p->max_steps; c->env_mc.sparse_rewards = p->sparse_rewards != 0;
-    return env_attach(c, ENV_MOUNTAIN_CAR, 5, seed);
-}
-#define ENV(c) ARG((c)->env_on, "no env on this context (mi_env_cartpole_create / mi_env_mountain_car_create)")
-// one env step of the context's env: act (E, device) -> obs_next (E x env_width), rew, done (E each)
-static void env_launch_step(mi_ctx* c, const int32_t* act, float* obs_next, float* rew, float* done) {
-    if (c->env_kind == ENV_MOUNTAIN_CAR)
-        launch_mountain_car_step(c->env_mc, c->env_state, c->env_nsteps, c->env_episode, act, c->env_seed, obs_next, rew, done, c->E, c->stream);
-    else
-        launch_cartpole_step(c->env_args, c->env_state, c->env_nsteps, c->env_episode, act, c->env_seed, obs_next, rew, done, c->E, c->stream);
-}
-int mi_env_reset(mi_ctx* c) {
-    ARG(c, "null"); JOIN(c); ENV(c);
-    if (c->env_kind == ENV_MOUNTAIN_CAR)
-        launch_mountain_car_reset(c->env_mc, c->env_state, c->env_nsteps, c->env_episode, c->env_seed, c->obsf, c->E, c->stream);
-    else
-        launch_cartpole_reset(c->env_args, c->env_state, c->env_nsteps, c->env_episode, c->env_seed, c->obsf, c->E, c->stream);
-    HIPC(hipGetLastError());
-    return 0;
-}
-int mi_env_step(mi_ctx* c, const int64_t* act, float* obs_out, float* rew_out, float* done_out) {
-    ARG(c && act, "null"); JOIN(c); ENV(c);
-    const size_t E = c->E, W = c->env_width;
-    if (c->env_kind == ENV_MOUNTAIN_CAR) { for (size_t e = 0; e < E; ++e) ARG(act[e] >= 0 && act[e] <= 2, "mi_env_step: every action must be 0, 1 or 2"); }
-    else for (size_t e = 0; e < E; ++e) ARG(act[e] == 0 || act[e] == 1, "mi_env_step: every action must be 0 or 1");
-    HIPC(hipStreamSynchronize(c->stream));      // (h_i may still be the source / destination of an earlier call's copy)
-    for (size_t e = 0; e < E; ++e) c->h_i[e] = (int32_t)act[e];
-    HIPC(hipMemcpyAsync(c->env_s_act, c->h_i, E * 4, hipMemcpyHostToDevice, c->stream));
-    env_launch_step(c, c->env_s_act, c->env_s_obs, c->env_s_rew, c->env_s_done);
-    HIPC(hipGetLastError());
-    if (obs_out) HIPC(hipMemcpyAsync(obs_out, c->env_s_obs, E * W * 4, hipMemcpyDeviceToHost, c->stream));
-    if (rew_out) HIPC(hipMemcpyAsync(rew_out, c->env_s_rew, E * 4, hipMemcpyDeviceToHost, c->stream));
-    if (done_out) HIPC(hipMemcpyAsync(done_out, c->env_s_done, E * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    return 0;
-}
-int mi_env_rollout(mi_ctx* c, uint64_t seed) {
-    ARG(c, "null"); JOIN(c); ENV(c);
-    ARG(!c->gru_on, "mi_env_rollout: a recurrent context (mi_set_gru) is not supported");
-    const size_t E = c->E, W = c->env_width;
-    if (c->env_kind == ENV_MOUNTAIN_CAR) launch_mountain_car_emit_obs(c->env_state, c->obsf, c->E, c->stream);
-    else launch_cartpole_emit_obs(c->env_state, c->obsf, c->E, c->stream);
-    for (int t = 0; t < c->T; ++t) {
-        if (int r = issue_policy_step(c, t, seed, nullptr)) return r;
-        env_launch_step(c, c->act + t * E, c->obsf + (t + 1) * E * W, c->rew + t * E, c->done + t * E);
-    }
-    return issue_policy_step(c, c->T, seed, nullptr);
-}
-int mi_env_get_state(mi_ctx* c, double* state, int32_t* n_steps, int64_t* episode) {
-    ARG(c, "null"); JOIN(c); ENV(c);
-    const size_t E = c->E, W = c->env_width;
-    if (state) HIPC(hipMemcpyAsync(state, c->env_state, E * W * 8, hipMemcpyDeviceToHost, c->stream));
-    if (n_steps) HIPC(hipMemcpyAsync(n_steps, c->env_nsteps, E * 4, hipMemcpyDeviceToHost, c->stream));
-    if (episode) HIPC(hipMemcpyAsync(episode, c->env_episode, E * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    return 0;
-}
-int mi_env_set_state(mi_ctx* c, const double* state, const int32_t* n_steps, const int64_t* episode) {
-    ARG(c, "null"); JOIN(c); ENV(c);
-    const size_t E = c->E, W = c->env_width;
-    if (n_steps) for (size_t e = 0; e < E; ++e) ARG(n_steps[e] >= 0, "mi_env_set_state: n_steps must not be negative");
-    if (state) HIPC(hipMemcpyAsync(c->env_state, state, E * W * 8, hipMemcpyHostToDevice, c->stream));
-    if (n_steps) HIPC(hipMemcpyAsync(c->env_nsteps, n_steps, E * 4, hipMemcpyHostToDevice, c->stream));
-    if (episode) HIPC(hipMemcpyAsync(c->env_episode, episode, E * 8, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));      // caller buffers may be pageable temporaries
-    return 0;
-}
 // ------------------------------------------------------------------------------------------ pipelined rollout (env groups)
 // The reference's loop (agents/ppo.py:225-236) is strictly serial per step: obs -> H2D -> forward -> D2H act -> env.step.  An env's
 // next frame depends only on its OWN action, so the E envs split into G contiguous groups whose chains

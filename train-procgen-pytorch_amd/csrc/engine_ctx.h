@@ -1,5 +1,5 @@
-// Internal header of the engine's two translation units (engine.hip: context, network program, C ABI; engine_ops.hip: the op-level
-// and debug entry points that only tests and micro-benchmarks call).  It holds what both need and nothing else: the context, the error
+// Internal header of the engine's translation units (engine.hip: context, network program, C ABI; engine_ops.hip: the op-level
+// and debug entry points that only tests and micro-benchmarks call; env_device.hip: the device-resident envs and their mi_env_* entries).  It holds what both need and nothing else: the context, the error
 // plumbing, and the few engine.hip functions the op code calls.
 #pragma once
 #include "common.h"
@@ -70,6 +70,29 @@ struct Profiler {
     double ms[2][PC_COUNT] = {};
     long long launches[2][PC_COUNT] = {}, units[2][PC_COUNT] = {};
     double bytes[2][PC_COUNT] = {}, flops[2][PC_COUNT] = {};
+};
+
+// ---- the device-resident env of a context (env_device.hip: mi_env_*_create fills it, every other mi_env_* entry reads it)
+struct CartPoleArgs { double low[9], high[9], x_threshold, theta_threshold; int max_steps; };      // kernel arguments of the two envs
+struct MountainCarArgs { double low[5], high[5], left_boundary, max_speed, force, goal_velocity; int max_steps, sparse_rewards; };
+struct DeviceEnv;
+// One constant row per env: how the messages of its create call name it, its state width (= observation width) and action count, what
+// mi_env_step answers to an action out of range, and the launchers of its step and reset kernels.
+struct EnvOps {
+    const char *entry, *columns, *actions, *action_range;
+    int width, n_actions;
+    // one step of all E envs on act[E]: advances state / n_steps / episode, writes the next observation (E x width), reward and done (E)
+    void (*step)(const DeviceEnv& d, int E, const int32_t* act, float* obs_next, float* rew, float* done, hipStream_t st);
+    void (*reset)(const DeviceEnv& d, int E, float* obs, hipStream_t st);
+};
+// ops: null = no env.  state [E][width] fp64, steps of the running episode, episode number; the staging slot of mi_env_step {actions,
+// next observation, reward, done}, which leaves the rings alone.
+struct DeviceEnv {
+    const EnvOps* ops = nullptr;
+    union { CartPoleArgs cp; MountainCarArgs mc; } args = {};
+    unsigned long long seed = 0;
+    double* state = nullptr; int32_t* nsteps = nullptr; long long* episode = nullptr;
+    int32_t* s_act = nullptr; float *s_obs = nullptr, *s_rew = nullptr, *s_done = nullptr;
 };
 
 MI_INTERNAL const DevPool::Backend* hip_pool();      // engine.hip: hipMalloc / hipHostMalloc / hipEventCreateWithFlags and their frees, counted
@@ -171,13 +194,7 @@ struct mi_ctx {
     // minibatch's pred / reward, the loss kernel's fp64 block partials
     int32_t* ipl_idx2 = nullptr; float *ipl_nv = nullptr, *ipl_gnext = nullptr, *ipl_pred = nullptr, *ipl_rew = nullptr; double* ipl_partial = nullptr;
     int ipl_last_n = 0;
-    // device-resident env (mi_env_cartpole_create, cartpole.hip: env_width 9, 2 actions; mi_env_mountain_car_create, mountain_car.hip:
-    // env_width 5, 3 actions): state [E][env_width] fp64, steps of the running episode, episode number; the staging slot of mi_env_step
-    // {actions, next observation, reward, done}, which leaves the rings alone
-    bool env_on = false; EnvKind env_kind = ENV_CARTPOLE; int env_width = 0;
-    CartPoleArgs env_args = {}; MountainCarArgs env_mc = {}; unsigned long long env_seed = 0;
-    double* env_state = nullptr; int32_t* env_nsteps = nullptr; long long* env_episode = nullptr;
-    int32_t* env_s_act = nullptr; float *env_s_obs = nullptr, *env_s_rew = nullptr, *env_s_done = nullptr;
+    DeviceEnv env;                    // the device-resident env, if any (env_device.hip)
     struct mi_sae* sae = nullptr;     // the sparse-autoencoder agent's state (sae.hip: mi_sae_create; released by mi_sae_destroy or mi_destroy)
     // Every device buffer, pinned buffer and event above belongs to a pool (declared last: destroyed first, while the pointers it
     // nulls still exist).  ctx_release is the one place that lets go of them.
@@ -200,6 +217,8 @@ struct InputSrc { const void* base; const int32_t* idx; long long first; };   //
 // their own streams, each in its own rows); 0 everywhere else
 struct FwdOpts { bool recurrent = false; bool heads = true; bool train = false; int soff = 0; };
 MI_INTERNAL void net_forward(mi_ctx* c, const InputSrc& src, int n, const FwdOpts& o);
+// mi_env_rollout (env_device.hip) chains T + 1 policy steps with its env steps
+MI_INTERNAL int issue_policy_step(mi_ctx* c, int32_t t, uint64_t seed, const float* du);
 MI_INTERNAL void linear_fwd(mi_ctx* c, const float* X, int relu_x, const float* W, const float* b, float* Y, int n, int in, int out, int relu_out, int x_bf16 = 0);
 MI_INTERNAL void linear_dgrad(mi_ctx* c, const float* dY, const float* W, const float* mask, float* dX, int n, int in, int out, int x_bf16 = 0);
 MI_INTERNAL void linear_wgrad(mi_ctx* c, const float* dY, const float* X, int relu_x, float* gW, float* gb, int n, int in, int out, int x_bf16 = 0);

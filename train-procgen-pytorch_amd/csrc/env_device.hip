@@ -1,0 +1,273 @@
+// The device-resident envs (mi_env_* in include/mi355ppo.h): the numpy vector envs of common/env/vec_envs.py with state, physics,
+// termination, episode resets, reward and done in HBM.  One thread per env, fp64, no LDS, no atomics; a few dozen floating-point
+// operations per env and step -- the point is not the arithmetic but that a rollout needs no host round trip.  gfx950 only.
+//
+// An env is a physics struct (CartPole, MountainCar): `Args` (its kernel arguments), `W` (state columns = observation width), `A`
+// (actions), `args(DeviceEnv)` (its member of the context's union) and two device functions
+//     fresh(p, seed, e, episode, s)         the start of episode `episode` of env e into s[W]
+//     advance(p, s, act, &reward) -> ended  one step on s[W] in the host env's operation order; reward of this step
+// The kernels, the launchers, the create checks and every other mi_env_* entry are shared: they reach an env through its table row
+// (EnvOps, below) alone.  fp contraction is off in every function that does env arithmetic (the pragma is lexically scoped): each operation
+// rounds as numpy's separate array operations do.
+#include "engine_ctx.h"
+#include "policy_math.h"
+
+// low + (high - low) * u per column (start_space of the reference's pre-vectorised envs).  The stream is the device env's own:
+// Philox4x32-10 keyed by the env's seed, counter {e, episode lo, episode hi, block0 + b}, b = 0 .. (W + 1) / 2 - 1 = two 53-bit
+// uniforms each (columns 2b and 2b + 1 from words {0, 1} and {2, 3}; an odd W leaves the last two words unused).  The host envs draw
+// whole numpy blocks whenever any env ends; that is not reproduced.
+template <int W, typename Args>
+__device__ __forceinline__ void env_draw(const Args& p, unsigned long long seed, int e, long long episode, int block0, double* s) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int b = 0; b < (W + 1) / 2; ++b) {
+        uint32_t c[4] = {(uint32_t)e, (uint32_t)(unsigned long long)episode, (uint32_t)((unsigned long long)episode >> 32), (uint32_t)(block0 + b)};
+        uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+        philox4x32_10(c, k);
+        s[2 * b] = p.low[2 * b] + (p.high[2 * b] - p.low[2 * b]) * philox_u53(c[0], c[1]);
+        if (2 * b + 1 < W) s[2 * b + 1] = p.low[2 * b + 1] + (p.high[2 * b + 1] - p.low[2 * b + 1]) * philox_u53(c[2], c[3]);
+    }
+}
+
+// CartPoleVec (the reference's discrete_env/cartpole_pre_vec.py:214-262 on pre_vec_env.py:86-118): blocks 0..4 of an episode's
+// counters (18 words needed, 20 drawn); reward 1 every step.
+struct CartPole {
+    using Args = CartPoleArgs;
+    static constexpr int W = 9, A = 2;
+    static const Args& args(const DeviceEnv& d) { return d.args.cp; }
+    static __device__ __forceinline__ void fresh(const Args& p, unsigned long long seed, int e, long long episode, double* s) {
+        env_draw<W>(p, seed, e, episode, 0, s);
+    }
+    static __device__ __forceinline__ bool advance(const Args& p, double* s, int act, double* reward) {
+#pragma clang fp contract(off)
+        const double x = s[0], xd = s[1], th = s[2], thd = s[3], g = s[4], length = s[5], m_cart = s[6], m_pole = s[7], f_mag = s[8];
+        const double tau = 0.02;
+        const double force = (act == 0 ? -1.0 : 1.0) * f_mag;
+        const double ct = cos(th), st = sin(th);
+        const double pml = m_pole * length, total = m_pole + m_cart;
+        const double temp = (force + (pml * (thd * thd)) * st) / total;
+        const double thacc = (g * st - ct * temp) / (length * (4.0 / 3.0 - (m_pole * (ct * ct)) / total));
+        const double xacc = temp - ((pml * thacc) * ct) / total;
+        s[0] = x + tau * xd; s[1] = xd + tau * xacc; s[2] = th + tau * thd; s[3] = thd + tau * thacc;
+        *reward = 1.0;
+        return (s[0] < -p.x_threshold) | (s[0] > p.x_threshold) | (s[2] < -p.theta_threshold) | (s[2] > p.theta_threshold);
+    }
+};
+
+// MountainCarVec (discrete_env/mountain_car_pre_vec.py:194-209 on pre_vec_env.py:78-118).  The start is drawn again while
+// goal_position > right_boundary (StartSpace.sample's condition, helper_pre_vec.py:28-38): attempt a uses blocks 3a .. 3a + 2 (10 words
+// needed, 12 drawn).  The loop is BOUNDED: after MC_MAX_ATTEMPTS rejected attempts the last draw is kept with goal_position =
+// right_boundary.  The host refuses range sets that accept a draw with probability below 1/2, so that happens with probability at most
+// 2^-32 per reset.  The velocity column has low == high == 0: 0 + 0 * u = 0 exactly.  The clips of the step are numpy's
+// minimum(maximum(x, lo), hi), the wall test an exact ==; the reward is that of the post-step, pre-reset position.
+#define MC_MAX_ATTEMPTS 32
+struct MountainCar {
+    using Args = MountainCarArgs;
+    static constexpr int W = 5, A = 3;
+    static const Args& args(const DeviceEnv& d) { return d.args.mc; }
+    static __device__ __forceinline__ void fresh(const Args& p, unsigned long long seed, int e, long long episode, double* s) {
+        bool ok = false;
+        for (int attempt = 0; attempt < MC_MAX_ATTEMPTS && !ok; ++attempt) {
+            env_draw<W>(p, seed, e, episode, 3 * attempt, s);
+            ok = !(s[4] > s[3]);
+        }
+        if (!ok) s[4] = s[3];
+    }
+    static __device__ __forceinline__ bool advance(const Args& p, double* s, int act, double* reward) {
+#pragma clang fp contract(off)
+        double pos = s[0], vel = s[1];
+        const double gravity = s[2], right = s[3], goal = s[4];
+        vel = vel + ((double)(act - 1) * p.force + cos(3.0 * pos) * (-gravity));
+        vel = vel < -p.max_speed ? -p.max_speed : vel;
+        vel = vel > p.max_speed ? p.max_speed : vel;
+        pos = pos + vel;
+        pos = pos < p.left_boundary ? p.left_boundary : pos;
+        pos = pos > right ? right : pos;
+        if (pos == p.left_boundary && vel < 0.0) vel = 0.0;
+        const bool ended = (pos >= goal) & (vel >= p.goal_velocity);
+        *reward = p.sparse_rewards ? -1.0 : sin(3.0 * pos) * 0.45 + 0.55 - 1.0;
+        s[0] = pos; s[1] = vel;
+        return ended;
+    }
+};
+
+template <int W>
+__device__ __forceinline__ void env_store(const double* s, double* state_row, float* obs_row) {
+#pragma unroll
+    for (int j = 0; j < W; ++j) { state_row[j] = s[j]; obs_row[j] = (float)s[j]; }
+}
+
+// One step of every env.  act: E actions (ring slot t); obs_next: E x W (ring slot t + 1); rew / done: E each (ring slot t).  As on the
+// host, done is this step's termination flag (truncation at max_steps included) and the stored observation is the post-reset state.
+template <typename Env>
+__global__ __launch_bounds__(64) void env_step_kernel(typename Env::Args p, double* state, int32_t* n_steps, long long* episode,
+                                                      const int32_t* act, unsigned long long seed, float* obs_next, float* rew,
+                                                      float* done, int E) {
+    constexpr int W = Env::W;
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= E) return;
+    double s[W], reward;
+#pragma unroll
+    for (int j = 0; j < W; ++j) s[j] = state[(size_t)e * W + j];
+    bool ended = Env::advance(p, s, act[e], &reward);
+    int ns = n_steps[e] + 1;
+    ended |= ns >= p.max_steps;
+    if (ended) {
+        const long long ep = episode[e] + 1;
+        Env::fresh(p, seed, e, ep, s);
+        episode[e] = ep;
+        ns = 0;
+    }
+    n_steps[e] = ns;
+    env_store<W>(s, state + (size_t)e * W, obs_next + (size_t)e * W);
+    rew[e] = (float)reward;
+    done[e] = ended ? 1.0f : 0.0f;
+}
+
+// every env starts a fresh episode (mi_env_reset): episode += 1, n_steps = 0, the state of that episode
+template <typename Env>
+__global__ __launch_bounds__(64) void env_reset_kernel(typename Env::Args p, double* state, int32_t* n_steps, long long* episode,
+                                                       unsigned long long seed, float* obs, int E) {
+    constexpr int W = Env::W;
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= E) return;
+    double s[W];
+    const long long ep = episode[e] + 1;
+    Env::fresh(p, seed, e, ep, s);
+    episode[e] = ep;
+    n_steps[e] = 0;
+    env_store<W>(s, state + (size_t)e * W, obs + (size_t)e * W);
+}
+
+// float(state) into a ring slot: observation 0 of a rollout
+__global__ __launch_bounds__(256) void env_emit_obs_kernel(const double* state, float* obs, int n /* E * W */) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < n) obs[k] = (float)state[k];
+}
+
+template <typename Env>
+static void env_step(const DeviceEnv& d, int E, const int32_t* act, float* obs_next, float* rew, float* done, hipStream_t st) {
+    hipLaunchKernelGGL(env_step_kernel<Env>, dim3((E + 63) / 64), dim3(64), 0, st, Env::args(d), d.state, d.nsteps, d.episode, act, d.seed,
+                       obs_next, rew, done, E);
+}
+template <typename Env>
+static void env_reset(const DeviceEnv& d, int E, float* obs, hipStream_t st) {
+    hipLaunchKernelGGL(env_reset_kernel<Env>, dim3((E + 63) / 64), dim3(64), 0, st, Env::args(d), d.state, d.nsteps, d.episode, d.seed, obs, E);
+}
+
+// ------------------------------------------------------------------------------------------ the env table and the mi_env_* entry points
+// The serial rollout of the cart-pole / mountain-car sets is T + 1 round trips: policy step -> actions to the host -> the numpy env's
+// step -> the next observations up.  With the env on the device a rollout is ONE call that enqueues T + 1 policy steps and T env steps
+// on the main stream and returns; the only host wait is the caller's read of the reward / done rings afterwards.  A context holds at
+// most one env: the create call points c->env.ops at its row, and every other mi_env_* entry goes through that row.
+template <typename Env>
+static constexpr EnvOps env_row(const char* entry, const char* columns, const char* actions, const char* action_range) {
+    return {entry, columns, actions, action_range, Env::W, Env::A, env_step<Env>, env_reset<Env>};
+}
+static const EnvOps CARTPOLE_ENV = env_row<CartPole>("mi_env_cartpole_create", "the cart-pole's nine state columns", "push left / push right",
+                                                     "mi_env_step: every action must be 0 or 1");
+static const EnvOps MOUNTAIN_CAR_ENV = env_row<MountainCar>("mi_env_mountain_car_create", "the mountain car's five state columns",
+                                                            "push left / none / push right", "mi_env_step: every action must be 0, 1 or 2");
+
+// what every create call checks, in this order (the context's shape before its occupancy), worded from the env's row
+static int env_check(mi_ctx* c, const EnvOps& o, int max_steps, const double* low, const double* high) {
+    const std::string f = std::string(o.entry) + ": ", w = std::to_string(o.width), a = std::to_string(o.n_actions);
+    ARG(c->cfg.arch == MI_ARCH_MLP, f + "arch must be MI_ARCH_MLP");
+    ARG(c->cfg.obs_dim == o.width, f + "obs_dim must be " + w + " (" + o.columns + ")");
+    ARG(c->cfg.n_actions == o.n_actions, f + "n_actions must be " + a + " (" + o.actions + ")");
+    ARG(c->E >= 2, f + "n_envs must be at least 2");
+    ARG(!c->gru_on, f + "a recurrent context (mi_set_gru) is not supported");
+    ARG(!c->env.ops, f + "this context already has an env");
+    ARG(max_steps >= 1, f + "max_steps must be at least 1");
+    for (int j = 0; j < o.width; ++j) ARG(low[j] <= high[j], f + "low must not exceed high");      // (also refuses NaN)
+    return 0;
+}
+// the env's buffers (the same seven allocations whatever the env) and the fields every mi_env_* entry reads
+static int env_attach(mi_ctx* c, const EnvOps* ops, uint64_t seed) {
+    const size_t E = c->E, W = ops->width;
+    DeviceEnv& d = c->env;
+    DevPool& m = c->pool; DevPool::Group all(m);
+    HIPC(m.dev(&d.state, E * W)); HIPC(m.dev(&d.nsteps, E)); HIPC(m.dev(&d.episode, E));
+    HIPC(m.dev(&d.s_act, E)); HIPC(m.dev(&d.s_obs, E * W)); HIPC(m.dev(&d.s_rew, E)); HIPC(m.dev(&d.s_done, E));
+    all.keep = true;
+    d.seed = seed;
+    d.ops = ops;
+    return 0;
+}
+int mi_env_cartpole_create(mi_ctx* c, const mi_cartpole_params* p, uint64_t seed) {
+    ARG(c && p, "null"); JOIN(c);
+    const EnvOps& o = CARTPOLE_ENV;
+    if (int r = env_check(c, o, p->max_steps, p->low, p->high)) return r;
+    CartPoleArgs& a = c->env.args.cp;
+    for (int j = 0; j < 9; ++j) { a.low[j] = p->low[j]; a.high[j] = p->high[j]; }
+    a.x_threshold = p->x_threshold; a.theta_threshold = p->theta_threshold; a.max_steps = p->max_steps;
+    return env_attach(c, &o, seed);
+}
+int mi_env_mountain_car_create(mi_ctx* c, const mi_mountain_car_params* p, uint64_t seed) {
+    ARG(c && p, "null"); JOIN(c);
+    const EnvOps& o = MOUNTAIN_CAR_ENV;
+    if (int r = env_check(c, o, p->max_steps, p->low, p->high)) return r;
+    ARG(p->max_speed >= 0, "mi_env_mountain_car_create: max_speed must not be negative");
+    // (the start loop is bounded on the device whatever the ranges; the host's acceptance rule makes its fallback a 2^-32 event)
+    MountainCarArgs& a = c->env.args.mc;
+    for (int j = 0; j < 5; ++j) { a.low[j] = p->low[j]; a.high[j] = p->high[j]; }
+    a.left_boundary = p->left_boundary; a.max_speed = p->max_speed; a.force = p->force;
+    a.goal_velocity = p->goal_velocity; a.max_steps = p->max_steps; a.sparse_rewards = p->sparse_rewards != 0;
+    return env_attach(c, &o, seed);
+}
+#define ENV(c) ARG((c)->env.ops, "no env on this context (mi_env_cartpole_create / mi_env_mountain_car_create)")
+int mi_env_reset(mi_ctx* c) {
+    ARG(c, "null"); JOIN(c); ENV(c);
+    c->env.ops->reset(c->env, c->E, c->obsf, c->stream);
+    HIPC(hipGetLastError());
+    return 0;
+}
+int mi_env_step(mi_ctx* c, const int64_t* act, float* obs_out, float* rew_out, float* done_out) {
+    ARG(c && act, "null"); JOIN(c); ENV(c);
+    const DeviceEnv& d = c->env;
+    const size_t E = c->E, W = d.ops->width;
+    for (size_t e = 0; e < E; ++e) ARG(act[e] >= 0 && act[e] < d.ops->n_actions, d.ops->action_range);
+    HIPC(hipStreamSynchronize(c->stream));      // (h_i may still be the source / destination of an earlier call's copy)
+    for (size_t e = 0; e < E; ++e) c->h_i[e] = (int32_t)act[e];
+    HIPC(hipMemcpyAsync(d.s_act, c->h_i, E * 4, hipMemcpyHostToDevice, c->stream));
+    d.ops->step(d, c->E, d.s_act, d.s_obs, d.s_rew, d.s_done, c->stream);
+    HIPC(hipGetLastError());
+    if (obs_out) HIPC(hipMemcpyAsync(obs_out, d.s_obs, E * W * 4, hipMemcpyDeviceToHost, c->stream));
+    if (rew_out) HIPC(hipMemcpyAsync(rew_out, d.s_rew, E * 4, hipMemcpyDeviceToHost, c->stream));
+    if (done_out) HIPC(hipMemcpyAsync(done_out, d.s_done, E * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return 0;
+}
+int mi_env_rollout(mi_ctx* c, uint64_t seed) {
+    ARG(c, "null"); JOIN(c); ENV(c);
+    ARG(!c->gru_on, "mi_env_rollout: a recurrent context (mi_set_gru) is not supported");
+    const DeviceEnv& d = c->env;
+    const size_t E = c->E, W = d.ops->width;
+    hipLaunchKernelGGL(env_emit_obs_kernel, dim3((unsigned)((E * W + 255) / 256)), dim3(256), 0, c->stream, d.state, c->obsf, (int)(E * W));
+    for (int t = 0; t < c->T; ++t) {
+        if (int r = issue_policy_step(c, t, seed, nullptr)) return r;
+        d.ops->step(d, c->E, c->act + t * E, c->obsf + (t + 1) * E * W, c->rew + t * E, c->done + t * E, c->stream);
+    }
+    return issue_policy_step(c, c->T, seed, nullptr);
+}
+int mi_env_get_state(mi_ctx* c, double* state, int32_t* n_steps, int64_t* episode) {
+    ARG(c, "null"); JOIN(c); ENV(c);
+    const DeviceEnv& d = c->env;
+    const size_t E = c->E, W = d.ops->width;
+    if (state) HIPC(hipMemcpyAsync(state, d.state, E * W * 8, hipMemcpyDeviceToHost, c->stream));
+    if (n_steps) HIPC(hipMemcpyAsync(n_steps, d.nsteps, E * 4, hipMemcpyDeviceToHost, c->stream));
+    if (episode) HIPC(hipMemcpyAsync(episode, d.episode, E * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return 0;
+}
+int mi_env_set_state(mi_ctx* c, const double* state, const int32_t* n_steps, const int64_t* episode) {
+    ARG(c, "null"); JOIN(c); ENV(c);
+    const DeviceEnv& d = c->env;
+    const size_t E = c->E, W = d.ops->width;
+    if (n_steps) for (size_t e = 0; e < E; ++e) ARG(n_steps[e] >= 0, "mi_env_set_state: n_steps must not be negative");
+    if (state) HIPC(hipMemcpyAsync(d.state, state, E * W * 8, hipMemcpyHostToDevice, c->stream));
+    if (n_steps) HIPC(hipMemcpyAsync(d.nsteps, n_steps, E * 4, hipMemcpyHostToDevice, c->stream));
+    if (episode) HIPC(hipMemcpyAsync(d.episode, episode, E * 8, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));      // caller buffers may be pageable temporaries
+    return 0;
+}

@@ -272,20 +272,22 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ device-resident envs (mi_env_*): cart-pole, mountain car
-    _env_width = 0          # columns of the env's state = the observation width: set by the create call (9 cart-pole, 5 mountain car)
+    _env_width = 0          # columns of the env's state = the observation width: set by the create call from its params struct
+
+    def _env_create(self, create, params, low, high, seed, *scalars):
+        """What the create calls share: low / high as the params struct's arrays (their length is the env's width), the 64-bit seed."""
+        W = dict(params._fields_)["low"]._length_
+        low, high = np.asarray(low, np.float64).reshape(W), np.asarray(high, np.float64).reshape(W)
+        p = params((C.c_double * W)(*low), (C.c_double * W)(*high), *scalars)
+        self._chk(create(self._ctx, C.byref(p), C.c_uint64(int(seed) & (2 ** 64 - 1))))
+        self._env_width = W
 
     def env_cartpole_create(self, low, high, x_threshold, theta_threshold, max_steps, seed=0):
-        low, high = np.asarray(low, np.float64).reshape(9), np.asarray(high, np.float64).reshape(9)
-        p = _CartPoleParams((C.c_double * 9)(*low), (C.c_double * 9)(*high), float(x_threshold), float(theta_threshold), int(max_steps))
-        self._chk(self.lib.mi_env_cartpole_create(self._ctx, C.byref(p), C.c_uint64(int(seed) & (2 ** 64 - 1))))
-        self._env_width = 9
+        self._env_create(self.lib.mi_env_cartpole_create, _CartPoleParams, low, high, seed, float(x_threshold), float(theta_threshold), int(max_steps))
 
     def env_mountain_car_create(self, low, high, left_boundary, max_speed, force, goal_velocity, max_steps, sparse_rewards=True, seed=0):
-        low, high = np.asarray(low, np.float64).reshape(5), np.asarray(high, np.float64).reshape(5)
-        p = _MountainCarParams((C.c_double * 5)(*low), (C.c_double * 5)(*high), float(left_boundary), float(max_speed), float(force),
-                               float(goal_velocity), int(max_steps), int(bool(sparse_rewards)))
-        self._chk(self.lib.mi_env_mountain_car_create(self._ctx, C.byref(p), C.c_uint64(int(seed) & (2 ** 64 - 1))))
-        self._env_width = 5
+        self._env_create(self.lib.mi_env_mountain_car_create, _MountainCarParams, low, high, seed, float(left_boundary), float(max_speed),
+                         float(force), float(goal_velocity), int(max_steps), int(bool(sparse_rewards)))
 
     def env_reset(self):
         """Every env starts a fresh episode; observation slot 0 holds float32(state).  Asynchronous."""

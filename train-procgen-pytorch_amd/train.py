@@ -39,7 +39,7 @@ from agents.ppo import PPO
 from agents.ppo_pure import PPOPure
 from agents.sae import SAE, check_supported as sae_check_supported
 from agents.ipl import IPL, check_supported as ipl_check_supported
-from common.env.vec_envs import EnvGroups, SyntheticFrames, create_cartpole, create_mountain_car, create_procgen_env
+from common.env.vec_envs import EnvGroups, SyntheticFrames, create_procgen_env, device_env_labels, vector_env
 from common.logger import Logger, SimpleLogger
 from common.misc_util import set_global_seeds
 from common.model import ImpalaModel, MLPModel
@@ -173,12 +173,11 @@ def create_logdir_train(model_file, env_name, exp_name, seed, rank_suffix=""):
 def _one_env(env_name, n_envs, seed, A, args, hp, is_valid, ret_rms=None, num_threads=None):
     if env_name == "synthetic":
         return SyntheticFrames(n_envs, A, seed)
-    if env_name == "mountain_car":
-        # 5 observations, 3 actions -> MLPModel(5, ...); --device_env: the same env resident on the device (DeviceMountainCar)
-        return create_mountain_car(hp, is_valid, seed=seed, n_envs=n_envs, device=bool(getattr(args, "device_env", False)))
-    if env_name.startswith("cartpole"):
-        # 9 observations -> MLPModel(9, ...), BASELINE config 1; --device_env: the same env resident on the device (DeviceCartPole)
-        return create_cartpole(hp, is_valid, seed=seed, n_envs=n_envs, device=bool(getattr(args, "device_env", False)))
+    vec = vector_env(env_name)
+    if vec is not None:
+        # cart-pole: 9 observations -> MLPModel(9, ...), BASELINE config 1; mountain car: 5 observations, 3 actions -> MLPModel(5, ...);
+        # --device_env: the same env resident on the device (DeviceCartPole, DeviceMountainCar)
+        return vec.create(hp, is_valid, seed=seed, n_envs=n_envs, device=bool(getattr(args, "device_env", False)))
     return create_procgen_env(env_name=env_name, n_envs=n_envs, is_valid=is_valid, val_env_name=args.val_env_name,
                               start_level=args.start_level, num_levels=args.num_levels, distribution_mode=args.distribution_mode,
                               num_threads=num_threads or args.num_threads, paint_vel_info=hp.get("paint_vel_info", args.paint_vel_info),
@@ -204,7 +203,7 @@ def make_env(env_name, n_envs, seed, A, args, hp, is_valid=False):
     if G <= 0:
         # auto: 4 chains keep the GPU's stream slots busy; with a validation env the agent runs both rollouts as lanes of one loop, 2 + 2
         G = (2 if getattr(args, "use_valid_env", False) else 4) if n_envs >= 128 and n_envs % 8 == 0 else 2
-    if G == 1 or n_envs % G or (n_envs // G) % 2 or env_name.startswith("cartpole") or env_name == "mountain_car":
+    if G == 1 or n_envs % G or (n_envs // G) % 2 or vector_env(env_name) is not None:
         return _one_env(env_name, n_envs, seed, A, args, hp, is_valid)
     rms = None
     if env_name != "synthetic" and hp.get("normalize_rew", True):
@@ -232,8 +231,8 @@ def initialize_model(device, env, hp):
 def check_device_env(env_name, hp, algo):
     """--device_env covers the MLP 9-observation cart-pole and the MLP 5-observation mountain car with a non-recurrent policy on one GPU
     under algo ppo / ppo-pure."""
-    if not (env_name.startswith("cartpole") or env_name == "mountain_car"):
-        raise NotImplementedError(f"--device_env with env_name {env_name} is not supported: only the cart-pole (cartpole*) and mountain_car have a device-resident env")
+    if vector_env(env_name) is None:
+        raise NotImplementedError(f"--device_env with env_name {env_name} is not supported: only {device_env_labels()} have a device-resident env")
     if hp.get("recurrent", False):
         raise NotImplementedError("--device_env with recurrent: True is not supported: the device rollout runs no GRU step")
     if int(os.environ.get("WORLD_SIZE", 1)) > 1:
