@@ -463,6 +463,32 @@ int mi_op_adam(mi_ctx* ctx, int32_t variant, int64_t n, float* p, float* g, floa
                float* v2, const int64_t* off5, float lr, float max_norm, int32_t step, float* gnorm_out);
 /* op-level: the cross-rank merge of R (<= 4096) advantage statistics {count, mean, M2} (fp64) -> stats3_out, as mi_adv_normalize_global runs it */
 int mi_op_adv_merge(mi_ctx* ctx, const double* all, int32_t R, double* stats3_out);
+/* op-level: the policy / value heads at update size (csrc/heads.hip) on caller data through the production launchers, any context.
+ * mode 0: heads_fwd_kernel.  out = hout [n][O] = feat [n][256] Wh^T + bh; H must be 256.  dY, gW, gb unused.
+ * mode 1: heads_bwd_kernel + its slab sum, H in [1, 256].  out = dfeat [n][H] = (dY [n][O] Wh) * (feat > 0 if relu_mask); gW [O][H] and gb [O]
+ *         hold the initial gradients and receive += dY^T feat, += colsum(dY).  The workspace is the 512 * (O*H + O) floats the launcher asks
+ *         for, poisoned.  bh unused.
+ * Refused (-1) before any launch: O outside [1, 16], mode 0 with H != 256, mode 1 with H > 256, n outside [1, 65536].
+ * Outputs are poisoned and followed by canary bands as in mi_op_resblock. */
+int mi_op_heads(mi_ctx* ctx, int32_t mode, int32_t n, int32_t H, int32_t O, const float* feat, const float* Wh, const float* bh, const float* dY,
+                int32_t relu_mask, float* out, float* gW, float* gb);
+/* op-level: the rollout's sampling kernels on caller data, any context.  (a) heads_sample_kernel on feat [n][H], Wh [A + 1][H], bh [A + 1]
+ * (H in [1, 4096]: every staging branch) with hout requested and no staging / flag / ticket pointers; (b) sample_kernel and (c)
+ * logp_all_kernel on the hout that (a) wrote.  u [n] = the uniforms, or NULL: Philox(seed, counter + row).
+ * Out: act2 [2][n] and logp2 [2][n] of (a), (b); value3 [3][n] of (a), (b), (c); pack [n][3] and hout [n][A + 1] of (a); table [n][A] of (c). */
+int mi_op_sample(mi_ctx* ctx, int32_t n, int32_t H, int32_t A, const float* feat, const float* Wh, const float* bh, const float* u, uint64_t seed,
+                 uint64_t counter, int32_t value_from_logits, int32_t* act2, float* logp2, float* value3, float* pack, float* hout, float* table);
+/* op-level: the PPO loss kernels alone (csrc/loss.hip) on caller arrays, any context.  hout [n][A + 1]; idx [n] into act, old_logp, old_value,
+ * ret, adv [n_rows]; means and gradients scale with 1 / n_global; hp->fs_coef must be 0.
+ * mode 0: loss_fwd_kernel, loss_finalize_kernel (phase 3), loss_bwd_kernel: the two-phase path, the only one where x_entropy_coef != 0 is legal.
+ * mode 1: loss_fwd_seg_kernel with the gradient in the same pass + loss_finalize_seg_kernel (phase 3) over n_seg <= 16 segments of seg_n[k] >= 0
+ *         consecutive samples (sum n), as mi_minibatch_multi; x_entropy_coef != 0 is refused.  An empty segment's record is not meaningful.
+ * Out: dY [n][A + 1]; partial [blocks][8 + A], blocks = sum ceil(segment / 64) (columns 0..2 and 8..8+A written, the others poison);
+ * stats [segments][32] (0 pi_loss 1 value_loss 2 entropy 3 x_ent 4 total 5 fs 6 marg, 8.. q[A]; the others poison); log [segments][8]. */
+int mi_op_ppo_loss(mi_ctx* ctx, int32_t mode, int32_t n, int32_t A, const float* hout, const int32_t* idx, int32_t n_rows, const int32_t* act,
+                   const float* old_logp, const float* old_value, const float* ret, const float* adv, const mi_hparams* hp,
+                   int32_t value_from_logits, int32_t n_global, const int32_t* seg_n, int32_t n_seg, float* dY_out, float* partial_out,
+                   float* stats_out, float* log_out);
 int mi_selftest_mfma(mi_ctx* ctx, float* max_err);
 /* what the last mi_minibatch left in the activation buffers (first n samples), fp32 NHWC: which = 8 * block + k, k = 0 pooled map,
  * 1 res1.conv1 out, 2 res1 out, 3 res2.conv1 out, 4 block out, 5 max-pool arg-max (window position ky*3+kx); which = 100: features

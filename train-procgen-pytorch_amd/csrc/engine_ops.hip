@@ -751,6 +751,150 @@ int mi_op_ipl_greedy(mi_ctx* c, int32_t n, int32_t A, const float* hout, int32_t
     return 0;
 }
 
+// The policy / value heads at update size (heads.hip) on caller data through the production launchers; independent of the context's sizes.
+//   mode 0: launch_heads_fwd: out = hout [n][O] = feat [n][256] Wh^T + bh.  H must be 256.
+//   mode 1: launch_heads_bwd with its slab sum: out = dfeat [n][H] = (dY [n][O] Wh) * (feat > 0 if relu_mask); gW [O][H] and gb [O] are in / out
+//           (+= dY^T feat, += colsum(dY)).  The workspace is exactly the 512 * (O*H + O) floats the launcher asks for, poisoned: the slab
+//           sum reads what the kernel must have written.  H <= 256.
+// O <= 16 in both modes; what the kernels do not support is refused before anything is launched.
+int mi_op_heads(mi_ctx* c, int32_t mode, int32_t n, int32_t H, int32_t O, const float* feat, const float* Wh, const float* bh, const float* dY,
+                int32_t relu_mask, float* out, float* gW, float* gb) {
+    ARG(c && feat && Wh && out, "null"); JOIN(c);
+    ARG(mode == 0 || mode == 1, "mode");
+    ARG(n >= 1 && n <= 65536, "n must be in [1, 65536]");
+    ARG(O >= 1 && O <= 16, "the heads kernels take at most 16 outputs (O in [1, 16])");
+    ARG(mode == 0 ? H == 256 : (H >= 1 && H <= 256), "mode 0 (heads_fwd_kernel) needs H == 256, mode 1 (heads_bwd_kernel) H in [1, 256]");
+    ARG(mode == 0 ? bh != nullptr : (dY && gW && gb), "mode 0 needs bh; mode 1 needs dY, gW and gb");
+    const std::string hook = "mi_op_heads mode " + std::to_string(mode);
+    OpMem m(hook.c_str(), c->stream);
+    const size_t nf = (size_t)n * H, nw = (size_t)O * H, ny = (size_t)n * O;
+    float *dfe = nullptr, *dw = nullptr, *db = nullptr, *ddy = nullptr, *dout = nullptr;
+    if (int r = upload(m, feat, nf * 4, (void**)&dfe)) return r;
+    if (int r = upload(m, Wh, nw * 4, (void**)&dw)) return r;
+    if (mode == 0) {
+        if (int r = upload(m, bh, (size_t)O * 4, (void**)&db)) return r;
+        HIPC(m.out(&dout, ny * 4, "hout"));
+        launch_heads_fwd(dfe, dw, db, dout, n, O, c->stream);
+        if (int r = op_finish(c, m)) return r;
+        HIPC(hipMemcpy(out, dout, ny * 4, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    if (int r = upload(m, dY, ny * 4, (void**)&ddy)) return r;
+    float *dgw = nullptr, *dgb = nullptr, *ws = nullptr;
+    HIPC(m.out(&dout, nf * 4, "dfeat")); HIPC(m.out(&dgw, nw * 4, "gW")); HIPC(m.out(&dgb, (size_t)O * 4, "gb"));
+    HIPC(m.out(&ws, (size_t)512 * (nw + O) * 4, "the slab workspace"));
+    HIPC(hipStreamSynchronize(c->stream));          // (the fills run on the context's stream, the copies on the null stream)
+    HIPC(hipMemcpy(dgw, gW, nw * 4, hipMemcpyHostToDevice)); HIPC(hipMemcpy(dgb, gb, (size_t)O * 4, hipMemcpyHostToDevice));
+    launch_heads_bwd(ddy, dfe, dw, relu_mask != 0, dout, dgw, dgb, ws, n, H, O, c->stream);
+    if (int r = op_finish(c, m)) return r;
+    HIPC(hipMemcpy(out, dout, nf * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(gW, dgw, nw * 4, hipMemcpyDeviceToHost)); HIPC(hipMemcpy(gb, dgb, (size_t)O * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The rollout's three sampling kernels (heads.hip) on caller data, any context: (a) launch_heads_sample on feat [n][H], Wh [A + 1][H], bh
+// with hout requested and no staging / flag / ticket pointers, (b) launch_sample and (c) launch_logp_all on the hout that (a) wrote.  u [n]
+// holds the uniforms, or is NULL and the kernels draw Philox(seed, counter + row).
+// Out: act2 [2][n] and logp2 [2][n] of (a), (b); value3 [3][n] of (a), (b), (c); pack [n][3] and hout [n][A + 1] of (a); table [n][A] of (c).
+int mi_op_sample(mi_ctx* c, int32_t n, int32_t H, int32_t A, const float* feat, const float* Wh, const float* bh, const float* u, uint64_t seed,
+                 uint64_t counter, int32_t value_from_logits, int32_t* act2, float* logp2, float* value3, float* pack, float* hout, float* table) {
+    ARG(c && feat && Wh && bh && act2 && logp2 && value3 && pack && hout && table, "null"); JOIN(c);
+    ARG(n >= 1 && n <= 65536, "n must be in [1, 65536]"); ARG(A >= 1 && A <= 16, "A must be in [1, 16]"); ARG(H >= 1 && H <= 4096, "H must be in [1, 4096]");
+    ARG(value_from_logits == 0 || value_from_logits == 1, "value_from_logits");
+    OpMem m("mi_op_sample", c->stream);
+    const size_t nh = (size_t)n * (A + 1), N = (size_t)n;
+    float *dfe = nullptr, *dw = nullptr, *db = nullptr, *du = nullptr;
+    if (int r = upload(m, feat, N * H * 4, (void**)&dfe)) return r;
+    if (int r = upload(m, Wh, (size_t)(A + 1) * H * 4, (void**)&dw)) return r;
+    if (int r = upload(m, bh, (size_t)(A + 1) * 4, (void**)&db)) return r;
+    if (u) { if (int r = upload(m, u, N * 4, (void**)&du)) return r; }
+    int32_t* dact[2] = {}; float *dlp[2] = {}, *dval[3] = {}, *dpack = nullptr, *dh = nullptr, *dtab = nullptr;
+    static const char* who[3] = {"heads_sample", "sample", "logp_all"};
+    for (int k = 0; k < 3; ++k) {
+        if (k < 2) { HIPC(m.out(&dact[k], N * 4, (std::string(who[k]) + "'s act").c_str())); HIPC(m.out(&dlp[k], N * 4, (std::string(who[k]) + "'s logp").c_str())); }
+        HIPC(m.out(&dval[k], N * 4, (std::string(who[k]) + "'s value").c_str()));
+    }
+    HIPC(m.out(&dpack, N * 3 * 4, "pack")); HIPC(m.out(&dh, nh * 4, "hout")); HIPC(m.out(&dtab, N * A * 4, "the log-probability table"));
+    launch_heads_sample(dfe, dw, db, n, H, A, du, seed, counter, dact[0], dlp[0], dval[0], dpack, dh, nullptr, nullptr, nullptr, c->stream,
+                        nullptr, nullptr, 0, value_from_logits);
+    launch_sample(dh, n, A, du, seed, counter, dact[1], dlp[1], dval[1], c->stream, value_from_logits);
+    launch_logp_all(dh, n, A, dtab, dval[2], c->stream, value_from_logits);
+    if (int r = op_finish(c, m)) return r;
+    for (int k = 0; k < 3; ++k) {
+        if (k < 2) { HIPC(hipMemcpy(act2 + k * N, dact[k], N * 4, hipMemcpyDeviceToHost)); HIPC(hipMemcpy(logp2 + k * N, dlp[k], N * 4, hipMemcpyDeviceToHost)); }
+        HIPC(hipMemcpy(value3 + k * N, dval[k], N * 4, hipMemcpyDeviceToHost));
+    }
+    HIPC(hipMemcpy(pack, dpack, N * 3 * 4, hipMemcpyDeviceToHost)); HIPC(hipMemcpy(hout, dh, nh * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(table, dtab, N * A * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The PPO loss kernels alone (loss.hip) on caller arrays, any context: hout [n][A + 1]; idx [n] into the per-sample arrays act, old_logp,
+// old_value, ret, adv [n_rows]; means and gradients scale with 1 / n_global.  fs_coef must be 0 (the feature-sparsity kernels are not run).
+//   mode 0: the two-phase path of multi-rank mode 1 on one rank -- launch_loss_fwd, launch_loss_finalize (phase 3), launch_loss_bwd -- the
+//           only order in which x_entropy_coef != 0 is legal.  One segment: seg_n / n_seg are not read.
+//   mode 1: the one-pass path of mi_minibatch / mi_minibatch_multi -- launch_loss_fwd_seg(with_bwd) + launch_loss_finalize_seg (phase 3, no
+//           feature-sparsity parts) over n_seg <= 16 segments of seg_n[k] >= 0 consecutive samples (sum = n); refuses x_entropy_coef != 0.
+// Out: dY [n][A + 1]; partial [blocks][8 + A] (columns 0..2 and 8..8+A are written); stats [segments][32] (0..6 and 8..8+A); log [segments][8].
+int mi_op_ppo_loss(mi_ctx* c, int32_t mode, int32_t n, int32_t A, const float* hout, const int32_t* idx, int32_t n_rows, const int32_t* act,
+                   const float* old_logp, const float* old_value, const float* ret, const float* adv, const mi_hparams* hp,
+                   int32_t value_from_logits, int32_t n_global, const int32_t* seg_n, int32_t n_seg, float* dY_out, float* partial_out,
+                   float* stats_out, float* log_out) {
+    ARG(c && hout && idx && act && old_logp && old_value && ret && adv && hp && dY_out && partial_out && stats_out && log_out, "null"); JOIN(c);
+    ARG(mode == 0 || mode == 1, "mode");
+    ARG(n >= 1 && n <= 65536 && n_rows >= 1 && n_rows <= (1 << 24), "n must be in [1, 65536], n_rows in [1, 2^24]");
+    ARG(A >= 1 && A <= 16, "A must be in [1, 16]"); ARG(n_global >= 1, "n_global");
+    ARG(value_from_logits == 0 || value_from_logits == 1, "value_from_logits");
+    ARG(hp->fs_coef == 0.f, "fs_coef must be 0: the feature-sparsity kernels are not part of this hook");
+    ARG(mode == 0 || hp->x_entropy_coef == 0.f, "mode 1 (the one-pass path) needs x_entropy_coef == 0");
+    for (int k = 0; k < n; ++k) ARG(idx[k] >= 0 && idx[k] < n_rows, "index out of range");
+    for (int k = 0; k < n_rows; ++k) ARG(act[k] >= 0 && act[k] < A, "action out of range");
+    SegTab st{};
+    st.n_seg = 1; st.start[1] = n;
+    if (mode == 1) {
+        ARG(seg_n && n_seg >= 1 && n_seg <= MI_MAX_SEG, "mode 1: 1 .. 16 segments");
+        long long tot = 0;
+        for (int k = 0; k < n_seg; ++k) { ARG(seg_n[k] >= 0, "negative segment"); tot += seg_n[k]; }
+        ARG(tot == n, "segments do not add up to n");
+        st.n_seg = n_seg;
+        for (int k = 0; k < n_seg; ++k) st.start[k + 1] = st.start[k] + seg_n[k];
+    }
+    const std::string hook = "mi_op_ppo_loss mode " + std::to_string(mode);
+    OpMem m(hook.c_str(), c->stream);
+    const size_t nh = (size_t)n * (A + 1);
+    const int nblk = mode == 0 ? loss_blocks(n) : loss_blocks_seg(st);
+    float *dh = nullptr, *dlp = nullptr, *dov = nullptr, *dret = nullptr, *dadv = nullptr; int32_t *didx = nullptr, *dact = nullptr;
+    if (int r = upload(m, hout, nh * 4, (void**)&dh)) return r;
+    if (int r = upload(m, idx, (size_t)n * 4, (void**)&didx)) return r;
+    if (int r = upload(m, act, (size_t)n_rows * 4, (void**)&dact)) return r;
+    if (int r = upload(m, old_logp, (size_t)n_rows * 4, (void**)&dlp)) return r;
+    if (int r = upload(m, old_value, (size_t)n_rows * 4, (void**)&dov)) return r;
+    if (int r = upload(m, ret, (size_t)n_rows * 4, (void**)&dret)) return r;
+    if (int r = upload(m, adv, (size_t)n_rows * 4, (void**)&dadv)) return r;
+    LossArgs a{};
+    float *stats = nullptr, *log = nullptr;
+    HIPC(m.out(&a.dY, nh * 4, "dY")); HIPC(m.out(&a.partial, (size_t)nblk * (8 + A) * 4, "the block partials"));
+    HIPC(m.out(&stats, (size_t)st.n_seg * 32 * 4, "the statistics")); HIPC(m.out(&log, (size_t)st.n_seg * 8 * 4, "the log records"));
+    a.hout = dh; a.idx = didx; a.act = dact; a.old_logp = dlp; a.old_value = dov; a.ret = dret; a.adv = dadv; a.stats = stats; a.n = n; a.A = A;
+    a.inv_n_global = 1.0f / (float)n_global;
+    a.value_from_logits = value_from_logits;
+    a.hp = LossHP{hp->eps_clip, hp->value_coef, hp->entropy_coef, hp->x_entropy_coef, hp->entropy_multiplier, hp->fs_coef};
+    if (mode == 0) {
+        launch_loss_fwd(a, c->stream);
+        launch_loss_finalize(a, nblk, 3, nullptr, log, c->stream);
+        launch_loss_bwd(a, c->stream);
+    } else {
+        launch_loss_fwd_seg(a, st, true, c->stream);
+        launch_loss_finalize_seg(a, st, 3, stats, nullptr, 2048, nullptr, log, c->stream);
+    }
+    if (int r = op_finish(c, m)) return r;
+    HIPC(hipMemcpy(dY_out, a.dY, nh * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(partial_out, a.partial, (size_t)nblk * (8 + A) * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(stats_out, stats, (size_t)st.n_seg * 32 * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(log_out, log, (size_t)st.n_seg * 8 * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // D = A(16x4) * B(4x16) with asymmetric integer data through the operand maps the kernels assume:
 // A[i = lane&15][k = lane>>4], B[k = lane>>4][j = lane&15], D[row = (lane>>4)*4 + r][col = lane&15]
 __global__ void mfma_selftest_kernel(float* d) {

@@ -9,8 +9,14 @@
 // ------------------------------------------------------------------------------------------ heads forward (training-sized batches)
 // hout[s][o] = feat[s] . Wh[o] + bh[o] for the (A+1) <= 16 head outputs, H == 256 (policy.py:74-80).  The generic GEMM ran this
 // 8192 x 16 x 256 product as 16-wide tiles of a 64-wide kernel plus a split-K pass (19 us); here 16 rows and the head matrix go
-// through LDS and thread (row, output) owns one dot product, summed in the order of heads_sample_kernel -- the rollout's logits and
-// the update's logits of one observation under one set of weights are the same bits.
+// through LDS and thread (row, output) owns one dot product, written with the sums in the order of heads_sample_kernel's H == 256 loop.
+// The two kernels' logits of one observation under one set of weights are NOT the same bits, as this comment used to say: how the four
+// products of a step are rounded is left to the compiler's contraction, and as built this loop multiplies and adds them unfused while
+// heads_sample_kernel's takes one multiply and three fused multiply-adds.  What holds, and what tests/test_gpu_policy_ops.py pins: each is
+// within the dot product's bound of the float64 logit, and the two differ by at most 138 * 2^-24 * (sum|feat * W| + |b|) (a step's term differs
+// by at most 8 roundings of its products, each of the 64 additions and the bias's by one more in either kernel).  Making them equal means spelling
+// the step out with fmaf in both loops; that moves every update-sized logit by a rounding and with it the training results, so it is not
+// done in passing.
 __global__ __launch_bounds__(256) void heads_fwd_kernel(const float* __restrict__ feat, const float* __restrict__ Wh, const float* __restrict__ bh,
                                                         float* __restrict__ hout, int n, int O) {
     __shared__ __attribute__((aligned(16))) float s_f[16 * 260];
@@ -175,7 +181,8 @@ void launch_philox_debug(const uint32_t* in6, int n, uint32_t* out4, float* u_ou
 // taken in action order 0..A-1 (each lane re-adds the terms from LDS), so the numbers are those of the sequential
 // log_softmax_twice + CDF walk of sample_kernel.
 // WIDE (H > 256: IMPALA output_dim up to 512, any MLP latent_size): features and head rows are staged in K chunks of 256 through the
-// same LDS rows, each dot product carried across the chunks in the same order of operations as the single-chunk loop.
+// same LDS rows, each dot product carried across the chunks in the same order of sums as the single-chunk loop (whether the
+// four products of a step are fused is the compiler's choice per loop: as built, the H == 256 loop fuses them, the others do not).
 // LSE (mi_config.value_from_logits): the value is mx + log(s1) of the first normalisation below -- the same sums in the same order as
 // log_softmax_twice_t<true>, so GIVEN THE SAME LOGITS it is the number sample_kernel / logp_all_kernel / the loss compute.  This kernel's
 // logits are its own dot products, taken in another order than the GEMM's that feeds those kernels, so across the two paths the values

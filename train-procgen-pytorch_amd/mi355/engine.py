@@ -60,7 +60,7 @@ EXPORTS = ("mi_last_error mi_create mi_destroy mi_sync mi_host_alloc mi_host_fre
            "mi_get_params mi_copy_params mi_get_grads mi_set_adam_state mi_get_adam_state mi_put_obs mi_get_obs mi_put_step "
            "mi_put_policy_outputs mi_read_field mi_write_field mi_policy_step mi_rollout_step mi_rollout_groups mi_rollout_lane_info mi_rollout_submit mi_rollout_wait mi_predict_staged mi_value_saliency mi_commit_staged mi_set_gru mi_rec_state mi_get_hidden mi_rec_begin mi_get_hidden_ring mi_forward_rec mi_forward mi_compute_estimates "
            "mi_adv_stats mi_adv_apply mi_minibatch mi_minibatch_multi mi_optimizer_step mi_loss_log_read mi_device_ptr "
-           "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_op_fc_bf16 mi_op_reduce mi_op_adam mi_op_adv_merge mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_gru_step mi_debug_step_latency mi_debug_lane_probe mi_debug_live_resources "
+           "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_op_fc_bf16 mi_op_reduce mi_op_adam mi_op_adv_merge mi_op_heads mi_op_sample mi_op_ppo_loss mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_gru_step mi_debug_step_latency mi_debug_lane_probe mi_debug_live_resources "
            "mi_gru_train mi_minibatch_rec mi_get_gru mi_get_gru_grads mi_get_gru_adam_state mi_set_gru_adam_state mi_debug_gru_seq "
            "mi_sae_create mi_sae_destroy mi_sae_param_count mi_sae_set_params mi_sae_get_params mi_sae_get_grads mi_sae_set_adam_state mi_sae_get_adam_state mi_sae_put_ring "
            "mi_sae_get_hidden mi_sae_get_logits mi_sae_step mi_sae_minibatch mi_sae_probe_minibatch mi_sae_optimizer_step mi_sae_debug_forward "
@@ -884,6 +884,64 @@ class Engine:
         out = np.empty(3, np.float64)
         self._chk(self.lib.mi_op_adv_merge(self._ctx, _fp(a), C.c_int32(a.shape[0]), _fp(out)))
         return out
+
+    def op_heads_fwd(self, feat, Wh, bh):
+        """launch_heads_fwd on feat (n, 256), Wh (O, 256), bh (O,) (mi_op_heads mode 0) -> hout (n, O)."""
+        feat, Wh, bh = _f32(feat), _f32(Wh), _f32(bh)
+        n, H, O = feat.shape[0], feat.shape[1], Wh.shape[0]
+        out = np.empty((n, O), np.float32)
+        self._chk(self.lib.mi_op_heads(self._ctx, C.c_int32(0), C.c_int32(n), C.c_int32(H), C.c_int32(O), _fp(feat), _fp(Wh), _fp(bh), None,
+                                       C.c_int32(0), _fp(out), None, None))
+        return out
+
+    def op_heads_bwd(self, dY, feat, Wh, relu_mask, gW0, gb0):
+        """launch_heads_bwd and its slab sum on dY (n, O), feat (n, H), Wh (O, H) (mi_op_heads mode 1) ->
+        (dfeat (n, H), gW0 + dY^T feat, gb0 + colsum(dY))."""
+        dY, feat, Wh = _f32(dY), _f32(feat), _f32(Wh)
+        n, H, O = feat.shape[0], feat.shape[1], Wh.shape[0]
+        gW, gb = np.array(gW0, dtype=np.float32, order="C").reshape(O, H), np.array(gb0, dtype=np.float32, order="C").reshape(O)
+        if dY.shape != (n, O) or Wh.shape != (O, H):
+            raise EngineError("op_heads_bwd: dY (n, O), feat (n, H), Wh (O, H)")
+        out = np.empty((n, H), np.float32)
+        self._chk(self.lib.mi_op_heads(self._ctx, C.c_int32(1), C.c_int32(n), C.c_int32(H), C.c_int32(O), _fp(feat), _fp(Wh), None, _fp(dY),
+                                       C.c_int32(int(bool(relu_mask))), _fp(out), _fp(gW), _fp(gb)))
+        return out, gW, gb
+
+    def op_sample(self, feat, Wh, bh, u=None, seed=0, counter=0, value_from_logits=False):
+        """The three sampling kernels on caller data (mi_op_sample): heads_sample_kernel on feat (n, H), Wh (A + 1, H), bh (A + 1,), then
+        sample_kernel and logp_all_kernel on the hout it wrote -> dict(fused=(act, logp, value), sample=(act, logp, value), pack (n, 3),
+        hout (n, A + 1), table (n, A), table_value (n,)).  u (n,) or None: Philox(seed, counter + row)."""
+        feat, Wh, bh = _f32(feat), _f32(Wh), _f32(bh).reshape(-1)
+        n, H, A = feat.shape[0], feat.shape[1], Wh.shape[0] - 1
+        if Wh.shape != (A + 1, H) or bh.size != A + 1:
+            raise EngineError("op_sample: feat (n, H), Wh (A + 1, H), bh (A + 1,)")
+        u = None if u is None else _f32(u).reshape(n)
+        act, logp, val = np.empty((2, n), np.int32), np.empty((2, n), np.float32), np.empty((3, n), np.float32)
+        pack, hout, table = np.empty((n, 3), np.float32), np.empty((n, A + 1), np.float32), np.empty((n, A), np.float32)
+        self._chk(self.lib.mi_op_sample(self._ctx, C.c_int32(n), C.c_int32(H), C.c_int32(A), _fp(feat), _fp(Wh), _fp(bh), _fp(u), C.c_uint64(seed),
+                                        C.c_uint64(counter), C.c_int32(int(bool(value_from_logits))), _fp(act), _fp(logp), _fp(val), _fp(pack),
+                                        _fp(hout), _fp(table)))
+        return dict(fused=(act[0], logp[0], val[0]), sample=(act[1], logp[1], val[1]), pack=pack, hout=hout, table=table, table_value=val[2])
+
+    def op_ppo_loss(self, mode, hout, idx, act, old_logp, old_value, ret, adv, hp, value_from_logits=False, n_global=None, seg_n=None):
+        """The PPO loss kernels on caller arrays (mi_op_ppo_loss): mode 0 the two-phase path (loss_fwd, finalize, loss_bwd), mode 1 the
+        one-pass segmented path over seg_n.  hout (n, A + 1); idx (n,) into act / old_logp / old_value / ret / adv ->
+        (dY (n, A + 1), partial (blocks, 8 + A), stats (segments, 32), log (segments, 8))."""
+        hout = _f32(hout)
+        n, A = hout.shape[0], hout.shape[1] - 1
+        idx, act = np.ascontiguousarray(idx, dtype=np.int32).reshape(n), np.ascontiguousarray(act, dtype=np.int32).reshape(-1)
+        arrs = [_f32(a).reshape(-1) for a in (old_logp, old_value, ret, adv)]
+        if any(a.size != act.size for a in arrs):
+            raise EngineError("op_ppo_loss: act, old_logp, old_value, ret, adv must have one length")
+        seg = np.ascontiguousarray([n] if (mode == 0 or seg_n is None) else seg_n, dtype=np.int32)
+        nblk = int(sum(-(-int(k) // 64) for k in seg))
+        dY, partial = np.empty((n, A + 1), np.float32), np.empty((nblk, 8 + A), np.float32)
+        stats, log = np.empty((seg.size, 32), np.float32), np.empty((seg.size, 8), np.float32)
+        self._chk(self.lib.mi_op_ppo_loss(self._ctx, C.c_int32(mode), C.c_int32(n), C.c_int32(A), _fp(hout), _fp(idx), C.c_int32(act.size), _fp(act),
+                                          *[_fp(a) for a in arrs], C.byref(hp), C.c_int32(int(bool(value_from_logits))),
+                                          C.c_int32(n if n_global is None else n_global), _fp(seg), C.c_int32(seg.size), _fp(dY), _fp(partial),
+                                          _fp(stats), _fp(log)))
+        return dY, partial, stats, log
 
     def debug_read(self, which, n):
         """Activation tensor `which` (see include/mi355ppo.h mi_debug_read) of the last minibatch pass, first n samples, fp32 NHWC."""
