@@ -159,6 +159,13 @@ int mi_env_mountain_car_create(mi_ctx* ctx, const mi_mountain_car_params* params
 int mi_env_reset(mi_ctx* ctx);
 int mi_env_step(mi_ctx* ctx, const int64_t* act, float* obs_out /* E x W */, float* rew_out, float* done_out);
 int mi_env_rollout(mi_ctx* ctx, uint64_t seed);
+/* mi_env_rollout as ONE launch (opt-in): a workgroup carries 16 envs through all T + 1 policy steps and T env steps -- the MLP and the heads
+ * in fp32 on the matrix cores with the activations in LDS, the sampler and the env step on the threads that own an env.  It leaves what
+ * mi_env_rollout(ctx, seed) leaves -- observation slots 0..T, act / logp / rew / done [T], value [T + 1], the env's state / n_steps / episode --
+ * from the same sampling counters t * E + e and the same reset stream; the env arithmetic is the same code, the policy numbers differ by
+ * fp32 summation order only.  Asynchronous on the context's stream.  Refused by name, before anything is written: no env on the context,
+ * a context with a GRU set, mlp_depth above 16, mlp_width or out_dim not a multiple of 16 or above 512, more than 15 actions. */
+int mi_env_rollout_resident(mi_ctx* ctx, uint64_t seed);
 int mi_env_get_state(mi_ctx* ctx, double* state /* E x W */, int32_t* n_steps, int64_t* episode);
 int mi_env_set_state(mi_ctx* ctx, const double* state, const int32_t* n_steps, const int64_t* episode);
 

@@ -55,6 +55,8 @@ class PPO(BaseAgent):
         self.seed = int(kwargs.get("seed", 0))
         self.merge_accumulation = bool(kwargs.get("merge_accumulation", True))      # (new) see optimize()
         self.joint_rollouts = bool(kwargs.get("joint_rollouts", True))              # (new) training + validation rollout in one host loop (train())
+        # (new) train.py --resident_rollout: a device-resident env's rollout as ONE launch (mi_env_rollout_resident) instead of the chain
+        self.resident_rollout = bool(kwargs.get("resident_rollout", False))
         # train.py --detect_nan (reference: autograd anomaly mode + a NaN hook on every module's output, train.py:123-124,234-250):
         # here the policy outputs of every rollout step, every minibatch's loss record and every gradient norm are checked
         self.detect_nan = bool(kwargs.get("detect_nan", False))
@@ -297,7 +299,7 @@ class PPO(BaseAgent):
     def _collect_device(self, env, engine, storage, obs, hidden_state, done):
         """The same T steps + bootstrap step for an env that lives on the device (common/env/vec_envs.py DeviceCartPole): ONE call
         enqueues T + 1 policy steps and T env steps (mi_env_rollout; the policy steps are `_collect`'s kernels with its sampling
-        counters), and the host waits once, for the reward / done rings it mirrors for the logger.  `obs` is what the env's state on the
+        counters; with `resident_rollout` the one kernel of mi_env_rollout_resident, same counters), and the host waits once, for the reward / done rings it mirrors for the logger.  `obs` is what the env's state on the
         device already is (its reset() or the previous rollout returned it) and is not uploaded."""
         from common.env.vec_envs import StepInfo
         if self.policy.is_recurrent():
@@ -306,7 +308,7 @@ class PPO(BaseAgent):
         if env.engine is not engine:                             # first use on this lane: the env is created in this engine's context
             env.attach_engine(engine)
             env.reset()
-        engine.env_rollout(self.seed * 1000003 + self._iter)
+        engine.env_rollout(self.seed * 1000003 + self._iter, resident=self.resident_rollout)      # (either lane's engine: the validation twin too)
         engine.read_field_into(F_REW, storage._rew)              # (T, E) each, straight into the pinned mirrors
         engine.read_field_into(F_DONE, storage._done)
         if self.detect_nan:

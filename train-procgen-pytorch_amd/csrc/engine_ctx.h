@@ -1,5 +1,5 @@
 // Internal header of the engine's translation units (engine.hip: context, network program, C ABI; engine_ops.hip: the op-level
-// and debug entry points that only tests and micro-benchmarks call; env_device.hip: the device-resident envs and their mi_env_* entries).  It holds what both need and nothing else: the context, the error
+// and debug entry points that only tests and micro-benchmarks call; env_device.hip: the device-resident envs and their mi_env_* entries; env_resident.hip: their one-launch rollout).  It holds what both need and nothing else: the context, the error
 // plumbing, and the few engine.hip functions the op code calls.
 #pragma once
 #include "common.h"
@@ -76,14 +76,29 @@ struct Profiler {
 struct CartPoleArgs { double low[9], high[9], x_threshold, theta_threshold; int max_steps; };      // kernel arguments of the two envs
 struct MountainCarArgs { double low[5], high[5], left_boundary, max_speed, force, goal_velocity; int max_steps, sparse_rewards; };
 struct DeviceEnv;
+// What the resident rollout kernel (env_resident.hip) reads of the network and writes of the rings.  RES_R envs per workgroup (one MFMA
+// M tile, a compile-time choice); an MLP of at most RES_MAX_LAYERS layers, each at most RES_MAX_WIDTH wide (the LDS activation rows).
+// vec[l] / heads_vec: the layer's weight rows may be loaded 16 bytes at a time (in a multiple of 16 and w_off a multiple of 4).
+#define RES_R 16
+#define RES_MAX_LAYERS 16
+#define RES_MAX_WIDTH 512
+struct ResidentNet {
+    const float* params;
+    int n_layers, H, lse, heads_vec;
+    int in[RES_MAX_LAYERS], out[RES_MAX_LAYERS], vec[RES_MAX_LAYERS];
+    long long w_off[RES_MAX_LAYERS], b_off[RES_MAX_LAYERS], wh_off, bh_off;
+};
+struct ResidentRings { float* obs; int32_t* act; float *logp, *value, *rew, *done; };
 // One constant row per env: how the messages of its create call name it, its state width (= observation width) and action count, what
-// mi_env_step answers to an action out of range, and the launchers of its step and reset kernels.
+// mi_env_step answers to an action out of range, and the launchers of its step, reset and resident rollout kernels.
 struct EnvOps {
     const char *entry, *columns, *actions, *action_range;
     int width, n_actions;
     // one step of all E envs on act[E]: advances state / n_steps / episode, writes the next observation (E x width), reward and done (E)
     void (*step)(const DeviceEnv& d, int E, const int32_t* act, float* obs_next, float* rew, float* done, hipStream_t st);
     void (*reset)(const DeviceEnv& d, int E, float* obs, hipStream_t st);
+    // a whole rollout in one launch (mi_env_rollout_resident): what T + 1 policy steps and T env steps leave in the rings and the env
+    void (*rollout)(const DeviceEnv& d, const ResidentNet& net, const ResidentRings& ring, int E, int T, unsigned long long seed, hipStream_t st);
 };
 // ops: null = no env.  state [E][width] fp64, steps of the running episode, episode number; the staging slot of mi_env_step {actions,
 // next observation, reward, done}, which leaves the rings alone.

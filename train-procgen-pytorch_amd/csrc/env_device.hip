@@ -11,85 +11,7 @@
 // rounds as numpy's separate array operations do.
 #include "engine_ctx.h"
 #include "policy_math.h"
-
-// low + (high - low) * u per column (start_space of the reference's pre-vectorised envs).  The stream is the device env's own:
-// Philox4x32-10 keyed by the env's seed, counter {e, episode lo, episode hi, block0 + b}, b = 0 .. (W + 1) / 2 - 1 = two 53-bit
-// uniforms each (columns 2b and 2b + 1 from words {0, 1} and {2, 3}; an odd W leaves the last two words unused).  The host envs draw
-// whole numpy blocks whenever any env ends; that is not reproduced.
-template <int W, typename Args>
-__device__ __forceinline__ void env_draw(const Args& p, unsigned long long seed, int e, long long episode, int block0, double* s) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int b = 0; b < (W + 1) / 2; ++b) {
-        uint32_t c[4] = {(uint32_t)e, (uint32_t)(unsigned long long)episode, (uint32_t)((unsigned long long)episode >> 32), (uint32_t)(block0 + b)};
-        uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-        philox4x32_10(c, k);
-        s[2 * b] = p.low[2 * b] + (p.high[2 * b] - p.low[2 * b]) * philox_u53(c[0], c[1]);
-        if (2 * b + 1 < W) s[2 * b + 1] = p.low[2 * b + 1] + (p.high[2 * b + 1] - p.low[2 * b + 1]) * philox_u53(c[2], c[3]);
-    }
-}
-
-// CartPoleVec (the reference's discrete_env/cartpole_pre_vec.py:214-262 on pre_vec_env.py:86-118): blocks 0..4 of an episode's
-// counters (18 words needed, 20 drawn); reward 1 every step.
-struct CartPole {
-    using Args = CartPoleArgs;
-    static constexpr int W = 9, A = 2;
-    static const Args& args(const DeviceEnv& d) { return d.args.cp; }
-    static __device__ __forceinline__ void fresh(const Args& p, unsigned long long seed, int e, long long episode, double* s) {
-        env_draw<W>(p, seed, e, episode, 0, s);
-    }
-    static __device__ __forceinline__ bool advance(const Args& p, double* s, int act, double* reward) {
-#pragma clang fp contract(off)
-        const double x = s[0], xd = s[1], th = s[2], thd = s[3], g = s[4], length = s[5], m_cart = s[6], m_pole = s[7], f_mag = s[8];
-        const double tau = 0.02;
-        const double force = (act == 0 ? -1.0 : 1.0) * f_mag;
-        const double ct = cos(th), st = sin(th);
-        const double pml = m_pole * length, total = m_pole + m_cart;
-        const double temp = (force + (pml * (thd * thd)) * st) / total;
-        const double thacc = (g * st - ct * temp) / (length * (4.0 / 3.0 - (m_pole * (ct * ct)) / total));
-        const double xacc = temp - ((pml * thacc) * ct) / total;
-        s[0] = x + tau * xd; s[1] = xd + tau * xacc; s[2] = th + tau * thd; s[3] = thd + tau * thacc;
-        *reward = 1.0;
-        return (s[0] < -p.x_threshold) | (s[0] > p.x_threshold) | (s[2] < -p.theta_threshold) | (s[2] > p.theta_threshold);
-    }
-};
-
-// MountainCarVec (discrete_env/mountain_car_pre_vec.py:194-209 on pre_vec_env.py:78-118).  The start is drawn again while
-// goal_position > right_boundary (StartSpace.sample's condition, helper_pre_vec.py:28-38): attempt a uses blocks 3a .. 3a + 2 (10 words
-// needed, 12 drawn).  The loop is BOUNDED: after MC_MAX_ATTEMPTS rejected attempts the last draw is kept with goal_position =
-// right_boundary.  The host refuses range sets that accept a draw with probability below 1/2, so that happens with probability at most
-// 2^-32 per reset.  The velocity column has low == high == 0: 0 + 0 * u = 0 exactly.  The clips of the step are numpy's
-// minimum(maximum(x, lo), hi), the wall test an exact ==; the reward is that of the post-step, pre-reset position.
-#define MC_MAX_ATTEMPTS 32
-struct MountainCar {
-    using Args = MountainCarArgs;
-    static constexpr int W = 5, A = 3;
-    static const Args& args(const DeviceEnv& d) { return d.args.mc; }
-    static __device__ __forceinline__ void fresh(const Args& p, unsigned long long seed, int e, long long episode, double* s) {
-        bool ok = false;
-        for (int attempt = 0; attempt < MC_MAX_ATTEMPTS && !ok; ++attempt) {
-            env_draw<W>(p, seed, e, episode, 3 * attempt, s);
-            ok = !(s[4] > s[3]);
-        }
-        if (!ok) s[4] = s[3];
-    }
-    static __device__ __forceinline__ bool advance(const Args& p, double* s, int act, double* reward) {
-#pragma clang fp contract(off)
-        double pos = s[0], vel = s[1];
-        const double gravity = s[2], right = s[3], goal = s[4];
-        vel = vel + ((double)(act - 1) * p.force + cos(3.0 * pos) * (-gravity));
-        vel = vel < -p.max_speed ? -p.max_speed : vel;
-        vel = vel > p.max_speed ? p.max_speed : vel;
-        pos = pos + vel;
-        pos = pos < p.left_boundary ? p.left_boundary : pos;
-        pos = pos > right ? right : pos;
-        if (pos == p.left_boundary && vel < 0.0) vel = 0.0;
-        const bool ended = (pos >= goal) & (vel >= p.goal_velocity);
-        *reward = p.sparse_rewards ? -1.0 : sin(3.0 * pos) * 0.45 + 0.55 - 1.0;
-        s[0] = pos; s[1] = vel;
-        return ended;
-    }
-};
+#include "env_physics.h"
 
 template <int W>
 __device__ __forceinline__ void env_store(const double* s, double* state_row, float* obs_row) {
@@ -162,7 +84,7 @@ static void env_reset(const DeviceEnv& d, int E, float* obs, hipStream_t st) {
 // most one env: the create call points c->env.ops at its row, and every other mi_env_* entry goes through that row.
 template <typename Env>
 static constexpr EnvOps env_row(const char* entry, const char* columns, const char* actions, const char* action_range) {
-    return {entry, columns, actions, action_range, Env::W, Env::A, env_step<Env>, env_reset<Env>};
+    return {entry, columns, actions, action_range, Env::W, Env::A, env_step<Env>, env_reset<Env>, env_rollout_resident<Env>};
 }
 static const EnvOps CARTPOLE_ENV = env_row<CartPole>("mi_env_cartpole_create", "the cart-pole's nine state columns", "push left / push right",
                                                      "mi_env_step: every action must be 0 or 1");
@@ -249,6 +171,32 @@ int mi_env_rollout(mi_ctx* c, uint64_t seed) {
         d.ops->step(d, c->E, c->act + t * E, c->obsf + (t + 1) * E * W, c->rew + t * E, c->done + t * E, c->stream);
     }
     return issue_policy_step(c, c->T, seed, nullptr);
+}
+// The same rollout as ONE launch (env_resident.hip): every refusal comes before the launch, so a refused call leaves every ring as it was.
+int mi_env_rollout_resident(mi_ctx* c, uint64_t seed) {
+    ARG(c, "null"); JOIN(c); ENV(c);
+    const std::string f = "mi_env_rollout_resident: ";
+    ARG(!c->gru_on, f + "a recurrent context (mi_set_gru) is not supported");
+    const size_t L = c->mlp.size();
+    ARG(L >= 2 && L <= RES_MAX_LAYERS, f + "mlp_depth must be at least 2 and at most " + std::to_string(RES_MAX_LAYERS));
+    ARG(c->cfg.mlp_width % 16 == 0 && c->cfg.mlp_width <= RES_MAX_WIDTH, f + "mlp_width must be a multiple of 16 and at most " + std::to_string(RES_MAX_WIDTH));
+    ARG(c->H % 16 == 0 && c->H <= RES_MAX_WIDTH, f + "out_dim must be a multiple of 16 and at most " + std::to_string(RES_MAX_WIDTH));
+    ARG(c->A + 1 <= 16, f + "n_actions must be at most 15");
+    const DeviceEnv& d = c->env;
+    ARG(c->cfg.obs_dim == d.ops->width && c->cfg.obs_dim <= 16, f + "obs_dim must be the env's state width");
+    ResidentNet net = {};
+    net.params = c->params; net.n_layers = (int)L; net.H = c->H; net.lse = c->lse;
+    for (size_t l = 0; l < L; ++l) {
+        const Linear& m = c->mlp[l];
+        net.in[l] = m.in; net.out[l] = m.out; net.w_off[l] = m.w_off; net.b_off[l] = m.b_off;
+        net.vec[l] = m.in % 16 == 0 && m.w_off % 4 == 0;
+    }
+    net.wh_off = c->wh_off; net.bh_off = c->bh_off; net.heads_vec = c->wh_off % 4 == 0;      // (H is a multiple of 16)
+    const ResidentRings ring = {c->obsf, c->act, c->logp, c->value, c->rew, c->done};
+    c->prof.phase = 0;
+    d.ops->rollout(d, net, ring, c->E, c->T, seed, c->stream);
+    HIPC(hipGetLastError());
+    return 0;
 }
 int mi_env_get_state(mi_ctx* c, double* state, int32_t* n_steps, int64_t* episode) {
     ARG(c, "null"); JOIN(c); ENV(c);

@@ -65,7 +65,7 @@ EXPORTS = ("mi_last_error mi_create mi_destroy mi_sync mi_host_alloc mi_host_fre
            "mi_sae_create mi_sae_destroy mi_sae_param_count mi_sae_set_params mi_sae_get_params mi_sae_get_grads mi_sae_set_adam_state mi_sae_get_adam_state mi_sae_put_ring "
            "mi_sae_get_hidden mi_sae_get_logits mi_sae_step mi_sae_minibatch mi_sae_probe_minibatch mi_sae_optimizer_step mi_sae_debug_forward "
            "mi_ipl_minibatch mi_ipl_read_pred mi_predict_greedy mi_op_ipl_loss mi_op_ipl_greedy "
-           "mi_env_cartpole_create mi_env_mountain_car_create mi_env_reset mi_env_step mi_env_rollout mi_env_get_state mi_env_set_state").split()
+           "mi_env_cartpole_create mi_env_mountain_car_create mi_env_reset mi_env_step mi_env_rollout mi_env_rollout_resident mi_env_get_state mi_env_set_state").split()
 
 
 def load_library():
@@ -317,9 +317,12 @@ class Engine:
         self._chk(self.lib.mi_env_step(self._ctx, _fp(act), _fp(obs), _fp(rew), _fp(done)))
         return obs, rew, done
 
-    def env_rollout(self, seed=0):
-        """The whole rollout -- T + 1 policy steps, T env steps -- enqueued on the engine's stream; returns without waiting."""
-        self._chk(self.lib.mi_env_rollout(self._ctx, C.c_uint64(seed)))
+    def env_rollout(self, seed=0, resident=False):
+        """The whole rollout -- T + 1 policy steps, T env steps -- enqueued on the engine's stream; returns without waiting.  resident: as ONE
+        kernel launch (mi_env_rollout_resident: same rings, state, sampling counters and reset stream; values / log-probabilities differ
+        from the chain's by fp32 summation order) instead of the chain of launches."""
+        call = self.lib.mi_env_rollout_resident if resident else self.lib.mi_env_rollout
+        self._chk(call(self._ctx, C.c_uint64(seed)))
 
     # ------------------------------------------------------------------ policy
     def policy_step(self, t, seed=0, u=None, want_outputs=True):

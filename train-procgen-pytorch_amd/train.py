@@ -11,7 +11,7 @@ there), the log directory layout logs/train/<env>/<exp>/<time>__seed_<seed> with
 format, `--model_file auto` (create_logdir_train, train.py:277-294: the single run directory under the experiment that holds
 model_*.pth is reused and its newest checkpoint loaded -- the reference finds that file and then still hands 'auto' to torch.load),
 `--detect_nan`.  Different on purpose: `--device` defaults to gpu and `cpu` is refused (there is no CPU fallback); config.yml is
-read relative to this file instead of the hard-coded GLOBAL_DIR of helper_local.py:28; new flags --precision, --rollout_groups, --device_env.
+read relative to this file instead of the hard-coded GLOBAL_DIR of helper_local.py:28; new flags --precision, --rollout_groups, --device_env, --resident_rollout.
 `--env_name cartpole*` and `--env_name mountain_car` run the numpy restatements of the reference's pre-vectorised envs (CartPoleVec,
 MountainCarVec) with the serial step; `--device_env` keeps either env on the device (DeviceCartPole, DeviceMountainCar).  A --device_env
 run is not the host run's trajectory past the first episode reset: episode starts come from the device env's own Philox stream."""
@@ -127,6 +127,8 @@ def add_training_args(p):
                    help="env groups of the pipelined rollout (one group's frame upload + forward beside the host's env.step of another); 0 = auto (from 128 envs per rank: 4, or 2 + 2 when a validation env runs beside the training env; else 2; a recurrent policy: 1); 1 = the reference's serial step; a recurrent policy is pipelined only with an explicit G >= 2")
     p.add_argument('--device_env', action="store_true",
                    help="cartpole* and mountain_car only: the env lives on the device (state, physics, resets, reward and done in HBM) and a whole rollout is one call with no host round trip per step; episode starts come from the device env's own Philox stream, not numpy's.  Non-recurrent MLP policies, one GPU, algo ppo / ppo-pure")
+    p.add_argument('--resident_rollout', action="store_true",
+                   help="with --device_env: the whole rollout (T + 1 policy steps, T env steps) is ONE kernel launch -- a workgroup carries 16 envs through every step, the MLP on the matrix cores with activations in LDS (mi_env_rollout_resident).  Same actions, rewards, dones and observations as the default chain of launches; values and log-probabilities differ by fp32 summation order.  mlp_width / latent_size multiples of 16 up to 512")
     p.add_argument('--x_entropy_coef', type=float, default=None)
     p.add_argument('--algo', type=str, default=None, choices=['ppo', 'ppo-pure', 'sae', 'IPL'],
                    help="overrides the set's `algo`: ppo = the reference's agents/ppo.py (a recurrent policy's GRU stays frozen), ppo-pure = agents/ppo_pure.py (a recurrent policy is trained through its GRU with BPTT; single GPU), sae = agents/sae.py (a sparse autoencoder on the block-3 features of the trained IMPALA policy given by --model_file, then a linear probe on its codes; single GPU, use --param_name sae), IPL = agents/IPL.py (non-recurrent, single GPU; sets hard-500-ipl and ipl_cartpole)")
@@ -255,6 +257,10 @@ def train_ppo(args):
         raise NotImplementedError("only algo: ppo, algo: ppo-pure, algo: sae and algo: IPL are accelerated")
     if getattr(args, "device_env", False):                  # everything the device-resident env does not cover, by name, before any env exists
         check_device_env(env_name, hp, algo)
+    if getattr(args, "resident_rollout", False):            # (an opt-in of the device-resident env: reaches the agent as a hyper-parameter)
+        if not getattr(args, "device_env", False):
+            raise NotImplementedError("--resident_rollout needs --device_env: the one-launch rollout runs the device-resident env")
+        hp["resident_rollout"] = True
     if algo == "IPL":                                       # everything outside the built scope, by name, before any engine exists
         hp["learned_gamma"] = bool(hp.get("learned_gamma", False)) or bool(getattr(args, "learned_gamma", False))
         ipl_check_supported(hp, use_greedy_env=bool(getattr(args, "use_greedy_env", False)))
@@ -300,6 +306,7 @@ def train_ppo(args):
     env_valid = make_env(env_name, n_envs, args.seed + 2 * rank + 1, A, args, hp, is_valid=True) if args.use_valid_env else None
     n_groups = len(getattr(env, "env_groups", ()))
     print(f"rollout: {n_groups} pipelined env groups" if n_groups > 1 else
+          "rollout: device-resident env, one kernel launch per rollout" if getattr(env, "on_device", False) and hp.get("resident_rollout") else
           "rollout: device-resident env, one call per rollout" if getattr(env, "on_device", False) else "rollout: serial steps")
     logdir, model_file = create_logdir_train(args.model_file, env_name, args.exp_name, args.seed, f'__rank_{rank}' if world > 1 and rank > 0 else '')
     np.save(os.path.join(logdir, "hyperparameters.npy"), hp)
