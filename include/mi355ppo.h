@@ -132,6 +132,20 @@ typedef struct mi_cartpole_params {
     int32_t max_steps;
 } mi_cartpole_params;
 int mi_env_cartpole_create(mi_ctx* ctx, const mi_cartpole_params* params, uint64_t seed);
+/* ---- the device-resident swing-up cart-pole (the host env is common/env/vec_envs.py CartPoleSwingVec = the reference's
+ *      discrete_env/cartpole_swing_pre_vec.py:19-239 on pre_vec_env.py:21-125).  The cart-pole's context shape (MLP, obs_dim == 9,
+ *      n_actions == 2), state layout, dynamics (the same device function), refusals and start stream (blocks 0..4); the pole hangs down
+ *      at the start, which is the caller's `low` / `high` alone (theta in pi -+ 0.05).  What differs in a step: an env ends beyond
+ *      +-x_threshold or when n_steps reaches max_steps -- there is NO angle threshold -- and the reward is that of the post-step,
+ *      pre-reset state, float(rt * rx) with rt = cos(theta), set to 0 where rt < 0, and rx = cos((x / x_threshold) * (pi / 2)); a row
+ *      that has just ended beyond x_threshold with rt == 0 yields -0.0, as CartPoleSwingVec does.  x_threshold divides, so a value that
+ *      is not positive (or NaN) is refused by name. */
+typedef struct mi_cartpole_swing_params {
+    double low[9], high[9];          /* start ranges per state column */
+    double x_threshold;
+    int32_t max_steps;
+} mi_cartpole_swing_params;
+int mi_env_cartpole_swing_create(mi_ctx* ctx, const mi_cartpole_swing_params* params, uint64_t seed);
 /* ---- the device-resident mountain car (the host env is common/env/vec_envs.py MountainCarVec = the reference's
  *      discrete_env/mountain_car_pre_vec.py:15-219 on pre_vec_env.py:21-125 and helper_pre_vec.py:4-38).  A context holds ONE env: the
  *      create call fixes its kind, and mi_env_reset / _step / _rollout / _get_state / _set_state below dispatch on it; W, the state

@@ -5,6 +5,10 @@ common/env/procgen_wrappers.py:45-124.  Rollout collection stays on the host (no
 * CartPoleVec   -- the reference's 9-observation pre-vectorised cart-pole (discrete_env/cartpole_pre_vec.py) restated in numpy,
                    the plumbing config C1 (MLPModel(9, ...)).
 * DeviceCartPole -- the same env resident on the device (opt-in, train.py --device_env).
+* CartPoleSwingVec -- the reference's pre-vectorised swing-up cart-pole (discrete_env/cartpole_swing_pre_vec.py) restated in numpy and
+                   pinned to the reference's own class by a trajectory fixture: the cart-pole's 9 observations, 2 actions and dynamics,
+                   the pole starts hanging down, reward for holding it up near the centre (`--env_name cartpole_swing`, create_vector_env).
+* DeviceCartPoleSwing -- the same env resident on the device (opt-in, train.py --device_env).
 * MountainCarVec -- the reference's 5-observation pre-vectorised mountain car (discrete_env/mountain_car_pre_vec.py) restated in numpy
                    and pinned to the reference's own class by a trajectory fixture (MLPModel(5, ...), 3 actions).
 * DeviceMountainCar -- the same env resident on the device (opt-in, train.py --device_env).
@@ -105,9 +109,11 @@ class CartPoleVec:
     (pre_vec_env.py:86-87); reward 1 every step; info[i] = {'env_reward': 1.0} (:112-113).  Kept from the reference: when ANY env ends,
     a whole (n_envs, 9) block is drawn and only the ended rows take their values (pre_vec_env.py:111-118), and `done` is the
     `terminated` array AFTER the reset.  The generator is numpy's default_rng(seed) -- what gymnasium's seeding.np_random(seed)
-    constructs (PCG64 over SeedSequence(seed)).  Parity with the reference's class is UNPINNED: it cannot be imported here without
-    stand-ins for gymnasium code it executes (spaces, Env, seeding) and the reference holds no trajectory fixture;
-    tests/test_env_pipeline.py checks the dynamics against a scalar restatement of the same equations."""
+    constructs (PCG64 over SeedSequence(seed)).  The STEP is pinned to the reference's class: tests/golden/g18_cartpole_swing.npz case c/
+    holds one teacher-forced step of CartPoleVecEnv and tests/test_cartpole_swing_host.py reproduces it bit for bit on the rows that go
+    on, with done equal.  Trajectories from a seed are NOT the reference's: its constructor ends in reset(seed=seed) and so draws one
+    block that this constructor does not draw; tests/test_env_pipeline.py checks the dynamics against a scalar
+    restatement of the same equations."""
     tau = 0.02
 
     def __init__(self, n_envs, degrees=12, h_range=2.4, min_gravity=9.8, max_gravity=10.4, min_pole_length=0.5, max_pole_length=1.0,
@@ -240,6 +246,123 @@ def create_cartpole(hyperparameters, is_valid=False, seed=0, n_envs=None, device
     `<name>` (training) or `<name>_v` (validation) overrides a range entry (config.yml `cartpole`: degrees_v 9, h_range_v 1.8);
     max_steps may come from the hyper-parameters too.  device=True: the same arguments build the device-resident DeviceCartPole."""
     return _create_pre_vec(CARTPOLE_PARAM_RANGE, CartPoleVec, DeviceCartPole, hyperparameters, is_valid, seed, n_envs, device)
+
+
+def _cartpole_swing_setup(self, n_envs, h_range, min_gravity, max_gravity, min_pole_length, max_pole_length, min_cart_mass, max_cart_mass,
+                          min_pole_mass, max_pole_mass, min_force_mag, max_force_mag, max_steps, seed):
+    """The constructor part that CartPoleSwingVec and DeviceCartPoleSwing share: the one threshold (cartpole_swing_pre_vec.py:124) and
+    the start ranges per state column (:155-163: the pole hangs down, theta in pi -+ 0.05)."""
+    if n_envs < 2:
+        raise Exception("n_envs must be greater than or equal to 2")
+    self.n_envs = self.num_envs = n_envs
+    self.max_steps, self.seed = max_steps, int(seed)
+    self.x_threshold = h_range
+    self.low = np.array([-0.05, -0.05, np.pi - 0.05, -0.05, min_gravity, min_pole_length, min_cart_mass, min_pole_mass, min_force_mag],
+                        dtype=np.float64)
+    self.high = np.array([0.05, 0.05, np.pi + 0.05, 0.05, max_gravity, max_pole_length, max_cart_mass, max_pole_mass, max_force_mag],
+                         dtype=np.float64)
+    self.observation_space = _Space(shape=(9,))
+    self.action_space = _Space(n=2)
+
+
+class CartPoleSwingVec:
+    """The reference's pre-vectorised swing-up cart-pole (discrete_env/cartpole_swing_pre_vec.py:19-239 on discrete_env/pre_vec_env.py:21-125),
+    restated in numpy float64: the env of `--env_name cartpole_swing`, which the reference's sweep runs with the `mlpmodel` set.
+    Observation = the cart-pole's 9-column state
+
+        [x, x_dot, theta, theta_dot, gravity, pole_length, cart_mass, pole_mass, force_mag]
+
+    and its 2 actions and Euler step (tau = 0.02, CartPoleVec.step's operation order), but another task: every episode starts with the
+    pole hanging DOWN (theta drawn from pi -+ 0.05, the other dynamic variables from +-0.05, the parameters from their ranges); an
+    episode terminates only beyond +-h_range -- there is no angle threshold -- and is truncated at max_steps (default 1000).  Reward, of
+    the post-step, pre-reset state (:230-238): rt = cos(theta), set to 0 where rt < 0 (the pole below the horizontal), rx = cos((x /
+    x_threshold) * (pi / 2)) (1 in the centre, 0 at the edge), reward = rt * rx.  A row that has just ended beyond the edge with rt = 0
+    has rx < 0 and yields -0.0: kept.  info = {'env_reward': reward}.  When ANY env ends a whole (n_envs, 9) block is drawn and only the
+    ended rows take their values, and `done` is the `terminated` array AFTER the reset.
+
+    The generator is numpy's default_rng(seed) -- what gymnasium's seeding.np_random(seed) constructs -- and is consumed exactly as the
+    reference consumes it, including the block its constructor draws through reset(seed=seed) before the caller's own reset().  Parity
+    is PINNED: tests/golden/g18_cartpole_swing.npz holds trajectories of the reference's own class
+    (tests/golden/make_golden_cartpole_swing.py) and tests/test_cartpole_swing_host.py reproduces them bit for bit."""
+    tau = 0.02
+
+    def __init__(self, n_envs, h_range=2.4, min_gravity=9.8, max_gravity=10.4, min_pole_length=0.5, max_pole_length=1.0, min_cart_mass=1.0,
+                 max_cart_mass=1.5, min_pole_mass=0.1, max_pole_mass=0.2, min_force_mag=10., max_force_mag=10., max_steps=1000, seed=0,
+                 **_ignored):
+        _cartpole_swing_setup(self, n_envs, h_range, min_gravity, max_gravity, min_pole_length, max_pole_length, min_cart_mass, max_cart_mass,
+                              min_pole_mass, max_pole_mass, min_force_mag, max_force_mag, max_steps, seed)
+        self.rng = np.random.default_rng(seed)
+        self.reward = np.zeros(n_envs)
+        self.info = StepInfo(n_envs, {"env_reward": self.reward})
+        self.state = np.zeros((n_envs, 9))
+        self.reset()                                     # the reference's constructor ends in reset(seed=seed): one block is consumed here
+
+    def _set(self):
+        fresh = self.rng.uniform(low=self.low, high=self.high, size=(self.n_envs, 9))
+        self.state[self.terminated] = fresh[self.terminated]
+        self.n_steps[self.terminated] = 0
+        return self.state
+
+    def reset(self):
+        self.terminated = np.full(self.n_envs, True)
+        self.n_steps = np.zeros(self.n_envs)
+        return self._set()
+
+    def step(self, act):
+        act = np.asarray(act)
+        assert act.size == self.n_envs and np.all(act < 2)
+        x, xd, th, thd, g, length, m_cart, m_pole, f_mag = self.state.T
+        force = np.where(act.reshape(-1) == 0, -1.0, 1.0) * f_mag
+        ct, st = np.cos(th), np.sin(th)
+        pml, total = m_pole * length, m_pole + m_cart
+        temp = (force + pml * thd ** 2 * st) / total
+        thacc = (g * st - ct * temp) / (length * (4.0 / 3.0 - m_pole * ct ** 2 / total))
+        xacc = temp - pml * thacc * ct / total
+        nx, nth = x + self.tau * xd, th + self.tau * thd
+        self.state = np.vstack((nx, xd + self.tau * xacc, nth, thd + self.tau * thacc, g, length, m_cart, m_pole, f_mag)).T
+        self.terminated = (nx < -self.x_threshold) | (nx > self.x_threshold)
+        rt = np.cos(nth)
+        rt[rt < 0] = 0
+        self.reward = rt * np.cos((nx / self.x_threshold) * (np.pi / 2.0))
+        self.info = StepInfo(self.n_envs, {"env_reward": self.reward})
+        self.n_steps += 1
+        self.terminated[self.n_steps >= self.max_steps] = True
+        if np.any(self.terminated):
+            self._set()
+        return self.state, self.reward, self.terminated, self.info
+
+    def close(self):
+        pass
+
+
+class DeviceCartPoleSwing(_DeviceEnv):
+    """CartPoleSwingVec with the env on the device (train.py --device_env; csrc/env_physics.h `CartPoleSwing`, mi_env_* in include/mi355ppo.h):
+    same constructor arguments, spaces, start ranges and threshold (the same fp64 bits) and the same step arithmetic in fp64 in the same
+    operation order -- the dynamics are the device function DeviceCartPole runs.  As for DeviceCartPole the stream of the episode starts
+    is the device env's own: the start of episode k of env e comes from Philox4x32-10 keyed by `seed`, counter {e, k low word, k high word,
+    block}; CartPoleSwingVec's numpy block draws are NOT reproduced, so the two classes agree step for step until the first reset and in
+    distribution afterwards.  The reward reaches the host as float32.
+    Limits: the 9-observation MLP policy, non-recurrent, one GPU."""
+
+    def __init__(self, n_envs, h_range=2.4, min_gravity=9.8, max_gravity=10.4, min_pole_length=0.5, max_pole_length=1.0, min_cart_mass=1.0,
+                 max_cart_mass=1.5, min_pole_mass=0.1, max_pole_mass=0.2, min_force_mag=10., max_force_mag=10., max_steps=1000, seed=0,
+                 **_ignored):
+        _cartpole_swing_setup(self, n_envs, h_range, min_gravity, max_gravity, min_pole_length, max_pole_length, min_cart_mass, max_cart_mass,
+                              min_pole_mass, max_pole_mass, min_force_mag, max_force_mag, max_steps, seed)
+
+    def _create(self, engine):
+        engine.env_cartpole_swing_create(self.low, self.high, self.x_threshold, self.max_steps, self.seed)
+
+
+# create_cartpole_swing (discrete_env/cartpole_swing_pre_vec.py:313-327): create_cartpole's ranges without `degrees`
+CARTPOLE_SWING_PARAM_RANGE = {k: v for k, v in CARTPOLE_PARAM_RANGE.items() if k != "degrees"}
+
+
+def create_cartpole_swing(hyperparameters, is_valid=False, seed=0, n_envs=None, device=False):
+    """create_cartpole_swing / create_pre_vec / assign_env_vars: as create_cartpole -- the validation env takes the SECOND value of every
+    range, a hyper-parameter `<name>` (training) or `<name>_v` (validation) overrides a range entry, max_steps may come from the
+    hyper-parameters too (else the class's 1000).  device=True: the same arguments build the device-resident DeviceCartPoleSwing."""
+    return _create_pre_vec(CARTPOLE_SWING_PARAM_RANGE, CartPoleSwingVec, DeviceCartPoleSwing, hyperparameters, is_valid, seed, n_envs, device)
 
 
 def mountain_car_acceptance(min_goal_position, max_goal_position, min_right_boundary, max_right_boundary):
@@ -411,6 +534,14 @@ VECTOR_ENVS = {"cartpole*": VectorEnv("the cart-pole (cartpole*)", create_cartpo
 def vector_env(env_name):
     """The VECTOR_ENVS entry of an env name, or None (synthetic frames, Procgen)."""
     return next((v for pattern, v in VECTOR_ENVS.items() if fnmatchcase(env_name, pattern)), None)
+
+
+def create_vector_env(env_name, hyperparameters, is_valid=False, seed=0, n_envs=None, device=False):
+    """Build the pre-vectorised env of an env name that `vector_env` knows: the swing-up cart-pole for the exact name `cartpole_swing`
+    (the reference's env_constructor maps that name to create_cartpole_swing; the `cartpole*` row would build the balance task under
+    it), else the `create` of the name's VECTOR_ENVS row."""
+    create = create_cartpole_swing if env_name == "cartpole_swing" else vector_env(env_name).create
+    return create(hyperparameters, is_valid, seed=seed, n_envs=n_envs, device=device)
 
 
 def device_env_labels():

@@ -73,7 +73,8 @@ struct Profiler {
 };
 
 // ---- the device-resident env of a context (env_device.hip: mi_env_*_create fills it, every other mi_env_* entry reads it)
-struct CartPoleArgs { double low[9], high[9], x_threshold, theta_threshold; int max_steps; };      // kernel arguments of the two envs
+struct CartPoleArgs { double low[9], high[9], x_threshold, theta_threshold; int max_steps; };      // kernel arguments of the envs
+struct CartPoleSwingArgs { double low[9], high[9], x_threshold; int max_steps; };
 struct MountainCarArgs { double low[5], high[5], left_boundary, max_speed, force, goal_velocity; int max_steps, sparse_rewards; };
 struct DeviceEnv;
 // What the resident rollout kernel (env_resident.hip) reads of the network and writes of the rings.  RES_R envs per workgroup (one MFMA
@@ -104,7 +105,7 @@ struct EnvOps {
 // next observation, reward, done}, which leaves the rings alone.
 struct DeviceEnv {
     const EnvOps* ops = nullptr;
-    union { CartPoleArgs cp; MountainCarArgs mc; } args = {};
+    union { CartPoleArgs cp; CartPoleSwingArgs cs; MountainCarArgs mc; } args = {};
     unsigned long long seed = 0;
     double* state = nullptr; int32_t* nsteps = nullptr; long long* episode = nullptr;
     int32_t* s_act = nullptr; float *s_obs = nullptr, *s_rew = nullptr, *s_done = nullptr;

@@ -2,7 +2,7 @@
 // termination, episode resets, reward and done in HBM.  One thread per env, fp64, no LDS, no atomics; a few dozen floating-point
 // operations per env and step -- the point is not the arithmetic but that a rollout needs no host round trip.  gfx950 only.
 //
-// An env is a physics struct (CartPole, MountainCar): `Args` (its kernel arguments), `W` (state columns = observation width), `A`
+// An env is a physics struct (CartPole, CartPoleSwing, MountainCar): `Args` (its kernel arguments), `W` (state columns = observation width), `A`
 // (actions), `args(DeviceEnv)` (its member of the context's union) and two device functions
 //     fresh(p, seed, e, episode, s)         the start of episode `episode` of env e into s[W]
 //     advance(p, s, act, &reward) -> ended  one step on s[W] in the host env's operation order; reward of this step
@@ -88,6 +88,8 @@ static constexpr EnvOps env_row(const char* entry, const char* columns, const ch
 }
 static const EnvOps CARTPOLE_ENV = env_row<CartPole>("mi_env_cartpole_create", "the cart-pole's nine state columns", "push left / push right",
                                                      "mi_env_step: every action must be 0 or 1");
+static const EnvOps CARTPOLE_SWING_ENV = env_row<CartPoleSwing>("mi_env_cartpole_swing_create", "the swing-up cart-pole's nine state columns",
+                                                                "push left / push right", "mi_env_step: every action must be 0 or 1");
 static const EnvOps MOUNTAIN_CAR_ENV = env_row<MountainCar>("mi_env_mountain_car_create", "the mountain car's five state columns",
                                                             "push left / none / push right", "mi_env_step: every action must be 0, 1 or 2");
 
@@ -125,6 +127,16 @@ int mi_env_cartpole_create(mi_ctx* c, const mi_cartpole_params* p, uint64_t seed
     a.x_threshold = p->x_threshold; a.theta_threshold = p->theta_threshold; a.max_steps = p->max_steps;
     return env_attach(c, &o, seed);
 }
+int mi_env_cartpole_swing_create(mi_ctx* c, const mi_cartpole_swing_params* p, uint64_t seed) {
+    ARG(c && p, "null"); JOIN(c);
+    const EnvOps& o = CARTPOLE_SWING_ENV;
+    if (int r = env_check(c, o, p->max_steps, p->low, p->high)) return r;
+    ARG(p->x_threshold > 0, "mi_env_cartpole_swing_create: x_threshold must be positive (the reward divides by it)");      // (also refuses NaN)
+    CartPoleSwingArgs& a = c->env.args.cs;
+    for (int j = 0; j < 9; ++j) { a.low[j] = p->low[j]; a.high[j] = p->high[j]; }
+    a.x_threshold = p->x_threshold; a.max_steps = p->max_steps;
+    return env_attach(c, &o, seed);
+}
 int mi_env_mountain_car_create(mi_ctx* c, const mi_mountain_car_params* p, uint64_t seed) {
     ARG(c && p, "null"); JOIN(c);
     const EnvOps& o = MOUNTAIN_CAR_ENV;
@@ -137,7 +149,7 @@ int mi_env_mountain_car_create(mi_ctx* c, const mi_mountain_car_params* p, uint6
     a.goal_velocity = p->goal_velocity; a.max_steps = p->max_steps; a.sparse_rewards = p->sparse_rewards != 0;
     return env_attach(c, &o, seed);
 }
-#define ENV(c) ARG((c)->env.ops, "no env on this context (mi_env_cartpole_create / mi_env_mountain_car_create)")
+#define ENV(c) ARG((c)->env.ops, "no env on this context (mi_env_cartpole_create / mi_env_cartpole_swing_create / mi_env_mountain_car_create)")
 int mi_env_reset(mi_ctx* c) {
     ARG(c, "null"); JOIN(c); ENV(c);
     c->env.ops->reset(c->env, c->E, c->obsf, c->stream);

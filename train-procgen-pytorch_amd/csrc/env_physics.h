@@ -1,5 +1,5 @@
 // The physics of the device-resident envs, shared by their translation units (env_device.hip: the step / reset kernels and the mi_env_*
-// entries; env_resident.hip: the one-launch rollout).  An env is a physics struct (CartPole, MountainCar): `Args` (its kernel arguments),
+// entries; env_resident.hip: the one-launch rollout).  An env is a physics struct (CartPole, CartPoleSwing, MountainCar): `Args` (its kernel arguments),
 // `W` (state columns = observation width), `A` (actions), `args(DeviceEnv)` (its member of the context's union) and two device functions
 //     fresh(p, seed, e, episode, s)         the start of episode `episode` of env e into s[W]
 //     advance(p, s, act, &reward) -> ended  one step on s[W] in the host env's operation order; reward of this step
@@ -26,6 +26,21 @@ __device__ __forceinline__ void env_draw(const Args& p, unsigned long long seed,
     }
 }
 
+// The Euler step of Florian's cart-pole equations with the per-env parameters (tau = 0.02), in CartPoleVec.step's operation order: what
+// the cart-pole and the swing-up share.  Advances the four dynamic columns of s[9] in place.
+__device__ __forceinline__ void cartpole_euler(double* s, int act) {
+#pragma clang fp contract(off)
+    const double x = s[0], xd = s[1], th = s[2], thd = s[3], g = s[4], length = s[5], m_cart = s[6], m_pole = s[7], f_mag = s[8];
+    const double tau = 0.02;
+    const double force = (act == 0 ? -1.0 : 1.0) * f_mag;
+    const double ct = cos(th), st = sin(th);
+    const double pml = m_pole * length, total = m_pole + m_cart;
+    const double temp = (force + (pml * (thd * thd)) * st) / total;
+    const double thacc = (g * st - ct * temp) / (length * (4.0 / 3.0 - (m_pole * (ct * ct)) / total));
+    const double xacc = temp - ((pml * thacc) * ct) / total;
+    s[0] = x + tau * xd; s[1] = xd + tau * xacc; s[2] = th + tau * thd; s[3] = thd + tau * thacc;
+}
+
 // CartPoleVec (the reference's discrete_env/cartpole_pre_vec.py:214-262 on pre_vec_env.py:86-118): blocks 0..4 of an episode's
 // counters (18 words needed, 20 drawn); reward 1 every step.
 struct CartPole {
@@ -37,17 +52,31 @@ struct CartPole {
     }
     static __device__ __forceinline__ bool advance(const Args& p, double* s, int act, double* reward) {
 #pragma clang fp contract(off)
-        const double x = s[0], xd = s[1], th = s[2], thd = s[3], g = s[4], length = s[5], m_cart = s[6], m_pole = s[7], f_mag = s[8];
-        const double tau = 0.02;
-        const double force = (act == 0 ? -1.0 : 1.0) * f_mag;
-        const double ct = cos(th), st = sin(th);
-        const double pml = m_pole * length, total = m_pole + m_cart;
-        const double temp = (force + (pml * (thd * thd)) * st) / total;
-        const double thacc = (g * st - ct * temp) / (length * (4.0 / 3.0 - (m_pole * (ct * ct)) / total));
-        const double xacc = temp - ((pml * thacc) * ct) / total;
-        s[0] = x + tau * xd; s[1] = xd + tau * xacc; s[2] = th + tau * thd; s[3] = thd + tau * thacc;
+        cartpole_euler(s, act);
         *reward = 1.0;
         return (s[0] < -p.x_threshold) | (s[0] > p.x_threshold) | (s[2] < -p.theta_threshold) | (s[2] > p.theta_threshold);
+    }
+};
+
+// CartPoleSwingVec (discrete_env/cartpole_swing_pre_vec.py:195-239): the cart-pole's dynamics and start stream (the pole hangs down:
+// theta starts around pi, which is a matter of `low` / `high` alone), termination beyond +-x_threshold only -- no angle threshold --
+// and the reward of the post-step, pre-reset state: max(cos(theta), 0) * cos((x / x_threshold) * (pi / 2)).  The clamp is numpy's
+// `rt[rt < 0] = 0` (a NaN stays); a row that ends with the clamp on has cos(..) < 0 and yields -0.0, as on the host.
+struct CartPoleSwing {
+    using Args = CartPoleSwingArgs;
+    static constexpr int W = 9, A = 2;
+    static const Args& args(const DeviceEnv& d) { return d.args.cs; }
+    static __device__ __forceinline__ void fresh(const Args& p, unsigned long long seed, int e, long long episode, double* s) {
+        env_draw<W>(p, seed, e, episode, 0, s);
+    }
+    static __device__ __forceinline__ bool advance(const Args& p, double* s, int act, double* reward) {
+#pragma clang fp contract(off)
+        cartpole_euler(s, act);
+        double rt = cos(s[2]);
+        rt = rt < 0.0 ? 0.0 : rt;
+        const double rx = cos((s[0] / p.x_threshold) * (3.141592653589793 / 2.0));
+        *reward = rt * rx;
+        return (s[0] < -p.x_threshold) | (s[0] > p.x_threshold);
     }
 };
 
@@ -88,7 +117,7 @@ struct MountainCar {
     }
 };
 
-// the one-launch rollout of an env (env_resident.hip instantiates it for both structs; env_device.hip puts it into the env's table row)
+// the one-launch rollout of an env (env_resident.hip instantiates it for every struct; env_device.hip puts it into the env's table row)
 template <typename Env>
 MI_INTERNAL void env_rollout_resident(const DeviceEnv& d, const ResidentNet& net, const ResidentRings& ring, int E, int T, unsigned long long seed,
                                       hipStream_t st);

@@ -182,4 +182,5 @@ void env_rollout_resident(const DeviceEnv& d, const ResidentNet& net, const Resi
                            d.seed, seed, E, T);
 }
 template void env_rollout_resident<CartPole>(const DeviceEnv&, const ResidentNet&, const ResidentRings&, int, int, unsigned long long, hipStream_t);
+template void env_rollout_resident<CartPoleSwing>(const DeviceEnv&, const ResidentNet&, const ResidentRings&, int, int, unsigned long long, hipStream_t);
 template void env_rollout_resident<MountainCar>(const DeviceEnv&, const ResidentNet&, const ResidentRings&, int, int, unsigned long long, hipStream_t);

@@ -39,6 +39,10 @@ class _CartPoleParams(C.Structure):
                 ("max_steps", C.c_int32)]
 
 
+class _CartPoleSwingParams(C.Structure):
+    _fields_ = [("low", C.c_double * 9), ("high", C.c_double * 9), ("x_threshold", C.c_double), ("max_steps", C.c_int32)]
+
+
 class _MountainCarParams(C.Structure):
     _fields_ = [("low", C.c_double * 5), ("high", C.c_double * 5), ("left_boundary", C.c_double), ("max_speed", C.c_double),
                 ("force", C.c_double), ("goal_velocity", C.c_double), ("max_steps", C.c_int32), ("sparse_rewards", C.c_int32)]
@@ -65,7 +69,7 @@ EXPORTS = ("mi_last_error mi_create mi_destroy mi_sync mi_host_alloc mi_host_fre
            "mi_sae_create mi_sae_destroy mi_sae_param_count mi_sae_set_params mi_sae_get_params mi_sae_get_grads mi_sae_set_adam_state mi_sae_get_adam_state mi_sae_put_ring "
            "mi_sae_get_hidden mi_sae_get_logits mi_sae_step mi_sae_minibatch mi_sae_probe_minibatch mi_sae_optimizer_step mi_sae_debug_forward "
            "mi_ipl_minibatch mi_ipl_read_pred mi_predict_greedy mi_op_ipl_loss mi_op_ipl_greedy "
-           "mi_env_cartpole_create mi_env_mountain_car_create mi_env_reset mi_env_step mi_env_rollout mi_env_rollout_resident mi_env_get_state mi_env_set_state").split()
+           "mi_env_cartpole_create mi_env_cartpole_swing_create mi_env_mountain_car_create mi_env_reset mi_env_step mi_env_rollout mi_env_rollout_resident mi_env_get_state mi_env_set_state").split()
 
 
 def load_library():
@@ -271,7 +275,7 @@ class Engine:
         self._chk(self.lib.mi_read_field(self._ctx, C.c_int32(field), _fp(out), C.c_int64(out.size)))
         return out
 
-    # ------------------------------------------------------------------ device-resident envs (mi_env_*): cart-pole, mountain car
+    # ------------------------------------------------------------------ device-resident envs (mi_env_*): cart-pole, swing-up cart-pole, mountain car
     _env_width = 0          # columns of the env's state = the observation width: set by the create call from its params struct
 
     def _env_create(self, create, params, low, high, seed, *scalars):
@@ -284,6 +288,9 @@ class Engine:
 
     def env_cartpole_create(self, low, high, x_threshold, theta_threshold, max_steps, seed=0):
         self._env_create(self.lib.mi_env_cartpole_create, _CartPoleParams, low, high, seed, float(x_threshold), float(theta_threshold), int(max_steps))
+
+    def env_cartpole_swing_create(self, low, high, x_threshold, max_steps, seed=0):
+        self._env_create(self.lib.mi_env_cartpole_swing_create, _CartPoleSwingParams, low, high, seed, float(x_threshold), int(max_steps))
 
     def env_mountain_car_create(self, low, high, left_boundary, max_speed, force, goal_velocity, max_steps, sparse_rewards=True, seed=0):
         self._env_create(self.lib.mi_env_mountain_car_create, _MountainCarParams, low, high, seed, float(left_boundary), float(max_speed),

@@ -13,7 +13,8 @@ model_*.pth is reused and its newest checkpoint loaded -- the reference finds th
 `--detect_nan`.  Different on purpose: `--device` defaults to gpu and `cpu` is refused (there is no CPU fallback); config.yml is
 read relative to this file instead of the hard-coded GLOBAL_DIR of helper_local.py:28; new flags --precision, --rollout_groups, --device_env, --resident_rollout.
 `--env_name cartpole*` and `--env_name mountain_car` run the numpy restatements of the reference's pre-vectorised envs (CartPoleVec,
-MountainCarVec) with the serial step; `--device_env` keeps either env on the device (DeviceCartPole, DeviceMountainCar).  A --device_env
+MountainCarVec) with the serial step -- the exact name `cartpole_swing` the swing-up task (CartPoleSwingVec), every other cartpole* name the
+balance task; `--device_env` keeps the env on the device (DeviceCartPole, DeviceCartPoleSwing, DeviceMountainCar).  A --device_env
 run is not the host run's trajectory past the first episode reset: episode starts come from the device env's own Philox stream."""
 import os
 import sys
@@ -39,7 +40,7 @@ from agents.ppo import PPO
 from agents.ppo_pure import PPOPure
 from agents.sae import SAE, check_supported as sae_check_supported
 from agents.ipl import IPL, check_supported as ipl_check_supported
-from common.env.vec_envs import EnvGroups, SyntheticFrames, create_procgen_env, device_env_labels, vector_env
+from common.env.vec_envs import EnvGroups, SyntheticFrames, create_procgen_env, create_vector_env, device_env_labels, vector_env
 from common.logger import Logger, SimpleLogger
 from common.misc_util import set_global_seeds
 from common.model import ImpalaModel, MLPModel
@@ -178,8 +179,9 @@ def _one_env(env_name, n_envs, seed, A, args, hp, is_valid, ret_rms=None, num_th
     vec = vector_env(env_name)
     if vec is not None:
         # cart-pole: 9 observations -> MLPModel(9, ...), BASELINE config 1; mountain car: 5 observations, 3 actions -> MLPModel(5, ...);
-        # --device_env: the same env resident on the device (DeviceCartPole, DeviceMountainCar)
-        return vec.create(hp, is_valid, seed=seed, n_envs=n_envs, device=bool(getattr(args, "device_env", False)))
+        # the exact name cartpole_swing: the swing-up task on the cart-pole's 9 observations and 2 actions;
+        # --device_env: the same env resident on the device (DeviceCartPole, DeviceCartPoleSwing, DeviceMountainCar)
+        return create_vector_env(env_name, hp, is_valid, seed=seed, n_envs=n_envs, device=bool(getattr(args, "device_env", False)))
     return create_procgen_env(env_name=env_name, n_envs=n_envs, is_valid=is_valid, val_env_name=args.val_env_name,
                               start_level=args.start_level, num_levels=args.num_levels, distribution_mode=args.distribution_mode,
                               num_threads=num_threads or args.num_threads, paint_vel_info=hp.get("paint_vel_info", args.paint_vel_info),
