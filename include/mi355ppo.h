@@ -275,6 +275,23 @@ int mi_minibatch(mi_ctx* ctx, const int64_t* idx, int32_t n_idx, int32_t n_globa
  * a rank's share of a global minibatch is ~1/R of it: this keeps its launches at single-GPU size. */
 int mi_minibatch_multi(mi_ctx* ctx, const int64_t* idx, int32_t n_idx, const int32_t* seg_n, int32_t n_seg, int32_t n_global,
                        const mi_hparams* hp);
+/* (new, opt-in: train.py --fused_update, PPO(fused_update=True), Engine.minibatch_fused) mi_minibatch_multi's pass for an MLP context in
+ * TWO kernel launches behind the index pull instead of the chain's twenty-odd (csrc/mlp_fused.hip): launch 1 takes a tile of 16
+ * gathered samples per workgroup through the gather, the MLP and the heads on the fp32 matrix cores with the activations in LDS, the
+ * per-sample loss and dY, and the data gradients back through the layers, and leaves every layer's input and output gradient for all
+ * rows in global memory; launch 2 sums every layer's weight and bias gradient tile by tile over all rows in row order into the flat
+ * gradient buffer (+=, as the chain) and derives each segment's statistics row and log record.  No float atomics, no grid barrier: two
+ * calls on the same inputs give the same bits.  The contract is mi_minibatch_multi's (n_seg == 1 is mi_minibatch): same index staging,
+ * same log_count / statistics ring / loss log bookkeeping; mi_optimizer_step, mi_get_grads and mi_loss_log_read work after it as after
+ * the chain; gradients and records equal the chain's up to fp32 summation order.
+ * Refused, each message starting with "mi_minibatch_fused: ", before any launch and before the loss log, the index ring or the
+ * gradient buffer change: arch other than MI_ARCH_MLP; a recurrent context (mi_set_gru); multirank mode other than 0; an armed or
+ * in-flight gradient exchange or an initialised communicator; x_entropy_coef != 0 or fs_coef != 0 (the batch-level terms need the
+ * two-phase loss, which stays on the chain); mlp_depth outside 2 .. 16, mlp_width or out_dim not a multiple of 16 or above 512,
+ * n_actions above 15, obs_dim above 16; n_idx < 1 or > max_batch, n_global < 1, n_seg outside 1 .. 16 (the chain's limit), a segment of no
+ * samples, segments that do not add up to n_idx, an index outside [0, T * E); a pending multirank minibatch; a full loss log. */
+int mi_minibatch_fused(mi_ctx* ctx, const int64_t* idx, int32_t n_idx, const int32_t* seg_n, int32_t n_seg, int32_t n_global,
+                       const mi_hparams* hp);
 /* clip_grad_norm_ + Adam.step + zero_grad (agents/ppo.py:174-176); adam_step = 1-based step count */
 int mi_optimizer_step(mi_ctx* ctx, float lr, float max_grad_norm, int32_t adam_step, float* grad_norm_out);
 int mi_loss_log_read(mi_ctx* ctx, float* out, int32_t max_records, int32_t* n_records, int32_t reset);

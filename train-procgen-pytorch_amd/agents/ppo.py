@@ -57,6 +57,9 @@ class PPO(BaseAgent):
         self.joint_rollouts = bool(kwargs.get("joint_rollouts", True))              # (new) training + validation rollout in one host loop (train())
         # (new) train.py --resident_rollout: a device-resident env's rollout as ONE launch (mi_env_rollout_resident) instead of the chain
         self.resident_rollout = bool(kwargs.get("resident_rollout", False))
+        # (new) train.py --fused_update: every minibatch pass of optimize() as TWO launches (mi_minibatch_fused, csrc/mlp_fused.hip) instead of
+        # the chain's twenty-odd; MLP policies on one rank without batch-level loss terms (checked below, once the collective is known)
+        self.fused_update = bool(kwargs.get("fused_update", False))
         # train.py --detect_nan (reference: autograd anomaly mode + a NaN hook on every module's output, train.py:123-124,234-250):
         # here the policy outputs of every rollout step, every minibatch's loss record and every gradient norm are checked
         self.detect_nan = bool(kwargs.get("detect_nan", False))
@@ -67,6 +70,17 @@ class PPO(BaseAgent):
         self.coll = Collective()
         if fs_coef != 0. and self.coll.active and policy.arch != "impala":
             fs_coef = self.fs_coef = 0.                            # (no feature-sparsity term without the IMPALA feature map, model.py:976-977)
+        if self.fused_update:
+            if policy.arch != "mlp":
+                raise ValueError(f"fused_update needs an mlpmodel policy (architecture: mlpmodel), not {policy.arch!r}: IMPALA minibatches stay on the chain of launches")
+            if policy.is_recurrent():
+                raise ValueError("fused_update does not support a recurrent policy")
+            if self.coll.active:
+                raise ValueError("fused_update runs on one rank only (WORLD_SIZE > 1: an active collective)")
+            if x_entropy_coef != 0:
+                raise ValueError("fused_update needs x_entropy_coef == 0 (the batch-level term needs the two-phase loss of the chain)")
+            if fs_coef != 0:
+                raise ValueError("fused_update needs fs_coef == 0 (the batch-level term needs the two-phase loss of the chain)")
         self.n_envs_global = n_envs * self.coll.world
         n_total = n_steps * self.n_envs_global
         batch_size = n_total // n_minibatch
@@ -230,7 +244,9 @@ class PPO(BaseAgent):
                 # (mi_allreduce_arm); with a per-minibatch statistics exchange the backward pass runs inside minibatch_finish (below)
                 if self._arm and nxt is not None and nxt[0] == "step":
                     eng.allreduce_arm()
-                if len(seg_n) > 1 or merge:
+                if self.fused_update:                        # one call covers the single and the merged-accumulation case
+                    eng.minibatch_fused(local, seg_n, n_global, hp)
+                elif len(seg_n) > 1 or merge:
                     eng.minibatch_multi(local, seg_n, n_global, hp)
                 else:
                     eng.minibatch(local, n_global, hp)

@@ -1691,6 +1691,58 @@ int mi_minibatch_multi(mi_ctx* c, const int64_t* idx, int32_t n, const int32_t* 
     return minibatch_impl(c, idx, n, seg_n, n_seg, n_global, hp);
 }
 
+// The same pass for an MLP context as two launches behind the index pull (mlp_fused.hip): mi_minibatch_multi's contract, opt-in.  Every
+// refusal comes before any launch and before log_count, the index ring or the gradient buffer change.
+static int fused_alloc(mi_ctx* c) {
+    if (c->fu_terms) return 0;
+    const size_t NB = c->NB;
+    DevPool& m = c->pool; DevPool::Group all(m);
+    for (size_t l = 0; l + 1 < c->mlp.size(); ++l) HIPC(m.dev(&c->fu_g[l], NB * c->mlp[l].out));
+    HIPC(m.dev(&c->fu_terms, NB * 32));
+    all.keep = true;
+    return 0;
+}
+#define FUSED_ARG(cond, msg) do { if (!(cond)) return fail(-1, std::string("mi_minibatch_fused: ") + msg); } while (0)
+int mi_minibatch_fused(mi_ctx* c, const int64_t* idx, int32_t n, const int32_t* seg_n, int32_t n_seg, int32_t n_global, const mi_hparams* hp) {
+    FUSED_ARG(c && hp && idx && seg_n, "null argument"); JOIN(c);
+    FUSED_ARG(c->cfg.arch == MI_ARCH_MLP, "the context's arch must be MI_ARCH_MLP (IMPALA contexts use mi_minibatch)");
+    FUSED_ARG(!c->gru_on, "a recurrent context (mi_set_gru) is not supported");
+    FUSED_ARG(c->multirank == 0, "multirank mode must be 0");
+    FUSED_ARG(!c->ar_armed && !c->ar_inflight && !c->comm, "an armed or in-flight gradient exchange or an initialised communicator is not supported");
+    FUSED_ARG(hp->x_entropy_coef == 0.f && hp->fs_coef == 0.f, "x_entropy_coef and fs_coef must be 0 (the batch-level terms need the two-phase loss of mi_minibatch)");
+    { const std::string why = resident_shape_refusal(c); FUSED_ARG(why.empty(), why); }
+    FUSED_ARG(c->cfg.obs_dim <= 16, "obs_dim must be at most 16");
+    FUSED_ARG(n >= 1 && n <= c->NB, "n_idx must be in [1, max_batch]"); FUSED_ARG(n_global >= 1, "n_global must be at least 1");
+    FUSED_ARG(n_seg >= 1 && n_seg <= MI_MAX_SEG, "1 .. 16 segments");
+    { long long tot = 0; for (int k = 0; k < n_seg; ++k) { FUSED_ARG(seg_n[k] >= 1, "every segment needs at least one sample"); tot += seg_n[k]; } FUSED_ARG(tot == n, "segments do not add up to n_idx"); }
+    const int64_t TE = (int64_t)c->T * c->E;
+    for (int k = 0; k < n; ++k) FUSED_ARG(idx[k] >= 0 && idx[k] < TE, "minibatch index out of range");
+    FUSED_ARG(c->pending_n < 0, "previous multirank minibatch not finished");
+    FUSED_ARG(c->log_count + n_seg <= c->log_cap, "loss log full: call mi_loss_log_read(reset=1)");
+    if (int r = fused_alloc(c)) return r;
+    if (int r = stage_indices(c, n, [&](int32_t* h) { for (int k = 0; k < n; ++k) h[k] = (int32_t)idx[k]; }, false)) return r;
+    c->prof.phase = 1;
+    c->prof.sample_now = (c->prof.mb_count++ % c->prof.period) == 0;
+    c->rec_last = false;
+    const size_t L = c->mlp.size();
+    FusedNet f = {};
+    f.net = resident_net(c);
+    for (size_t l = 0; l < L; ++l) { f.act[l] = c->mlp_act[l]; f.g[l] = l + 1 < L ? c->fu_g[l] : c->dfeat; }
+    f.act[L] = c->feat;
+    f.obs = c->obsf; f.obs_dim = c->cfg.obs_dim; f.dYh = c->dY; f.terms = c->fu_terms;
+    LossArgs a = loss_args(c, n, n_global, hp);
+    SegTab st{};
+    st.n_seg = n_seg;
+    for (int k = 0; k < n_seg; ++k) st.start[k + 1] = st.start[k] + seg_n[k];
+    a.stats = c->stats_ring + (size_t)c->log_count * 32;
+    launch_mlp_fused_pass(f, a, n, c->stream);
+    launch_mlp_fused_reduce(f, a, st, n, c->grads, c->stats_ring + (size_t)c->log_count * 32, c->loss_log + (size_t)c->log_count * 8, c->stream);
+    c->ring_args = a;
+    c->log_count += n_seg;
+    HIPC(hipGetLastError()); NETCHK(c);
+    return 0;
+}
+
 // Global minibatch positions of the NEXT mi_minibatch's rows (ascending; the rank's share of a global minibatch keeps the global order):
 // needed when fs_coef != 0 on more than one rank -- ties between equal column maxima go to the row that comes first globally.
 int mi_minibatch_positions(mi_ctx* c, const int32_t* gpos, int32_t n) {

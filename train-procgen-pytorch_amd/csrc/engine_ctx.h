@@ -90,6 +90,21 @@ struct ResidentNet {
     long long w_off[RES_MAX_LAYERS], b_off[RES_MAX_LAYERS], wh_off, bh_off;
 };
 struct ResidentRings { float* obs; int32_t* act; float *logp, *value, *rew, *done; };
+// What the fused MLP minibatch pass (mlp_fused.hip, mi_minibatch_fused) reads and leaves behind for its second launch: the network as
+// the resident rollout sees it (same limits), the observation ring, and per-row buffers of max_batch rows -- act[l] the input of layer
+// l (act[0]: the gathered observations, act[n_layers]: the embedder output), g[l] the gradient of layer l's output, dYh the heads'
+// gradient [n][A + 1], terms the per-sample loss terms [n][32].
+struct FusedNet {
+    ResidentNet net;
+    const float* obs; int obs_dim;
+    float* act[RES_MAX_LAYERS + 1];
+    float* g[RES_MAX_LAYERS];
+    float *dYh, *terms;
+};
+void launch_mlp_fused_pass(const FusedNet& f, const LossArgs& a, int n, hipStream_t st);
+// segment k's statistics row stats_base + 32 k and record log_base + 8 k; grads += the pass's gradient
+void launch_mlp_fused_reduce(const FusedNet& f, const LossArgs& a, const SegTab& seg, int n, float* grads, float* stats_base, float* log_base,
+                             hipStream_t st);
 // One constant row per env: how the messages of its create call name it, its state width (= observation width) and action count, what
 // mi_env_step answers to an action out of range, and the launchers of its step, reset and resident rollout kernels.
 struct EnvOps {
@@ -210,6 +225,9 @@ struct mi_ctx {
     // minibatch's pred / reward, the loss kernel's fp64 block partials
     int32_t* ipl_idx2 = nullptr; float *ipl_nv = nullptr, *ipl_gnext = nullptr, *ipl_pred = nullptr, *ipl_rew = nullptr; double* ipl_partial = nullptr;
     int ipl_last_n = 0;
+    // the fused MLP pass (mi_minibatch_fused; allocated by its first call, max_batch rows each): the output gradients of the layers below the
+    // last (the last layer's is dfeat) and the per-sample loss terms
+    float *fu_g[RES_MAX_LAYERS] = {}, *fu_terms = nullptr;
     DeviceEnv env;                    // the device-resident env, if any (env_device.hip)
     struct mi_sae* sae = nullptr;     // the sparse-autoencoder agent's state (sae.hip: mi_sae_create; released by mi_sae_destroy or mi_destroy)
     // Every device buffer, pinned buffer and event above belongs to a pool (declared last: destroyed first, while the pointers it
@@ -218,6 +236,30 @@ struct mi_ctx {
 };
 
 static inline char* obs_ring(mi_ctx* c) { return c->frames ? (char*)c->frames : (char*)c->obsf; }      // rollout observations [(T+1)][E]: uint8 frames or fp32 rows
+
+// The MLP shapes the 16-row-tile kernels take (res_layer.h: the resident rollout and the fused minibatch pass have the same limits): the
+// words of the first limit the context's network breaks, or "" -- the caller puts its entry's name in front.
+static inline std::string resident_shape_refusal(const mi_ctx* c) {
+    const size_t L = c->mlp.size();
+    if (!(L >= 2 && L <= RES_MAX_LAYERS)) return "mlp_depth must be at least 2 and at most " + std::to_string(RES_MAX_LAYERS);
+    if (!(c->cfg.mlp_width % 16 == 0 && c->cfg.mlp_width <= RES_MAX_WIDTH)) return "mlp_width must be a multiple of 16 and at most " + std::to_string(RES_MAX_WIDTH);
+    if (!(c->H % 16 == 0 && c->H <= RES_MAX_WIDTH)) return "out_dim must be a multiple of 16 and at most " + std::to_string(RES_MAX_WIDTH);
+    if (!(c->A + 1 <= 16)) return "n_actions must be at most 15";
+    return "";
+}
+// the network of a context that passed resident_shape_refusal, as those kernels read it
+static inline ResidentNet resident_net(const mi_ctx* c) {
+    ResidentNet net = {};
+    const size_t L = c->mlp.size();
+    net.params = c->params; net.n_layers = (int)L; net.H = c->H; net.lse = c->lse;
+    for (size_t l = 0; l < L; ++l) {
+        const Linear& m = c->mlp[l];
+        net.in[l] = m.in; net.out[l] = m.out; net.w_off[l] = m.w_off; net.b_off[l] = m.b_off;
+        net.vec[l] = m.in % 16 == 0 && m.w_off % 4 == 0;
+    }
+    net.wh_off = c->wh_off; net.bh_off = c->bh_off; net.heads_vec = c->wh_off % 4 == 0;      // (H is a multiple of 16)
+    return net;
+}
 
 // ------------------------------------------------------------------------------------------ engine.hip functions the op code calls
 MI_INTERNAL std::string net_err_take(mi_ctx* c);                 // (the network program also runs on the env-group worker threads: guarded)

@@ -189,21 +189,10 @@ int mi_env_rollout_resident(mi_ctx* c, uint64_t seed) {
     ARG(c, "null"); JOIN(c); ENV(c);
     const std::string f = "mi_env_rollout_resident: ";
     ARG(!c->gru_on, f + "a recurrent context (mi_set_gru) is not supported");
-    const size_t L = c->mlp.size();
-    ARG(L >= 2 && L <= RES_MAX_LAYERS, f + "mlp_depth must be at least 2 and at most " + std::to_string(RES_MAX_LAYERS));
-    ARG(c->cfg.mlp_width % 16 == 0 && c->cfg.mlp_width <= RES_MAX_WIDTH, f + "mlp_width must be a multiple of 16 and at most " + std::to_string(RES_MAX_WIDTH));
-    ARG(c->H % 16 == 0 && c->H <= RES_MAX_WIDTH, f + "out_dim must be a multiple of 16 and at most " + std::to_string(RES_MAX_WIDTH));
-    ARG(c->A + 1 <= 16, f + "n_actions must be at most 15");
+    { const std::string why = resident_shape_refusal(c); ARG(why.empty(), f + why); }
     const DeviceEnv& d = c->env;
     ARG(c->cfg.obs_dim == d.ops->width && c->cfg.obs_dim <= 16, f + "obs_dim must be the env's state width");
-    ResidentNet net = {};
-    net.params = c->params; net.n_layers = (int)L; net.H = c->H; net.lse = c->lse;
-    for (size_t l = 0; l < L; ++l) {
-        const Linear& m = c->mlp[l];
-        net.in[l] = m.in; net.out[l] = m.out; net.w_off[l] = m.w_off; net.b_off[l] = m.b_off;
-        net.vec[l] = m.in % 16 == 0 && m.w_off % 4 == 0;
-    }
-    net.wh_off = c->wh_off; net.bh_off = c->bh_off; net.heads_vec = c->wh_off % 4 == 0;      // (H is a multiple of 16)
+    const ResidentNet net = resident_net(c);
     const ResidentRings ring = {c->obsf, c->act, c->logp, c->value, c->rew, c->done};
     c->prof.phase = 0;
     d.ops->rollout(d, net, ring, c->E, c->T, seed, c->stream);

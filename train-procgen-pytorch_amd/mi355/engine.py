@@ -63,7 +63,7 @@ def lib_path():
 EXPORTS = ("mi_last_error mi_create mi_destroy mi_sync mi_host_alloc mi_host_free mi_host_register mi_host_unregister mi_param_count mi_set_params "
            "mi_get_params mi_copy_params mi_get_grads mi_set_adam_state mi_get_adam_state mi_put_obs mi_get_obs mi_put_step "
            "mi_put_policy_outputs mi_read_field mi_write_field mi_policy_step mi_rollout_step mi_rollout_groups mi_rollout_lane_info mi_rollout_submit mi_rollout_wait mi_predict_staged mi_value_saliency mi_commit_staged mi_set_gru mi_rec_state mi_get_hidden mi_rec_begin mi_get_hidden_ring mi_forward_rec mi_forward mi_compute_estimates "
-           "mi_adv_stats mi_adv_apply mi_minibatch mi_minibatch_multi mi_optimizer_step mi_loss_log_read mi_device_ptr "
+           "mi_adv_stats mi_adv_apply mi_minibatch mi_minibatch_multi mi_minibatch_fused mi_optimizer_step mi_loss_log_read mi_device_ptr "
            "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_op_fc_bf16 mi_op_reduce mi_op_adam mi_op_adv_merge mi_op_heads mi_op_sample mi_op_ppo_loss mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_gru_step mi_debug_step_latency mi_debug_lane_probe mi_debug_live_resources "
            "mi_gru_train mi_minibatch_rec mi_get_gru mi_get_gru_grads mi_get_gru_adam_state mi_set_gru_adam_state mi_debug_gru_seq "
            "mi_sae_create mi_sae_destroy mi_sae_param_count mi_sae_set_params mi_sae_get_params mi_sae_get_grads mi_sae_set_adam_state mi_sae_get_adam_state mi_sae_put_ring "
@@ -560,6 +560,14 @@ class Engine:
         idx = np.ascontiguousarray(idx, dtype=np.int64)
         seg = np.ascontiguousarray(seg_n, dtype=np.int32)
         self._chk(self.lib.mi_minibatch_multi(self._ctx, _fp(idx), C.c_int32(idx.size), seg.ctypes.data_as(C.c_void_p), C.c_int32(seg.size),
+                                              C.c_int32(n_global), C.byref(hp)))
+
+    def minibatch_fused(self, idx, seg_n, n_global, hp):
+        """minibatch_multi's pass of an MLP engine in two kernel launches (mi_minibatch_fused, csrc/mlp_fused.hip): same bookkeeping, gradients and
+        records equal up to fp32 summation order.  One segment (seg_n = [len(idx)]) is minibatch()."""
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        seg = np.ascontiguousarray(seg_n, dtype=np.int32)
+        self._chk(self.lib.mi_minibatch_fused(self._ctx, _fp(idx), C.c_int32(idx.size), seg.ctypes.data_as(C.c_void_p), C.c_int32(seg.size),
                                               C.c_int32(n_global), C.byref(hp)))
 
     def minibatch_finish(self):

@@ -130,6 +130,8 @@ def add_training_args(p):
                    help="cartpole* and mountain_car only: the env lives on the device (state, physics, resets, reward and done in HBM) and a whole rollout is one call with no host round trip per step; episode starts come from the device env's own Philox stream, not numpy's.  Non-recurrent MLP policies, one GPU, algo ppo / ppo-pure")
     p.add_argument('--resident_rollout', action="store_true",
                    help="with --device_env: the whole rollout (T + 1 policy steps, T env steps) is ONE kernel launch -- a workgroup carries 16 envs through every step, the MLP on the matrix cores with activations in LDS (mi_env_rollout_resident).  Same actions, rewards, dones and observations as the default chain of launches; values and log-probabilities differ by fp32 summation order.  mlp_width / latent_size multiples of 16 up to 512")
+    p.add_argument('--fused_update', action="store_true",
+                   help="MLP policies (architecture: mlpmodel): every minibatch pass of the update is TWO kernel launches -- a workgroup carries 16 samples through the gather, the MLP on the matrix cores with activations in LDS, the loss and the data gradients; a second launch sums the weight gradients in row order and derives the loss records (mi_minibatch_fused).  Same gradients and loss records as the default chain of launches up to fp32 summation order.  Non-recurrent, one GPU, algo ppo / ppo-pure, x_entropy_coef = fs_coef = 0; mlp_width / latent_size multiples of 16 up to 512.  Does not need --device_env")
     p.add_argument('--x_entropy_coef', type=float, default=None)
     p.add_argument('--algo', type=str, default=None, choices=['ppo', 'ppo-pure', 'sae', 'IPL'],
                    help="overrides the set's `algo`: ppo = the reference's agents/ppo.py (a recurrent policy's GRU stays frozen), ppo-pure = agents/ppo_pure.py (a recurrent policy is trained through its GRU with BPTT; single GPU), sae = agents/sae.py (a sparse autoencoder on the block-3 features of the trained IMPALA policy given by --model_file, then a linear probe on its codes; single GPU, use --param_name sae), IPL = agents/IPL.py (non-recurrent, single GPU; sets hard-500-ipl and ipl_cartpole)")
@@ -247,6 +249,26 @@ def check_device_env(env_name, hp, algo):
         raise NotImplementedError("--device_env with algo: sae is not supported: the sparse-autoencoder agent acts on IMPALA frames")
 
 
+def check_fused_update(hp, algo):
+    """--fused_update covers a non-recurrent MLP policy on one GPU under algo ppo / ppo-pure with no batch-level loss term."""
+    if hp.get("architecture", "impala") != "mlpmodel":
+        raise NotImplementedError(f"--fused_update with architecture {hp.get('architecture', 'impala')} is not supported: the fused minibatch pass is the MLP's (architecture: mlpmodel)")
+    if hp.get("recurrent", False):
+        raise NotImplementedError("--fused_update with recurrent: True is not supported: the fused minibatch pass runs no GRU")
+    if int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        raise NotImplementedError(f"--fused_update runs on a single GPU: WORLD_SIZE = {os.environ['WORLD_SIZE']} is not supported")
+    if algo == "IPL":
+        raise NotImplementedError("--fused_update with algo: IPL is not supported: IPL's minibatch is three forward and two backward passes of its own")
+    if algo == "sae":
+        raise NotImplementedError("--fused_update with algo: sae is not supported: the sparse-autoencoder agent trains no policy")
+    if algo not in ("ppo", "ppo-pure"):
+        raise NotImplementedError(f"--fused_update with algo: {algo} is not supported: only algo ppo and ppo-pure")
+    if float(hp.get("x_entropy_coef", 0.) or 0.) != 0.:
+        raise NotImplementedError(f"--fused_update with x_entropy_coef = {hp['x_entropy_coef']} is not supported: the batch-level term needs the two-phase loss of the default update")
+    if float(hp.get("fs_coef", 0.) or 0.) != 0.:
+        raise NotImplementedError(f"--fused_update with fs_coef = {hp['fs_coef']} is not supported: the batch-level term needs the two-phase loss of the default update")
+
+
 def train_ppo(args):
     hp = merge_hyperparameters(get_hyperparams(args.param_name), args)
     env_name = hp.get("env_name", args.env_name)
@@ -263,6 +285,9 @@ def train_ppo(args):
         if not getattr(args, "device_env", False):
             raise NotImplementedError("--resident_rollout needs --device_env: the one-launch rollout runs the device-resident env")
         hp["resident_rollout"] = True
+    if getattr(args, "fused_update", False):                # (an opt-in of the MLP update, with or without --device_env: reaches the agent as a hyper-parameter)
+        check_fused_update(hp, algo)
+        hp["fused_update"] = True
     if algo == "IPL":                                       # everything outside the built scope, by name, before any engine exists
         hp["learned_gamma"] = bool(hp.get("learned_gamma", False)) or bool(getattr(args, "learned_gamma", False))
         ipl_check_supported(hp, use_greedy_env=bool(getattr(args, "use_greedy_env", False)))
@@ -310,6 +335,8 @@ def train_ppo(args):
     print(f"rollout: {n_groups} pipelined env groups" if n_groups > 1 else
           "rollout: device-resident env, one kernel launch per rollout" if getattr(env, "on_device", False) and hp.get("resident_rollout") else
           "rollout: device-resident env, one call per rollout" if getattr(env, "on_device", False) else "rollout: serial steps")
+    print("update: fused MLP minibatch pass, two kernel launches per minibatch (--fused_update)" if hp.get("fused_update") else
+          "update: one chain of launches per minibatch")
     logdir, model_file = create_logdir_train(args.model_file, env_name, args.exp_name, args.seed, f'__rank_{rank}' if world > 1 and rank > 0 else '')
     np.save(os.path.join(logdir, "hyperparameters.npy"), hp)
     print(f'Logging to {logdir}')
