@@ -180,6 +180,22 @@ int mi_env_rollout(mi_ctx* ctx, uint64_t seed);
  * fp32 summation order only.  Asynchronous on the context's stream.  Refused by name, before anything is written: no env on the context,
  * a context with a GRU set, mlp_depth above 16, mlp_width or out_dim not a multiple of 16 or above 512, more than 15 actions. */
 int mi_env_rollout_resident(mi_ctx* ctx, uint64_t seed);
+/* The evaluation of the context's policy on its env as ONE launch: every env runs exactly `episodes` (K) whole episodes on the resident
+ * rollout's skeleton (16 envs per workgroup, the MLP on the matrix cores, the env step in fp64) and the per-episode records stay on the
+ * device until the call copies them out.  Episode i (0 .. K - 1) of env e starts at the reset stream's episode first_episode + i of env e
+ * (the create call's seed) or, with `starts` [E][K][W], at row starts[e][i]; it ends as in mi_env_step: the env's own termination or
+ * n_steps == max_steps.  Step index t counts an env's steps since the launch began.  greedy == 0: the rollout's sampler, the uniform of
+ * (seed, t * E + e) and the inverse CDF on the twice-normalised log-probabilities; greedy != 0: the first maximum of those
+ * log-probabilities (mi_predict_greedy's rule; `seed` is unused).  value_from_logits contexts are allowed in both modes.
+ * Records, [E][K] each (any output may be NULL): ret = the fp64 sum of the env's fp64 rewards in step order; length; terminated = the
+ * env's own flag at the last step (0 for a truncation); value0 = the value head at the episode's first observation; start_out [E][K][W] =
+ * the state the episode began in (the parameter columns it was drawn with).
+ * A pure function of the parameters, the env's arguments and seed, first_episode, episodes, seed, greedy and starts: the env's state /
+ * n_steps / episode and every ring are neither read nor written, so a training run may call it between two iterations.  Synchronises.
+ * Refused by name, before any launch or allocation: no env on the context, a context with a GRU set, the shapes mi_env_rollout_resident
+ * refuses, episodes < 1, episodes * max_steps > 2^20 (call again with another first_episode), first_episode < 1, a NaN in starts. */
+int mi_env_evaluate(mi_ctx* ctx, int32_t episodes, uint64_t seed, int32_t greedy, int64_t first_episode, const double* starts /* may be NULL */,
+                    double* ret, int32_t* length, int32_t* terminated, float* value0, double* start_out);
 int mi_env_get_state(mi_ctx* ctx, double* state /* E x W */, int32_t* n_steps, int64_t* episode);
 int mi_env_set_state(mi_ctx* ctx, const double* state, const int32_t* n_steps, const int64_t* episode);
 

@@ -340,6 +340,30 @@ class PPO(BaseAgent):
         storage._hidden[T] = hidden_state                        # store_last: value[T] and the observations are already in the device ring
         return engine.get_obs(T), hidden_state, storage._done[T - 1].copy()
 
+    def evaluate(self, episodes=10, greedy=False, valid=False, seed=None, starts=None):
+        """Every env of `self.env` (valid: `self.env_valid`, on the validation twin with the current parameters) runs `episodes` WHOLE
+        episodes of the current policy in one kernel launch (Engine.env_evaluate) -> the record dict (ret, length, terminated, value0,
+        start) plus the statistics of common.logger.evaluation_stats.  greedy: arg-max actions instead of sampled ones; seed: the
+        sampler's (default: this iteration's rollout seed); starts (E, K, W): planted start states.  The env's own state and the rollout
+        rings are left alone, so train() continues on the same trajectory.  Device-resident envs only."""
+        from common.logger import evaluation_stats
+        env, engine = (self.env_valid, self.engine_valid) if valid else (self.env, self.engine)
+        if env is None or engine is None:
+            raise ValueError("evaluate(valid=True) needs a validation env and storage (env_valid, storage_valid)")
+        if not getattr(env, "on_device", False):
+            raise NotImplementedError("evaluate() runs whole episodes on a device-resident env: build the env with --device_env "
+                                      "(create_vector_env(..., device=True)); a host env is not supported")
+        if self.policy.is_recurrent():
+            raise NotImplementedError("a device-resident env with a recurrent policy is not supported")
+        if env.engine is not engine:                             # first use on this lane: the env is created in this engine's context
+            env.attach_engine(engine)
+            env.reset()
+        if valid:
+            engine.copy_params_from(self.engine)                 # device to device: the twin evaluates the current policy
+        out = engine.env_evaluate(episodes, seed=self.seed * 1000003 + self._iter if seed is None else seed, greedy=greedy, starts=starts)
+        out.update(evaluation_stats(out["ret"], out["length"], env.max_steps))
+        return out
+
     def _collect_pipelined(self, env, engine, storage, obs, hidden_state, done):
         """The same T steps + bootstrap step with the env groups of `env.env_groups` as independent chains (mi_rollout_submit /
         mi_rollout_wait): while the host waits for / steps group g, the other groups' frame uploads and forward passes run on

@@ -49,6 +49,22 @@ class _EpisodeTracker:
                 mean(l[r > 0]) if len(r) else float("nan"), self.true_mean]
 
 
+EVALUATION_KEYS = EPISODE_KEYS[:-1]      # balanced_mean_rewards needs the env's true mean reward, which an evaluation does not have
+
+
+def evaluation_stats(ret, length, max_steps):
+    """The episode statistics of an evaluation (Engine.env_evaluate, PPO.evaluate) over ALL its episodes -> dict keyed by EVALUATION_KEYS,
+    the quantities of _EpisodeTracker.stats() / SimpleLogger.STAT_NAMES without the 40-episode window: max / mean / median / min return,
+    max / mean / min length, mean timeout (length == max_steps) and the mean length of the episodes with a positive return (NaN if none).
+    ret, length: arrays of one shape, e.g. (E, K)."""
+    r, l = np.asarray(ret, np.float64).reshape(-1), np.asarray(length, np.float64).reshape(-1)
+    if r.size == 0 or r.size != l.size:
+        raise ValueError(f"evaluation_stats: {r.size} returns and {l.size} lengths (one of each per episode, at least one episode)")
+    pos = l[r > 0]
+    vals = [r.max(), r.mean(), np.median(r), r.min(), l.max(), l.mean(), l.min(), (l == max_steps).mean(), pos.mean() if pos.size else np.nan]
+    return dict(zip(EVALUATION_KEYS, (float(v) for v in vals)))
+
+
 class Logger(object):
     def __init__(self, n_envs, logdir, use_wandb=False, has_vq=False, algo="ppo", greedy=False):
         self.n_envs, self.logdir, self.use_wandb = n_envs, logdir, use_wandb

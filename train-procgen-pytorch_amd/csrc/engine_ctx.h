@@ -1,5 +1,5 @@
 // Internal header of the engine's translation units (engine.hip: context, network program, C ABI; engine_ops.hip: the op-level
-// and debug entry points that only tests and micro-benchmarks call; env_device.hip: the device-resident envs and their mi_env_* entries; env_resident.hip: their one-launch rollout).  It holds what both need and nothing else: the context, the error
+// and debug entry points that only tests and micro-benchmarks call; env_device.hip: the device-resident envs and their mi_env_* entries; env_resident.hip: their one-launch rollout; env_evaluate.hip: their one-launch evaluation).  It holds what both need and nothing else: the context, the error
 // plumbing, and the few engine.hip functions the op code calls.
 #pragma once
 #include "common.h"
@@ -90,6 +90,9 @@ struct ResidentNet {
     long long w_off[RES_MAX_LAYERS], b_off[RES_MAX_LAYERS], wh_off, bh_off;
 };
 struct ResidentRings { float* obs; int32_t* act; float *logp, *value, *rew, *done; };
+// What the evaluation kernel (env_evaluate.hip, mi_env_evaluate) reads and writes beside the network: the planted episode starts
+// [E][K][W] (null: every episode starts from the reset stream) and one record per env and episode, [E][K] each, start [E][K][W].
+struct EvalRecords { const double* starts; double* ret; int32_t *length, *terminated; float* value0; double* start; };
 // What the fused MLP minibatch pass (mlp_fused.hip, mi_minibatch_fused) reads and leaves behind for its second launch: the network as
 // the resident rollout sees it (same limits), the observation ring, and per-row buffers of max_batch rows -- act[l] the input of layer
 // l (act[0]: the gathered observations, act[n_layers]: the embedder output), g[l] the gradient of layer l's output, dYh the heads'
@@ -106,7 +109,7 @@ void launch_mlp_fused_pass(const FusedNet& f, const LossArgs& a, int n, hipStrea
 void launch_mlp_fused_reduce(const FusedNet& f, const LossArgs& a, const SegTab& seg, int n, float* grads, float* stats_base, float* log_base,
                              hipStream_t st);
 // One constant row per env: how the messages of its create call name it, its state width (= observation width) and action count, what
-// mi_env_step answers to an action out of range, and the launchers of its step, reset and resident rollout kernels.
+// mi_env_step answers to an action out of range, and the launchers of its step, reset, resident rollout and evaluation kernels.
 struct EnvOps {
     const char *entry, *columns, *actions, *action_range;
     int width, n_actions;
@@ -115,6 +118,10 @@ struct EnvOps {
     void (*reset)(const DeviceEnv& d, int E, float* obs, hipStream_t st);
     // a whole rollout in one launch (mi_env_rollout_resident): what T + 1 policy steps and T env steps leave in the rings and the env
     void (*rollout)(const DeviceEnv& d, const ResidentNet& net, const ResidentRings& ring, int E, int T, unsigned long long seed, hipStream_t st);
+    // K whole episodes of every env in one launch (mi_env_evaluate): reads the env's arguments and seed only, writes the records only
+    void (*evaluate)(const DeviceEnv& d, const ResidentNet& net, const EvalRecords& rec, int E, int K, long long first_episode,
+                     unsigned long long seed, bool greedy, hipStream_t st);
+    int (*max_steps)(const DeviceEnv& d);      // the create call's max_steps, as the env's Args member holds it
 };
 // ops: null = no env.  state [E][width] fp64, steps of the running episode, episode number; the staging slot of mi_env_step {actions,
 // next observation, reward, done}, which leaves the rings alone.

@@ -83,8 +83,10 @@ static void env_reset(const DeviceEnv& d, int E, float* obs, hipStream_t st) {
 // on the main stream and returns; the only host wait is the caller's read of the reward / done rings afterwards.  A context holds at
 // most one env: the create call points c->env.ops at its row, and every other mi_env_* entry goes through that row.
 template <typename Env>
+static int env_max_steps(const DeviceEnv& d) { return Env::args(d).max_steps; }
+template <typename Env>
 static constexpr EnvOps env_row(const char* entry, const char* columns, const char* actions, const char* action_range) {
-    return {entry, columns, actions, action_range, Env::W, Env::A, env_step<Env>, env_reset<Env>, env_rollout_resident<Env>};
+    return {entry, columns, actions, action_range, Env::W, Env::A, env_step<Env>, env_reset<Env>, env_rollout_resident<Env>, env_evaluate<Env>, env_max_steps<Env>};
 }
 static const EnvOps CARTPOLE_ENV = env_row<CartPole>("mi_env_cartpole_create", "the cart-pole's nine state columns", "push left / push right",
                                                      "mi_env_step: every action must be 0 or 1");
@@ -197,6 +199,43 @@ int mi_env_rollout_resident(mi_ctx* c, uint64_t seed) {
     c->prof.phase = 0;
     d.ops->rollout(d, net, ring, c->E, c->T, seed, c->stream);
     HIPC(hipGetLastError());
+    return 0;
+}
+// K whole episodes of every env in ONE launch (env_evaluate.hip).  Every refusal comes before any launch or allocation; the env's state /
+// n_steps / episode and the rings are neither read nor written, so a training run may call this between two iterations.
+#define EVAL_MAX_STEPS (1ll << 20)      // episodes * max_steps of one launch: tens of seconds at the resident rollout's 27 us per step
+int mi_env_evaluate(mi_ctx* c, int32_t episodes, uint64_t seed, int32_t greedy, int64_t first_episode, const double* starts, double* ret,
+                    int32_t* length, int32_t* terminated, float* value0, double* start_out) {
+    ARG(c, "null"); JOIN(c); ENV(c);
+    const std::string f = "mi_env_evaluate: ";
+    ARG(!c->gru_on, f + "a recurrent context (mi_set_gru) is not supported");
+    { const std::string why = resident_shape_refusal(c); ARG(why.empty(), f + why); }
+    const DeviceEnv& d = c->env;
+    ARG(c->cfg.obs_dim == d.ops->width && c->cfg.obs_dim <= 16, f + "obs_dim must be the env's state width");
+    ARG(episodes >= 1, f + "episodes must be at least 1");
+    ARG((long long)episodes * (long long)d.ops->max_steps(d) <= EVAL_MAX_STEPS,
+        f + "episodes * max_steps must be at most 2^20 = 1048576 (evaluate further episodes with another call and another first_episode)");
+    ARG(first_episode >= 1, f + "first_episode must be at least 1");
+    const size_t E = c->E, W = d.ops->width, K = (size_t)episodes, n = E * K;
+    if (starts) for (size_t k = 0; k < n * W; ++k) ARG(!isnan(starts[k]), f + "starts must not hold a NaN");
+    // the device buffers of the planted starts and the records: one group of the context's pool, given back when the call returns (the
+    // pool frees a group only as a whole and newest first, so nothing is kept between calls; behind the synchronise below, and hipFree
+    // waits for the device on the paths that leave early)
+    double *ev_starts = nullptr, *ev_ret = nullptr, *ev_start = nullptr; int32_t *ev_len = nullptr, *ev_term = nullptr; float* ev_v0 = nullptr;
+    DevPool& m = c->pool; DevPool::Group all(m);
+    HIPC(m.dev(&ev_starts, starts ? n * W : 1)); HIPC(m.dev(&ev_ret, n)); HIPC(m.dev(&ev_len, n)); HIPC(m.dev(&ev_term, n));
+    HIPC(m.dev(&ev_v0, n)); HIPC(m.dev(&ev_start, n * W));
+    if (starts) HIPC(hipMemcpyAsync(ev_starts, starts, n * W * 8, hipMemcpyHostToDevice, c->stream));
+    const ResidentNet net = resident_net(c);
+    const EvalRecords rec = {starts ? ev_starts : nullptr, ev_ret, ev_len, ev_term, ev_v0, ev_start};
+    d.ops->evaluate(d, net, rec, c->E, episodes, (long long)first_episode, seed, greedy != 0, c->stream);
+    HIPC(hipGetLastError());
+    if (ret) HIPC(hipMemcpyAsync(ret, ev_ret, n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (length) HIPC(hipMemcpyAsync(length, ev_len, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (terminated) HIPC(hipMemcpyAsync(terminated, ev_term, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (value0) HIPC(hipMemcpyAsync(value0, ev_v0, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (start_out) HIPC(hipMemcpyAsync(start_out, ev_start, n * W * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
     return 0;
 }
 int mi_env_get_state(mi_ctx* c, double* state, int32_t* n_steps, int64_t* episode) {

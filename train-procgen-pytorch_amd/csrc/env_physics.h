@@ -1,5 +1,5 @@
 // The physics of the device-resident envs, shared by their translation units (env_device.hip: the step / reset kernels and the mi_env_*
-// entries; env_resident.hip: the one-launch rollout).  An env is a physics struct (CartPole, CartPoleSwing, MountainCar): `Args` (its kernel arguments),
+// entries; env_resident.hip: the one-launch rollout; env_evaluate.hip: the one-launch evaluation).  An env is a physics struct (CartPole, CartPoleSwing, MountainCar): `Args` (its kernel arguments),
 // `W` (state columns = observation width), `A` (actions), `args(DeviceEnv)` (its member of the context's union) and two device functions
 //     fresh(p, seed, e, episode, s)         the start of episode `episode` of env e into s[W]
 //     advance(p, s, act, &reward) -> ended  one step on s[W] in the host env's operation order; reward of this step
@@ -121,3 +121,7 @@ struct MountainCar {
 template <typename Env>
 MI_INTERNAL void env_rollout_resident(const DeviceEnv& d, const ResidentNet& net, const ResidentRings& ring, int E, int T, unsigned long long seed,
                                       hipStream_t st);
+// the one-launch evaluation of an env, K whole episodes each (env_evaluate.hip instantiates it likewise)
+template <typename Env>
+MI_INTERNAL void env_evaluate(const DeviceEnv& d, const ResidentNet& net, const EvalRecords& rec, int E, int K, long long first_episode,
+                              unsigned long long seed, bool greedy, hipStream_t st);

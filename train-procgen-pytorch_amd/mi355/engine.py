@@ -69,7 +69,7 @@ EXPORTS = ("mi_last_error mi_create mi_destroy mi_sync mi_host_alloc mi_host_fre
            "mi_sae_create mi_sae_destroy mi_sae_param_count mi_sae_set_params mi_sae_get_params mi_sae_get_grads mi_sae_set_adam_state mi_sae_get_adam_state mi_sae_put_ring "
            "mi_sae_get_hidden mi_sae_get_logits mi_sae_step mi_sae_minibatch mi_sae_probe_minibatch mi_sae_optimizer_step mi_sae_debug_forward "
            "mi_ipl_minibatch mi_ipl_read_pred mi_predict_greedy mi_op_ipl_loss mi_op_ipl_greedy "
-           "mi_env_cartpole_create mi_env_cartpole_swing_create mi_env_mountain_car_create mi_env_reset mi_env_step mi_env_rollout mi_env_rollout_resident mi_env_get_state mi_env_set_state").split()
+           "mi_env_cartpole_create mi_env_cartpole_swing_create mi_env_mountain_car_create mi_env_reset mi_env_step mi_env_rollout mi_env_rollout_resident mi_env_evaluate mi_env_get_state mi_env_set_state").split()
 
 
 def load_library():
@@ -330,6 +330,27 @@ class Engine:
         from the chain's by fp32 summation order) instead of the chain of launches."""
         call = self.lib.mi_env_rollout_resident if resident else self.lib.mi_env_rollout
         self._chk(call(self._ctx, C.c_uint64(seed)))
+
+    def env_evaluate(self, episodes, seed=0, greedy=False, first_episode=1 << 40, starts=None):
+        """Every env runs exactly `episodes` whole episodes of the engine's policy in ONE kernel launch (mi_env_evaluate) -> dict of numpy
+        arrays, (E, K) each: ret float64 (the fp64 sum of the env's rewards), length int32, terminated int32 (the env's own flag: 0 for a
+        truncation at max_steps), value0 float32 (the value head at the episode's first observation), and start (E, K, W) float64 (the
+        state the episode began in).  Episode i of env e starts at the reset stream's episode first_episode + i -- the default keeps
+        evaluation episodes disjoint from any training run's, whose counters start at 1 -- or at starts[e, i] (E, K, W).  greedy: the first
+        arg-max of the log-probabilities instead of the sampler's uniform of (seed, t * E + e).  The env's state and the rollout rings are
+        neither read nor written.  Synchronises."""
+        K, W = int(episodes), self._env_width or 1
+        n = max(K, 0)
+        if starts is not None:
+            starts = np.ascontiguousarray(starts, dtype=np.float64)
+            if starts.size != self.E * n * W:
+                raise EngineError(f"env_evaluate: starts must have {self.E} x {n} x {W} elements")
+        out = dict(ret=np.zeros((self.E, n), np.float64), length=np.zeros((self.E, n), np.int32), terminated=np.zeros((self.E, n), np.int32),
+                   value0=np.zeros((self.E, n), np.float32), start=np.zeros((self.E, n, W), np.float64))
+        self._chk(self.lib.mi_env_evaluate(self._ctx, C.c_int32(K), C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_int32(int(bool(greedy))),
+                                           C.c_int64(int(first_episode)), _fp(starts), _fp(out["ret"]), _fp(out["length"]), _fp(out["terminated"]),
+                                           _fp(out["value0"]), _fp(out["start"])))
+        return out
 
     # ------------------------------------------------------------------ policy
     def policy_step(self, t, seed=0, u=None, want_outputs=True):
