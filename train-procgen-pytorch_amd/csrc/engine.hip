@@ -22,7 +22,7 @@
 //    1 stage_indices           pull the minibatch indices into d_idx
 //    2 forward_impala_bf16     repack (after an optimizer step), conv1+pool, per block: conv+pool, residual pair; fc
 //    3 net_heads               logits + value
-//    4 loss                    loss_fwd_seg (+ fs_metric_seg, loss_finalize_seg here when the side stream is not armed)
+//    4 loss                    loss_fwd_seg (+ fs_metric_seg, loss_finalize_seg here when the pass has no side job)
 //    5 heads_backward          dY -> dfeat, head gradients                          | fork 1 (fork_stats_and_fc): head slab sum, metric,
 //    6 fc data gradient        dfeat -> block-3 output gradient                     |   log records, fc weight / bias gradients
 //    7 blocks 3, 2, 1          backward_residual_pair, then the block's conv (+ pool) backward
@@ -717,13 +717,13 @@ static void net_heads(mi_ctx* c, int n, int soff = 0) {
     linear_fwd(c, c->feat + (size_t)soff * c->H, 0, c->params + c->wh_off, c->params + c->bh_off, c->hout + (size_t)soff * (c->A + 1), n, c->H, c->A + 1, 0);
 }
 // h' = GRU(feat, h_state * (1 - done)); feat <- h' ; h_state <- h'   (n == E rows)
-static void net_gru(mi_ctx* c, int n, int soff = 0) {
+static void net_gru(mi_ctx* c, int n, int soff, bool keep_x) {
     const int H = c->H;
     const size_t o = (size_t)soff * H;
     launch_mask_rows(c->h_state + o, c->d_done + soff, c->h_masked + o, n, H, CUR(c));
     linear_fwd(c, c->feat + o, 0, c->gru_wih, c->gru_bih, c->gru_gi + 3 * o, n, H, 3 * H, 0);
     linear_fwd(c, c->h_masked + o, 0, c->gru_whh, c->gru_bhh, c->gru_gh + 3 * o, n, H, 3 * H, 0);
-    if (c->sal_keep_x) hipMemcpyAsync(c->gru_x + o, c->feat + o, (size_t)n * H * 4, hipMemcpyDeviceToDevice, CUR(c));     // (the gates kernel overwrites feat with h')
+    if (keep_x) hipMemcpyAsync(c->gru_x + o, c->feat + o, (size_t)n * H * 4, hipMemcpyDeviceToDevice, CUR(c));     // (the gates kernel overwrites feat with h')
     launch_gru_gates(c->gru_gi + 3 * o, c->gru_gh + 3 * o, c->h_masked + o, c->h_state + o, c->feat + o, n, H, CUR(c));
 }
 
@@ -834,13 +834,13 @@ void net_forward(mi_ctx* c, const InputSrc& src, int n, const FwdOpts& o) {
     if (c->cfg.arch != MI_ARCH_IMPALA) forward_mlp(c, src, n, o.soff, feat);
     else if (!c->bf) forward_impala_fp32(c, src, n, o.soff, feat);
     else if (!forward_impala_bf16(c, src, n, o.soff, feat, o.train)) return;
-    if (o.recurrent && c->gru_on) net_gru(c, n, o.soff);
+    if (o.recurrent && c->gru_on) net_gru(c, n, o.soff, o.keep_gru_x);
     if (o.heads) net_heads(c, n, o.soff);
 }
 
 // ---- backward
 // The heads' three gradients from dY (n x (A+1)).  fused (each caller's own condition): one launch (heads.hip heads_bwd_kernel) that also sums
-// its slabs unless an armed side stream does (with_reduce false; it forks on done_ev = this launch's own completion); else two GEMMs + a
+// its slabs unless the side stream of a forking pass does (with_reduce false; it forks on done_ev = this launch's own completion); else two GEMMs + a
 // column sum.  prof: only net_backward's launch is bracketed for the profiler.
 static void heads_backward(mi_ctx* c, int n, int relu_mask, bool fused, bool prof, hipStream_t st, bool with_reduce = true, hipEvent_t done_ev = nullptr) {
     if (fused) {
@@ -852,32 +852,35 @@ static void heads_backward(mi_ctx* c, int n, int relu_mask, bool fused, bool pro
     linear_dgrad(c, c->dY, c->params + c->wh_off, relu_mask ? c->feat : nullptr, c->dfeat, n, c->H, c->A + 1);
 }
 
-static void backward_mlp(mi_ctx* c, int n) {
+// backward_*: the embedder's backward pass from dfeat.  Each returns where it left the gradient of the first layer's output (the MLP's first
+// linear layer; IMPALA fp32: block1.conv; bf16: block 1's max pool), which the value saliency takes on to the observation.
+static const float* backward_mlp(mi_ctx* c, int n) {
     const size_t L = c->mlp.size();
     const float* dy = c->dfeat;
     for (size_t l = L; l-- > 0;) {
         linear_wgrad(c, dy, c->mlp_act[l], 0, c->grads + c->mlp[l].w_off, c->grads + c->mlp[l].b_off, n, c->mlp[l].in, c->mlp[l].out);
-        if (l == 0) { c->sal_src = dy; break; }
+        if (l == 0) break;
         float* dx = c->GP[l & 1];
         linear_dgrad(c, dy, c->params + c->mlp[l].w_off, c->mlp_act[l], dx, n, c->mlp[l].in, c->mlp[l].out);
         dy = dx;
     }
     issue_grad_allreduce(c, 0, c->n_params, true);
+    return L ? dy : nullptr;
 }
 
 // + fs_coef * d(feature sparsity) / d(block3 output): one element per column (launch_fs_grad, loss.hip)
-static void fs_gradient(mi_ctx* c, int n, float* G) {
-    if (c->fs_grad_coef == 0.f) return;
-    if (c->fs_global_apply) { if (n > 0) launch_fs_apply_keys(G, c->bf, 2048, c->fs_keys, c->fs_keys_local, c->fs_arg, c->fs_grad_coef, CUR(c)); }      // the column's winner among the ranks
-    else launch_fs_grad(c->blk[2].P2, c->bf, n, 2048, c->fs_scratch, c->fs_G, G, c->fs_grad_coef, c->fs_colmax, c->fs_arg, CUR(c));
+static void fs_gradient(mi_ctx* c, int n, float* G, const BwdOpts& o) {
+    if (o.fs_coef == 0.f) return;
+    if (o.fs_from_keys) { if (n > 0) launch_fs_apply_keys(G, c->bf, 2048, c->fs_keys, c->fs_keys_local, c->fs_arg, o.fs_coef, CUR(c)); }      // the column's winner among the ranks
+    else launch_fs_grad(c->blk[2].P2, c->bf, n, 2048, c->fs_scratch, o.fs_groups, G, o.fs_coef, c->fs_colmax, c->fs_arg, CUR(c));
 }
 
-static void backward_impala_fp32(mi_ctx* c, const InputSrc& src, int n) {
+static const float* backward_impala_fp32(mi_ctx* c, const InputSrc& src, int n, const BwdOpts& o) {
     linear_wgrad(c, c->dfeat, c->blk[2].P2, 1, c->grads + c->fc.w_off, c->grads + c->fc.b_off, n, 2048, c->H, 0);
     issue_grad_allreduce(c, c->fc.w_off, c->n_params - c->fc.w_off, false);       // region A: fc + heads gradients are final
     float *Gout = c->GP[0], *Ga = c->GP[1], *Gb = c->GP[2];
     linear_dgrad(c, c->dfeat, c->params + c->fc.w_off, c->blk[2].P2, Gout, n, 2048, c->H, 0);
-    fs_gradient(c, n, Gout);
+    fs_gradient(c, n, Gout, o);
     for (int b = 2; b >= 0; --b) {
         Block& k = c->blk[b];
         const ConvLayer* L = &c->convs[b * 5];
@@ -894,7 +897,7 @@ static void backward_impala_fp32(mi_ctx* c, const InputSrc& src, int n) {
         // max pool, then the block's first conv
         { ProfScope ps(c, PC_POOL_BWD, n, (double)n * k.hin * k.hin * k.cout * (c->es * 1.25 + 0.25), 0.0);
           launch_maxpool_bwd(Gout, k.PI, c->GC, n, k.hin, k.cout, CUR(c)); }
-        if (b == 0) { c->sal_src = c->GC; conv_wgrad(c, L[0], nullptr, &src, 0, c->GC, n); }
+        if (b == 0) conv_wgrad(c, L[0], nullptr, &src, 0, c->GC, n);
         else {
             conv_wgrad(c, L[0], c->blk[b - 1].P2, nullptr, 0, c->GC, n);
             conv_dgrad(c, L[0], c->GC, nullptr, nullptr, Gout, n);
@@ -902,17 +905,17 @@ static void backward_impala_fp32(mi_ctx* c, const InputSrc& src, int n) {
     }
     conv_wgrad_reduce_all(c, n);
     issue_grad_allreduce(c, 0, c->fc.w_off, true);                                 // region B: the conv layers' gradients
+    return c->GC;
 }
 
 // First fork of a bf16 pass, behind heads_bwd: the side stream takes the logged statistics and embedder.fc's weight / bias gradients
 // (mi_ctx::side_stream); the main stream goes straight on to the data gradient.  Every buffer the side work touches (block-3 output, feat,
 // dfeat, loss partial sums, the split-K / column-sum / metric workspaces, the fc + head slices of grads) is next written after the join.
-static void fork_stats_and_fc(mi_ctx* c, int n) {
+static void fork_stats_and_fc(mi_ctx* c, int n, const SideJob& j) {
     fc_refresh(c);
-    const mi_ctx::SideJob& j = c->side;
     hipStream_t ss = side_stream(c);
     hipStreamWaitEvent(ss, c->ev_side_fork, 0);          // (recorded at heads_bwd_kernel's own completion: heads_backward in net_backward)
-    if (c->idx_ev_deferred >= 0) { hipEventRecord(c->idx_ev[c->idx_ev_deferred], ss); c->idx_ev_deferred = -1; }      // (stage_indices: the index slot's "read" marker)
+    if (j.idx_slot >= 0) hipEventRecord(c->idx_ev[j.idx_slot], ss);      // (stage_indices: the index slot's "read" marker)
     tl_stream = ss;
     launch_heads_bwd_reduce(c->gemm_ws, c->grads + c->wh_off, c->grads + c->bh_off, n, c->H, c->A + 1, ss);      // (before fc_tn reuses the slabs)
     launch_fs_metric_seg(c->blk[2].P2, c->bf, j.st, 2048, c->fs_scratch, c->fs_parts, ss);
@@ -921,7 +924,6 @@ static void fork_stats_and_fc(mi_ctx* c, int n) {
     launch_colsum_acc(c->dfeat, n, c->H, c->H, c->grads + c->fc.b_off, c->col_ws, ss);
     tl_stream = nullptr;
     hipEventRecord(c->ev_side_join, ss);
-    c->side.armed = false;
 }
 // Second fork, in front of block1.conv's weight gradient: that is the last kernel of the pass and nothing but its own slabs depends on it,
 // so the slab sums of the 14 layers before it run beside it (the table on the device is the cached one of this batch size: its last entry
@@ -996,13 +998,13 @@ static void backward_conv_pool_bf16(mi_ctx* c, int b, int n, const float* G, flo
     }
 }
 
-static void backward_impala_bf16(mi_ctx* c, const InputSrc& src, int n) {
+static const float* backward_impala_bf16(mi_ctx* c, const InputSrc& src, int n, const BwdOpts& o) {
     const bool fc16 = n >= 1024;
-    const bool fork1 = fc16 && c->side.armed && !tl_stream;
+    const bool fork1 = fc16 && o.side != nullptr && !tl_stream;
     const bool fork2 = c->side_on && !tl_stream && n >= 1024 && c->slab_desc_cached_n == n;
     float *Gout = c->GP[0], *Ga = c->GP[1], *Gb = c->GP[2];
-    // embedder.fc: weight / bias gradient (on the side stream when it is armed), then the data gradient
-    if (fork1) fork_stats_and_fc(c, n);
+    // embedder.fc: weight / bias gradient (on the side stream when the pass has a job for it), then the data gradient
+    if (fork1) fork_stats_and_fc(c, n, *o.side);
     else if (fc16) {
         fc_refresh(c);
         { const double H = c->H;
@@ -1018,7 +1020,7 @@ static void backward_impala_bf16(mi_ctx* c, const InputSrc& src, int n) {
         launch_fc_dgrad_bf16(c->dfeat, c->fc_wt, c->blk[2].P2, Gout, n, c->H, CUR(c));
     } else
         linear_dgrad(c, c->dfeat, c->params + c->fc.w_off, c->blk[2].P2, Gout, n, 2048, c->H, 1);
-    fs_gradient(c, n, Gout);
+    fs_gradient(c, n, Gout, o);
     // blocks 3 and 2: residual pair, then the block's conv + pool (its data gradient lands in Ga: swap)
     for (int b = 2; b >= 1; --b) {
         backward_residual_pair(c, b, n, Gout, Ga, Gb, nullptr);
@@ -1027,26 +1029,27 @@ static void backward_impala_bf16(mi_ctx* c, const InputSrc& src, int n) {
     }
     // block 1: its res1 is the last launch in front of the second fork, so the fork event is that launch's own completion
     const bool fork2_on_launch = backward_residual_pair(c, 0, n, Gout, Ga, Gb, fork2 ? c->ev_side_fork : nullptr);
-    c->sal_src = Gout;
+    const float* const first = Gout;          // the gradient of block 1's pooled map
     int slabs_done = 0;          // leading entries of the slab table already summed on the side stream
     if (fork2 && c->slab_desc_n >= 1) slabs_done = fork_slab_sums(c, fork2_on_launch);
     conv_wgrad(c, c->convs[0], nullptr, &src, 0, Gout, n, c->blk[0].PI);          // block1.conv, pool backward fused into the staging
     if (fork1 || slabs_done) hipStreamWaitEvent(c->stream, c->ev_side_join, 0);   // join: statistics, fc gradients (and the first slab sums) are in place behind this point
     conv_wgrad_reduce_all(c, n, slabs_done);
     issue_grad_allreduce(c, 0, c->fc.w_off, true);                                 // region B: the conv layers' gradients
+    return first;
 }
 
-// backward from dY (n x (A+1)); gradients accumulate into c->grads
-static void net_backward(mi_ctx* c, const InputSrc& src, int n) {
+// backward from dY (n x (A+1)), or from dfeat (o.from_dfeat); gradients accumulate into c->grads.  Returns what backward_* return.
+static const float* net_backward(mi_ctx* c, const InputSrc& src, int n, const BwdOpts& o) {
     const bool impala = c->cfg.arch == MI_ARCH_IMPALA;
     // (value saliency of a recurrent policy and mi_minibatch_rec come in with d / d (embedder output) in c->dfeat already: no heads step)
-    if (!c->bwd_from_dfeat) {
-        const bool to_side = c->side.armed && !tl_stream;      // side stream armed: it also sums the heads' slabs and forks on this launch's completion
+    if (!o.from_dfeat) {
+        const bool to_side = o.side != nullptr && !tl_stream;      // a side job: the side stream also sums the heads' slabs and forks on this launch's completion
         heads_backward(c, n, impala ? 1 : 0, c->H <= 256 && c->A + 1 <= 16 && !tl_ws, true, CUR(c), !to_side, to_side ? c->ev_side_fork : nullptr);
     }
-    if (!impala) backward_mlp(c, n);
-    else if (!c->bf) backward_impala_fp32(c, src, n);
-    else backward_impala_bf16(c, src, n);
+    if (!impala) return backward_mlp(c, n);
+    if (!c->bf) return backward_impala_fp32(c, src, n, o);
+    return backward_impala_bf16(c, src, n, o);
 }
 
 // ------------------------------------------------------------------------------------------ predict / forward
@@ -1389,11 +1392,9 @@ int mi_value_saliency(mi_ctx* c, const void* obs, size_t bytes, uint64_t seed, u
     c->prof.phase = 0;
     const bool rec = c->gru_on;
     if (rec && !c->gru_x) { DevPool::Group both(c->pool); HIPC(c->pool.dev(&c->gru_x, (size_t)E * c->H)); HIPC(c->pool.dev(&c->gru_dg, (size_t)E * 3 * c->H)); both.keep = true; }
-    c->sal_keep_x = rec;
-    net_forward(c, src, E, {.recurrent = rec, .train = true});          // recurrent: h' = GRU(embedder output, h (1 - done)) as a policy step does, heads on h'
-    c->sal_keep_x = false;
+    net_forward(c, src, E, {.recurrent = rec, .train = true, .keep_gru_x = rec});          // recurrent: h' = GRU(embedder output, h (1 - done)) as a policy step does, heads on h'
     launch_sample(c->hout, E, c->A, du, seed, counter, c->s_act, c->s_logp, c->s_val, c->stream, c->lse);
-    c->sal_src = nullptr;
+    const float* g1;      // where the backward pass leaves the gradient of the first layer's output
     if (rec) {
         // value = w_v . h' + b_v: back through the GRU cell to its input x (common/model.py:219-225 under autograd, agents/ppo.py:88-89), then
         // through the embedder's final ReLU (IMPALA) -- d value / d x = dgates W_ih -- and on down the usual backward pass from dfeat
@@ -1404,27 +1405,25 @@ int mi_value_saliency(mi_ctx* c, const void* obs, size_t bytes, uint64_t seed, u
         } else
         launch_gru_value_bwd(c->gru_gi, c->gru_gh, c->h_masked, c->params + c->wh_off + (size_t)c->A * c->H, c->gru_dg, E, c->H, c->stream);
         linear_dgrad(c, c->gru_dg, c->gru_wih, impala ? c->gru_x : nullptr, c->dfeat, E, c->H, 3 * c->H);
-        c->bwd_from_dfeat = true;
-        net_backward(c, src, E);
-        c->bwd_from_dfeat = false;
+        g1 = net_backward(c, src, E, {.from_dfeat = true});
     } else {
         if (c->lse) launch_lse_value_seed(c->hout, c->dY, E, c->A, c->stream);
         else launch_value_seed(c->dY, E, c->A, c->stream);
-        net_backward(c, src, E);
+        g1 = net_backward(c, src, E, {});
     }
-    ARG(c->sal_src, "backward did not reach the first layer");
+    ARG(g1, "backward did not reach the first layer");
     const size_t gfloats = impala ? (size_t)E * 64 * 64 * 3 : (size_t)E * c->cfg.obs_dim;
     if (!c->sal_dx) HIPC(c->pool.dev(&c->sal_dx, impala ? (size_t)c->NB * 64 * 64 * 3 : (size_t)c->NB * c->cfg.obs_dim));
     if (impala) {
-        const void* dC = c->sal_src;
+        const void* dC = g1;
         if (c->bf) {                                       // the conv-output gradient is not materialised in bf16 mode: rebuild it from the pooled one
             if (!c->sal_dc) HIPC(c->pool.dev_raw(&c->sal_dc, (size_t)c->NB * 64 * 64 * 16 * 2 + 256));
-            launch_maxpool_bwd_bf16(c->sal_src, c->blk[0].PI, c->sal_dc, E, 64, 16, c->stream);
+            launch_maxpool_bwd_bf16(g1, c->blk[0].PI, c->sal_dc, E, 64, 16, c->stream);
             dC = c->sal_dc;
         }
         launch_conv1_input_grad(dC, c->bf, c->params + c->convs[0].w_off, c->sal_dx, E, c->stream);
     } else {
-        linear_dgrad(c, c->sal_src, c->params + c->mlp[0].w_off, nullptr, c->sal_dx, E, c->mlp[0].in, c->mlp[0].out);
+        linear_dgrad(c, g1, c->params + c->mlp[0].w_off, nullptr, c->sal_dx, E, c->mlp[0].in, c->mlp[0].out);
     }
     launch_fill(c->grads, c->n_params, 0.f, c->stream);    // discard the parameter gradients of this pass
     HIPC(hipGetLastError()); NETCHK(c);
@@ -1573,20 +1572,47 @@ static InputSrc minibatch_src(mi_ctx* c) {
 // The N gather indices of a pass: fill(h) writes them into the next slot of the pinned index ring (a slot is rewritten only after the
 // pull that read it has completed), a kernel pulls them into d_idx.
 // "slot read" marker: an event record between the pull and the first conv kernel is a ~5 us bubble on the main stream (kernel
-// traces: 5-7 us between pull_i32 and repack_all); when the pass forks the side stream (defer_marker), the marker is recorded THERE,
-// behind the fork (which is behind the pull in main-stream order: fork_stats_and_fc)
+// traces: 5-7 us between pull_i32 and repack_all); when the pass forks the side stream (deferred_slot set: the slot goes there, for
+// SideJob::idx_slot), the marker is recorded THERE, behind the fork (which is behind the pull in main-stream order: fork_stats_and_fc)
 template <typename Fill>
-static int stage_indices(mi_ctx* c, int N, Fill fill, bool defer_marker) {
+static int stage_indices(mi_ctx* c, int N, Fill fill, int* deferred_slot) {
     const int slot = c->idx_next;
     c->idx_next = (slot + 1) % mi_ctx::IDX_RING;
     if (c->idx_used[slot]) HIPC(hipEventSynchronize(c->idx_ev[slot]));     // the pull that read this slot is done
     int32_t* h = c->h_idx_ring[slot];
     fill(h);
     launch_pull_i32(h, c->d_idx, N, c->stream);              // (not hipMemcpyAsync: see pull_i32_kernel)
-    if (defer_marker) c->idx_ev_deferred = slot;
+    if (deferred_slot) *deferred_slot = slot;
     else HIPC(hipEventRecord(c->idx_ev[slot], c->stream));
     c->idx_used[slot] = true;
     return 0;
+}
+// What every minibatch entry does behind its own refusals and before its first launch.  The refusals all share, worded behind the entry's
+// prefix: the n_idx caller indices lie in [0, limit) (range_msg), no multirank pass is pending, the loss log has room for n_seg records.
+// Then the pass's N gather indices (stage_indices; N == 0: an empty pass pulls nothing), the profiler's sampling decision, and rec_last.
+template <typename Fill>
+static int begin_pass(mi_ctx* c, const char* prefix, const int64_t* idx, int n_idx, int64_t limit, const char* range_msg, int n_seg, int N, Fill fill,
+                      int* deferred_slot = nullptr) {
+    auto refuse = [&](const char* why) { return fail(-1, std::string(prefix) + why); };
+    for (int k = 0; k < n_idx; ++k) if (!(idx[k] >= 0 && idx[k] < limit)) return refuse(range_msg);
+    if (!(c->pending_n < 0)) return refuse("previous multirank minibatch not finished");
+    if (!(c->log_count + n_seg <= c->log_cap)) return refuse("loss log full: call mi_loss_log_read(reset=1)");
+    if (N > 0) if (int r = stage_indices(c, N, fill, deferred_slot)) return r;
+    c->prof.phase = 1;
+    c->prof.sample_now = (c->prof.mb_count++ % c->prof.period) == 0;
+    c->rec_last = false;
+    return 0;
+}
+static const char kArgPrefix[] = "invalid argument: ";      // ARG's
+static auto copy_indices(const int64_t* idx, int n) { return [=](int32_t* h) { for (int k = 0; k < n; ++k) h[k] = (int32_t)idx[k]; }; }
+// Where record log_count goes: its row of the statistics ring, its rank-local feature-sparsity value, its loss-log record
+struct LogSlot { float *ring, *fsr, *log; };
+static LogSlot log_slot(const mi_ctx* c) { return {c->stats_ring + (size_t)c->log_count * 32, c->fs_ring + c->log_count, c->loss_log + (size_t)c->log_count * 8}; }
+static SegTab seg_tab(const int32_t* seg_n, int n_seg) {
+    SegTab st{};
+    st.n_seg = n_seg;
+    for (int k = 0; k < n_seg; ++k) st.start[k + 1] = st.start[k] + seg_n[k];
+    return st;
 }
 static LossArgs loss_args(mi_ctx* c, int n, int n_global, const mi_hparams* hp) {
     LossArgs a{};
@@ -1612,28 +1638,23 @@ static void loss_and_records(mi_ctx* c, const LossArgs& a, const SegTab& st, boo
 // sums the gradients of the accumulated minibatches before the optimizer step, so only the fp32 summation order changes); it
 // needs a loss without batch-level terms (x_entropy_coef == 0, fs_coef == 0).
 static bool side_eligible(const mi_ctx* c, int n, bool batch_terms) {
-    return c->side_on && c->cfg.arch == MI_ARCH_IMPALA && c->bf && n >= 1024 && !batch_terms && !c->ar_armed && !c->comm && !c->bwd_from_dfeat &&
-           c->H <= 256 && c->A + 1 <= 16;
+    return c->side_on && c->cfg.arch == MI_ARCH_IMPALA && c->bf && n >= 1024 && !batch_terms && !c->ar_armed && !c->comm && c->H <= 256 && c->A + 1 <= 16;
 }
 static int minibatch_impl(mi_ctx* c, const int64_t* idx, int32_t n, const int32_t* seg_n, int32_t n_seg, int32_t n_global, const mi_hparams* hp) {
     ARG(c && hp, "null"); JOIN(c); ARG(n >= 0 && n <= c->NB, "n_idx must be in [0, max_batch]"); ARG(n_global >= 1, "n_global");
     ARG(n == 0 || idx, "idx"); ARG(n_seg >= 1 && n_seg <= MI_MAX_SEG && seg_n, "1 .. 16 segments");
-    ARG(c->log_count + n_seg <= c->log_cap, "loss log full: call mi_loss_log_read(reset=1)");
-    ARG(c->pending_n < 0, "previous multirank minibatch not finished");
     { long long tot = 0; for (int k = 0; k < n_seg; ++k) { ARG(seg_n[k] >= 0, "negative segment"); tot += seg_n[k]; } ARG(tot == n, "segments do not add up to n_idx"); }
     const bool batch_terms = hp->x_entropy_coef != 0.f || hp->fs_coef != 0.f;
     ARG(hp->fs_coef == 0.f || c->multirank != 2, "fs_coef != 0 needs the column maxima over the GLOBAL minibatch before the backward pass: multirank mode 1");
     ARG(hp->fs_coef == 0.f || c->multirank == 0 || c->cfg.arch != MI_ARCH_IMPALA || c->gpos_n == n,
         "fs_coef != 0 on several ranks: call mi_minibatch_positions with this pass's global minibatch positions first");
     ARG(n_seg == 1 || (!batch_terms && c->multirank != 1), "several minibatches per call need x_entropy_coef == 0, fs_coef == 0 and multirank mode 0 or 2");
-    const int64_t TE = (int64_t)c->T * c->E;
-    for (int k = 0; k < n; ++k) ARG(idx[k] >= 0 && idx[k] < TE, "minibatch index out of range");
-    if (n)
-        if (int r = stage_indices(c, n, [&](int32_t* h) { for (int k = 0; k < n; ++k) h[k] = (int32_t)idx[k]; }, side_eligible(c, n, batch_terms) && c->multirank != 1)) return r;
+    // no batch-level loss terms, bf16 IMPALA at update size, gradients exchanged (if at all) behind the pass: metric + records leave the
+    // critical path (net_backward forks); the in-library armed exchange hands region A over in the middle of the pass and keeps the old order
+    const bool fork = side_eligible(c, n, batch_terms) && c->multirank != 1;
+    SideJob side{};
+    if (int r = begin_pass(c, kArgPrefix, idx, n, (int64_t)c->T * c->E, "minibatch index out of range", n_seg, n, copy_indices(idx, n), fork ? &side.idx_slot : nullptr)) return r;
     InputSrc src = minibatch_src(c);
-    c->prof.phase = 1;
-    c->prof.sample_now = (c->prof.mb_count++ % c->prof.period) == 0;
-    c->rec_last = false;
     net_forward(c, src, n, {.train = true});
     const bool impala = c->cfg.arch == MI_ARCH_IMPALA;
     LossArgs a = loss_args(c, n, n_global, hp);
@@ -1645,27 +1666,22 @@ static int minibatch_impl(mi_ctx* c, const int64_t* idx, int32_t n, const int32_
         // modes 0 and 2: loss terms + logged statistics of all segments with one launch each.  The rank-local sums land in the
         // statistics ring (mode 0 derives the records right away, mode 2 after the cross-rank sum in mi_loss_log_finalize); without
         // batch-level terms the sample gradients dY come out of the same pass.
-        SegTab st{};
-        st.n_seg = n_seg;
-        for (int k = 0; k < n_seg; ++k) st.start[k + 1] = st.start[k] + seg_n[k];
-        float* ring = c->stats_ring + (size_t)c->log_count * 32;
-        float* fsr = c->fs_ring + c->log_count;
-        a.stats = ring;                                  // (x-entropy gradient, mode 0, n_seg == 1: the batch-mean action distribution)
-        // no batch-level loss terms, bf16 IMPALA at update size, gradients exchanged (if at all) behind the pass: metric + records leave the
-        // critical path (net_backward forks); the in-library armed exchange hands region A over in the middle of the pass and keeps the old order
+        const SegTab st = seg_tab(seg_n, n_seg);
+        const LogSlot s = log_slot(c);
+        a.stats = s.ring;                                // (x-entropy gradient, mode 0, n_seg == 1: the batch-mean action distribution)
         const int mode = c->multirank == 2 ? 1 : 3;
-        float* log = c->multirank == 2 ? nullptr : c->loss_log + (size_t)c->log_count * 8;
-        if (side_eligible(c, n, batch_terms)) {
+        float* log = c->multirank == 2 ? nullptr : s.log;
+        if (fork) {
             launch_loss_fwd_seg(a, st, true, c->stream);
-            c->side = mi_ctx::SideJob{true, a, st, mode, ring, fsr, log};
+            side = SideJob{a, st, mode, s.ring, s.fsr, log, side.idx_slot};
         } else
-            loss_and_records(c, a, st, !batch_terms, mode, ring, fsr, log);
+            loss_and_records(c, a, st, !batch_terms, mode, s.ring, s.fsr, log);
         c->ring_args = a;
         c->log_count += n_seg;
         if (batch_terms) launch_loss_bwd(a, c->stream);
-        if (impala && hp->fs_coef != 0.f && n > 0) { c->fs_grad_coef = hp->fs_coef; c->fs_G = fs_groups_per_segment(n_seg); }
-        net_backward(c, src, n);
-        c->fs_grad_coef = 0.f;
+        BwdOpts o{.side = fork ? &side : nullptr};
+        if (impala && hp->fs_coef != 0.f && n > 0) { o.fs_coef = hp->fs_coef; o.fs_groups = fs_groups_per_segment(n_seg); }
+        net_backward(c, src, n, o);
         HIPC(hipGetLastError()); NETCHK(c);
         return 0;
     }
@@ -1715,15 +1731,8 @@ int mi_minibatch_fused(mi_ctx* c, const int64_t* idx, int32_t n, const int32_t* 
     FUSED_ARG(n >= 1 && n <= c->NB, "n_idx must be in [1, max_batch]"); FUSED_ARG(n_global >= 1, "n_global must be at least 1");
     FUSED_ARG(n_seg >= 1 && n_seg <= MI_MAX_SEG, "1 .. 16 segments");
     { long long tot = 0; for (int k = 0; k < n_seg; ++k) { FUSED_ARG(seg_n[k] >= 1, "every segment needs at least one sample"); tot += seg_n[k]; } FUSED_ARG(tot == n, "segments do not add up to n_idx"); }
-    const int64_t TE = (int64_t)c->T * c->E;
-    for (int k = 0; k < n; ++k) FUSED_ARG(idx[k] >= 0 && idx[k] < TE, "minibatch index out of range");
-    FUSED_ARG(c->pending_n < 0, "previous multirank minibatch not finished");
-    FUSED_ARG(c->log_count + n_seg <= c->log_cap, "loss log full: call mi_loss_log_read(reset=1)");
     if (int r = fused_alloc(c)) return r;
-    if (int r = stage_indices(c, n, [&](int32_t* h) { for (int k = 0; k < n; ++k) h[k] = (int32_t)idx[k]; }, false)) return r;
-    c->prof.phase = 1;
-    c->prof.sample_now = (c->prof.mb_count++ % c->prof.period) == 0;
-    c->rec_last = false;
+    if (int r = begin_pass(c, "mi_minibatch_fused: ", idx, n, (int64_t)c->T * c->E, "minibatch index out of range", n_seg, n, copy_indices(idx, n))) return r;
     const size_t L = c->mlp.size();
     FusedNet f = {};
     f.net = resident_net(c);
@@ -1731,12 +1740,10 @@ int mi_minibatch_fused(mi_ctx* c, const int64_t* idx, int32_t n, const int32_t* 
     f.act[L] = c->feat;
     f.obs = c->obsf; f.obs_dim = c->cfg.obs_dim; f.dYh = c->dY; f.terms = c->fu_terms;
     LossArgs a = loss_args(c, n, n_global, hp);
-    SegTab st{};
-    st.n_seg = n_seg;
-    for (int k = 0; k < n_seg; ++k) st.start[k + 1] = st.start[k] + seg_n[k];
-    a.stats = c->stats_ring + (size_t)c->log_count * 32;
+    const LogSlot s = log_slot(c);
+    a.stats = s.ring;
     launch_mlp_fused_pass(f, a, n, c->stream);
-    launch_mlp_fused_reduce(f, a, st, n, c->grads, c->stats_ring + (size_t)c->log_count * 32, c->loss_log + (size_t)c->log_count * 8, c->stream);
+    launch_mlp_fused_reduce(f, a, seg_tab(seg_n, n_seg), n, c->grads, s.ring, s.log, c->stream);
     c->ring_args = a;
     c->log_count += n_seg;
     HIPC(hipGetLastError()); NETCHK(c);
@@ -1769,15 +1776,15 @@ int mi_loss_log_finalize(mi_ctx* c) {
 int mi_minibatch_finish(mi_ctx* c) {
     ARG(c, "null"); JOIN(c); ARG(c->pending_n >= 0, "no pending minibatch");
     const bool impala = c->cfg.arch == MI_ARCH_IMPALA;
-    float* slot = c->loss_log + (size_t)c->log_count * 8;
     if (c->fs_global_pending) launch_fs_from_keys(c->fs_keys, 2048, c->fs_val, c->stream);      // the metric of the GLOBAL minibatch (keys are all-reduced by now)
-    launch_loss_finalize(c->pending, 0, 2, impala ? c->fs_val : nullptr, slot, c->stream);
+    launch_loss_finalize(c->pending, 0, 2, impala ? c->fs_val : nullptr, log_slot(c).log, c->stream);
     c->log_count++;
     launch_loss_bwd(c->pending, c->stream);
     InputSrc src = minibatch_src(c);
-    if (c->fs_global_pending) { c->fs_grad_coef = c->pending.hp.fs_coef; c->fs_global_apply = true; }
-    net_backward(c, src, c->pending_n);
-    c->fs_grad_coef = 0.f; c->fs_global_apply = false; c->fs_global_pending = false;
+    BwdOpts o;
+    if (c->fs_global_pending) { o.fs_coef = c->pending.hp.fs_coef; o.fs_from_keys = true; }
+    net_backward(c, src, c->pending_n, o);
+    c->fs_global_pending = false;
     c->pending_n = -1;
     HIPC(hipGetLastError()); NETCHK(c);
     return 0;
@@ -1789,7 +1796,7 @@ int mi_minibatch_finish(mi_ctx* c) {
 //   1 forward(nobs), inference   -> nv = done ? rew : V(nobs)                      (ipl.hip next-value kernel)
 //   2 forward(obs), training     -> loss kernel: pred, dY, g_next, the record      -> backward(obs)
 //   3 forward(nobs), training    -> dY = {0 .., g_next}                            -> backward(nobs), into the same gradient buffer
-// nobs = ring row idx + E (slot T holds the bootstrap observation).  Everything runs on the main stream (no side-stream job is armed).
+// nobs = ring row idx + E (slot T holds the bootstrap observation).  Everything runs on the main stream (no pass has a side job).
 static int ipl_alloc(mi_ctx* c) {
     if (c->ipl_idx2) return 0;
     const size_t NB = c->NB;
@@ -1807,17 +1814,10 @@ int mi_ipl_minibatch(mi_ctx* c, const int64_t* idx, int32_t n, int32_t n_global,
     ARG(!c->lse, "mi_ipl_minibatch: value_from_logits is not supported");
     ARG(n <= c->NB, "mi_ipl_minibatch: n > max_batch");
     ARG(n >= 1, "mi_ipl_minibatch: n must be at least 1"); ARG(n_global >= 1, "n_global");
-    ARG(c->pending_n < 0, "previous multirank minibatch not finished");
-    ARG(c->log_count + 1 <= c->log_cap, "loss log full: call mi_loss_log_read(reset=1)");
-    const int64_t TE = (int64_t)c->T * c->E;
-    for (int k = 0; k < n; ++k) ARG(idx[k] >= 0 && idx[k] < TE, "minibatch index out of range");
     if (int r = ipl_alloc(c)) return r;
-    if (int r = stage_indices(c, n, [&](int32_t* h) { for (int k = 0; k < n; ++k) h[k] = (int32_t)idx[k]; }, false)) return r;
+    if (int r = begin_pass(c, kArgPrefix, idx, n, (int64_t)c->T * c->E, "minibatch index out of range", 1, n, copy_indices(idx, n))) return r;
     launch_ipl_shift_idx(c->d_idx, c->ipl_idx2, n, c->E, c->stream);
     const InputSrc obs = minibatch_src(c), nobs{obs_ring(c), c->ipl_idx2, 0};
-    c->prof.phase = 1;
-    c->prof.sample_now = (c->prof.mb_count++ % c->prof.period) == 0;
-    c->rec_last = false;
     IplArgs a{};
     a.hout = c->hout; a.idx = c->d_idx; a.act = c->act; a.rew = c->rew; a.done = c->done;
     a.nv = c->ipl_nv; a.dY = c->dY; a.g_next = c->ipl_gnext; a.pred = c->ipl_pred; a.rew_out = c->ipl_rew; a.partial = c->ipl_partial;
@@ -1828,13 +1828,13 @@ int mi_ipl_minibatch(mi_ctx* c, const int64_t* idx, int32_t n, int32_t n_global,
     net_forward(c, nobs, n, {});
     launch_ipl_next_value(a, c->hout, c->A + 1, c->A, c->stream);
     net_forward(c, obs, n, {.train = true});
-    launch_ipl_loss(a, c->loss_log + (size_t)c->log_count * 8, c->stream);
+    launch_ipl_loss(a, log_slot(c).log, c->stream);
     c->log_count += 1;
     c->ipl_last_n = n;
-    net_backward(c, obs, n);
+    net_backward(c, obs, n, {});
     net_forward(c, nobs, n, {.train = true});
     launch_ipl_next_seed(c->ipl_gnext, c->dY, n, c->A, c->stream);
-    net_backward(c, nobs, n);
+    net_backward(c, nobs, n, {});
     HIPC(hipGetLastError()); NETCHK(c);
     return 0;
 }
@@ -1864,9 +1864,9 @@ int mi_optimizer_step(mi_ctx* c, float lr, float max_norm, int32_t step, float* 
             launch_adam(g.t[k].p, c->gru_g + g.t[k].off, c->gru_m + g.t[k].off, c->gru_v + g.t[k].off, (long long)g.t[k].len, c->gru_sumsq, 256, max_norm, lr, a.beta1,
                         a.beta2, a.eps, a.step_size, a.bc2_sqrt, nullptr, c->stream);
     } else {
-    launch_sumsq_partials(c->grads, c->n_params, c->sumsq + 2, c->stream);          // 128 partial sums; the Adam kernel's waves add them up themselves
-    launch_adam(c->params, c->grads, c->adam_m, c->adam_v, c->n_params, c->sumsq + 2, 128, max_norm, lr, a.beta1, a.beta2, a.eps,
-                a.step_size, a.bc2_sqrt, c->gnorm, c->stream);
+        launch_sumsq_partials(c->grads, c->n_params, c->sumsq + 2, c->stream);          // 128 partial sums; the Adam kernel's waves add them up themselves
+        launch_adam(c->params, c->grads, c->adam_m, c->adam_v, c->n_params, c->sumsq + 2, 128, max_norm, lr, a.beta1, a.beta2, a.eps,
+                    a.step_size, a.bc2_sqrt, c->gnorm, c->stream);
     }
     c->fc_packed_valid = false;
     HIPC(hipGetLastError()); NETCHK(c);
@@ -1941,15 +1941,11 @@ int mi_minibatch_rec(mi_ctx* c, const int64_t* env_idx, int32_t n_env, const flo
     ARG(c->multirank == 0 && !c->ar_armed && !c->comm, "GRU training runs on a single rank: multirank modes 1 / 2 and the in-library gradient exchange are refused");
     ARG(n_env >= 1 && n_global >= 1, "n_env / n_global");
     ARG((int64_t)n_env * c->T <= c->NB, "n_env * T must not exceed max_batch");
-    ARG(c->log_count + 1 <= c->log_cap, "loss log full: call mi_loss_log_read(reset=1)");
-    ARG(c->pending_n < 0, "previous multirank minibatch not finished");
-    for (int i = 0; i < n_env; ++i) ARG(env_idx[i] >= 0 && env_idx[i] < c->E, "env index out of range");
     const int T = c->T, E = c->E, H = c->H, n = n_env, N = n_env * T;
-    if (int r = stage_indices(c, N, [&](int32_t* h) { for (int t = 0; t < T; ++t) for (int i = 0; i < n; ++i) h[t * n + i] = (int32_t)(t * E + env_idx[i]); }, false)) return r;
+    if (int r = begin_pass(c, kArgPrefix, env_idx, n, E, "env index out of range", 1, N,
+                           [&](int32_t* h) { for (int t = 0; t < T; ++t) for (int i = 0; i < n; ++i) h[t * n + i] = (int32_t)(t * E + env_idx[i]); })) return r;
     HIPC(hipMemcpyAsync(c->rec_h0, h0, (size_t)n * H * 4, hipMemcpyHostToDevice, c->stream));      // (pageable source: copied at call time)
     InputSrc src = minibatch_src(c);
-    c->prof.phase = 1;
-    c->prof.sample_now = (c->prof.mb_count++ % c->prof.period) == 0;
     const bool impala = c->cfg.arch == MI_ARCH_IMPALA;
     net_forward(c, src, N, {.heads = false, .train = true});                                 // embedder only: feat = x
     // the sequence forward writes h_t over feat (the heads and their backward read it there); x is needed again for dW_ih and, for IMPALA,
@@ -1962,11 +1958,9 @@ int mi_minibatch_rec(mi_ctx* c, const int64_t* env_idx, int32_t n_env, const flo
     LossArgs a = loss_args(c, N, n_global, hp);      // (value_from_logits is 0 and fs_coef == 0 here by the checks above; stats is set to the ring slot below)
     a.hp.fs_coef = 0.f;                              // (+0: the check above also lets -0 through)
     const bool batch_terms = hp->x_entropy_coef != 0.f;
-    SegTab st{};
-    st.n_seg = 1; st.start[1] = N;
-    float* ring = c->stats_ring + (size_t)c->log_count * 32;
-    a.stats = ring;
-    loss_and_records(c, a, st, !batch_terms, 3, ring, c->fs_ring + c->log_count, c->loss_log + (size_t)c->log_count * 8);
+    const LogSlot s = log_slot(c);
+    a.stats = s.ring;
+    loss_and_records(c, a, seg_tab(&N, 1), !batch_terms, 3, s.ring, s.fsr, s.log);
     c->ring_args = a;
     c->log_count += 1;
     if (batch_terms) launch_loss_bwd(a, c->stream);
@@ -1977,9 +1971,7 @@ int mi_minibatch_rec(mi_ctx* c, const int64_t* env_idx, int32_t n_env, const flo
     linear_wgrad(c, c->rec_dgi, c->rec_x, 0, c->gru_g, c->gru_g + 2 * W, N, H, 3 * H);                    // dW_ih += dGI^T X ; db_ih += colsum dGI
     linear_wgrad(c, c->rec_dgh, c->rec_hm, 0, c->gru_g + W, c->gru_g + 2 * W + B, N, H, 3 * H);           // dW_hh += dGH^T HM ; db_hh += colsum dGH
     linear_dgrad(c, c->rec_dgi, c->gru_wih, impala ? c->rec_x : nullptr, c->dfeat, N, H, 3 * H);          // dX = dGI W_ih (* x > 0: the embedder's final ReLU)
-    c->bwd_from_dfeat = true;
-    net_backward(c, src, N);
-    c->bwd_from_dfeat = false;
+    net_backward(c, src, N, {.from_dfeat = true});
     c->rec_last = true;
     HIPC(hipGetLastError()); NETCHK(c);
     return 0;

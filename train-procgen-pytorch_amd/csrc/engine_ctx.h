@@ -19,7 +19,7 @@
 #include <mutex>
 #include <thread>
 
-#pragma clang diagnostic ignored "-Wc++20-designator"      // FwdOpts is filled by name at every call site
+#pragma clang diagnostic ignored "-Wc++20-designator"      // FwdOpts and BwdOpts are filled by name at every call site
 #define MI_INTERNAL __attribute__((visibility("hidden")))      // shared by the two files, not part of the library's ABI
 
 MI_INTERNAL extern thread_local std::string g_err;
@@ -162,7 +162,7 @@ struct mi_ctx {
     float *feat = nullptr, *hout = nullptr, *dY = nullptr, *dfeat = nullptr, *GC = nullptr, *GP[3] = {};
     int lse = 0; float* d_val = nullptr;                  // value_from_logits (common/policy.py:77-78); d_val: mi_forward's values [NB] in that mode
     float* slabs = nullptr; size_t slab_floats = 0;
-    void* sal_dc = nullptr; float* sal_dx = nullptr; const float* sal_src = nullptr;       // value saliency: conv-out gradient temp (bf16 mode), input gradient, where net_backward left block 1's gradient
+    void* sal_dc = nullptr; float* sal_dx = nullptr;       // value saliency: conv-out gradient temp (bf16 mode), input gradient
     long long slab_off[15] = {}; SlabDesc h_slab_desc[15] = {}; SlabDesc* d_slab_desc = nullptr; int slab_desc_n = 0, slab_desc_cached_n = -1;   // per-layer slab regions; ONE reduce launch per backward pass
     float *gemm_ws = nullptr, *col_ws = nullptr, *fs_scratch = nullptr, *fs_val = nullptr; size_t gemm_ws_floats = 0;      // split-K / column-sum workspaces: per context
     float* lut = nullptr;
@@ -183,11 +183,11 @@ struct mi_ctx {
     int32_t* s_act = nullptr; float *s_logp = nullptr, *s_val = nullptr; bool staged_valid = false;
     // recurrent rollout (GRU cell, never trained)
     bool gru_on = false; float *gru_wih = nullptr, *gru_whh = nullptr, *gru_bih = nullptr, *gru_bhh = nullptr, *h_state = nullptr, *h_masked = nullptr, *gru_gi = nullptr, *gru_gh = nullptr, *d_done = nullptr;
-    float *gru_x = nullptr, *gru_dg = nullptr; bool sal_keep_x = false, bwd_from_dfeat = false;      // value saliency through the GRU: the cell's input (embedder output), d gates; net_backward starts at dfeat
+    float *gru_x = nullptr, *gru_dg = nullptr;      // value saliency through the GRU: the cell's input (embedder output, FwdOpts::keep_gru_x), d gates
     // pinned host staging
     // index staging ring: a slot is rewritten only after the H2D copy that read it has completed
     static constexpr int IDX_RING = 32;
-    int32_t* h_idx_ring[IDX_RING] = {}; hipEvent_t idx_ev[IDX_RING] = {}; bool idx_used[IDX_RING] = {}; int idx_next = 0, idx_ev_deferred = -1;
+    int32_t* h_idx_ring[IDX_RING] = {}; hipEvent_t idx_ev[IDX_RING] = {}; bool idx_used[IDX_RING] = {}; int idx_next = 0;
     float* h_f = nullptr; int32_t* h_i = nullptr; size_t h_f_floats = 0;
     int multirank = 0;
     LossArgs pending = {}; int pending_n = -1;
@@ -204,15 +204,14 @@ struct mi_ctx {
     // gradients are needed by nobody before the optimizer step, so they run beside the backward pass instead of in front of it
     // (seven small launches + fc_tn: ~65 us of kernels per 2.7 ms minibatch, of which the update gets ~15 us back -- 64.6 -> 64.2 ms per
     // iteration, same-box A/B by the debug flag: fc_tn and the column maxima are real work that now shares the machine with fc_dgrad).
-    // Fork after heads_bwd, join in front of the slab sums.
+    // Fork after heads_bwd, join in front of the slab sums.  What the fork runs comes in with the pass: BwdOpts::side.
     hipStream_t side_stream = nullptr; hipEvent_t ev_side_fork = nullptr, ev_side_join = nullptr;
     bool side_on = true;           // mi_debug_flags bit 4 clears it (A/B tests)
-    struct SideJob { bool armed; LossArgs a; SegTab st; int mode; float* ring; float* fsr; float* log; } side = {};
     bool rollout_tail = true;          // bf16 inference passes of <= 256 samples run blocks 2 + 3 as one launch (mi_debug_flags bit 0 clears it: A/B tests)
-    float *fs_colmax = nullptr, fs_grad_coef = 0.f; int *fs_arg = nullptr, fs_G = 0;      // feature-sparsity gradient (fs_coef != 0): column maxima / first arg-max rows of the minibatch
+    float* fs_colmax = nullptr; int* fs_arg = nullptr;      // feature-sparsity gradient (BwdOpts::fs_coef != 0): column maxima / first arg-max rows of the minibatch
     // ... on more than one rank (multirank mode 1): per-column candidates for the max-all-reduce (MI_PTR_FS_KEYS), this rank's own copy, and
     // the global minibatch positions of the pending pass's rows (mi_minibatch_positions)
-    long long *fs_keys = nullptr, *fs_keys_local = nullptr; int32_t *d_gpos = nullptr, *h_gpos = nullptr; int gpos_n = -1; bool fs_global_pending = false, fs_global_apply = false;
+    long long *fs_keys = nullptr, *fs_keys_local = nullptr; int32_t *d_gpos = nullptr, *h_gpos = nullptr; int gpos_n = -1; bool fs_global_pending = false;
     // data-parallel collectives (RCCL over xGMI), SURVEY 8(e): one communicator per context, a side stream for the gradient all-reduce;
     // mi_comm_init / mi_comm_destroy may be repeated on one context, so what they allocate has a pool of its own
     ncclComm_t comm = nullptr, comm_grad = nullptr; int comm_world = 1, comm_rank = 0; hipStream_t comm_stream = nullptr; hipEvent_t ev_ar_ready = nullptr, ev_ar_done = nullptr;   // comm: main-stream collectives; comm_grad: the side stream's
@@ -279,9 +278,16 @@ MI_INTERNAL std::vector<uint16_t> host_to_bf16(const float* x, size_t n);      /
 // mi_debug_gru_seq issues the GEMMs of mi_minibatch_rec, mi_debug_step_latency the rollout step's forward pass: through the same functions
 struct InputSrc { const void* base; const int32_t* idx; long long first; };   // frames or obs rows
 // soff: first row of the activation buffers this pass may use (env groups of the pipelined rollout run side by side on
-// their own streams, each in its own rows); 0 everywhere else
-struct FwdOpts { bool recurrent = false; bool heads = true; bool train = false; int soff = 0; };
+// their own streams, each in its own rows); 0 everywhere else.  keep_gru_x: the GRU cell's input survives in gru_x (value saliency)
+struct FwdOpts { bool recurrent = false; bool heads = true; bool train = false; int soff = 0; bool keep_gru_x = false; };
 MI_INTERNAL void net_forward(mi_ctx* c, const InputSrc& src, int n, const FwdOpts& o);
+// What the side stream of a forking minibatch pass runs beside the backward pass (mi_ctx::side_stream): the records of the pass's segments
+// (loss arguments, segment table, finalize mode, the log slot's three rows) and the "read" marker of index-ring slot idx_slot.
+struct SideJob { LossArgs a; SegTab st; int mode; float* ring; float* fsr; float* log; int idx_slot = -1; };
+// A backward pass (engine.hip net_backward); the defaults are the plain pass from dY.  from_dfeat: d / d (embedder output) is in dfeat
+// already, no heads step.  fs_coef != 0: + fs_coef * d(feature sparsity) / d(block-3 output), over fs_groups row groups per segment, or
+// (fs_from_keys) from the all-reduced keys of multirank mode 1.  side: the job of a pass that forks the side stream, on the caller's stack.
+struct BwdOpts { bool from_dfeat = false; float fs_coef = 0.f; int fs_groups = 0; bool fs_from_keys = false; const SideJob* side = nullptr; };
 // mi_env_rollout (env_device.hip) chains T + 1 policy steps with its env steps
 MI_INTERNAL int issue_policy_step(mi_ctx* c, int32_t t, uint64_t seed, const float* du);
 MI_INTERNAL void linear_fwd(mi_ctx* c, const float* X, int relu_x, const float* W, const float* b, float* Y, int n, int in, int out, int relu_out, int x_bf16 = 0);
