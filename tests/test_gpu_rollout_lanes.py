@@ -1,4 +1,4 @@
-"""Rollout lanes (csrc/lanes.h, engine.hip g_lanes / mi_rollout_groups; DESIGN.md section 5 "Lanes"): the env groups of every engine in the process run
+"""Rollout lanes (csrc/lanes.h, rollout.hip g_lanes / mi_rollout_groups; DESIGN.md section 5 "Lanes"): the env groups of every engine in the process run
 on at most four shared high-priority streams.  Placement moves no kernel, no ordering edge and no buffer, so every number a pipelined
 rollout returns or leaves in the ring stays BIT-equal to the serial mi_put_obs + mi_rollout_step loop -- across lane reuse within an
 engine, with two engines alive, and whatever earlier engines of the process created or destroyed -- and the four lanes of an engine

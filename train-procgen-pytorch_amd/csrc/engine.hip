@@ -11,11 +11,14 @@
 //
 // File map:
 //   engine_ctx.h    mi_ctx and the structs it embeds, the error plumbing (fail, HIPC, ARG, NETCHK, JOIN, CUR), and the declarations of
-//                   the functions of this file that engine_ops.hip calls
+//                   the functions of this file and of rollout.hip that another file calls
 //   lanes.h         which stream an env group of the pipelined rollout runs on: the process-wide lane registry (plain C++, host-tested)
+//   group_worker.h  how a step reaches an env group's worker thread and its result comes back: the hand-off (plain C++, host-tested)
 //   devpool.h       who frees what: the pool that owns a context's device buffers, pinned buffers and events (plain C++, host-tested)
-//   engine.hip      create / destroy, rollout storage, profiler, the network program (forward_* / backward_* per mode), rollout steps and
-//                   env groups, minibatch passes, optimizer, GRU, collectives
+//   engine.hip      create / destroy, layout tables, parameter and field I/O, profiler, the network program (forward_* / backward_* per
+//                   mode), estimates, minibatch passes, optimizer, GRU training, collectives
+//   rollout.hip     rollout steps, env groups (lanes, workers, submit / wait, teardown), the staged entries (predict, saliency, commit,
+//                   forward) and the recurrent rollout's state: host code only, no kernel
 //   engine_ops.hip  mi_op_*, mi_debug_* (but mi_debug_flags: it sets production state) and mi_selftest_mfma: tests and micro-benchmarks only
 //
 // A minibatch pass in launch order (bf16 IMPALA at update size; minibatch_impl -> net_forward -> loss -> net_backward):
@@ -30,12 +33,11 @@
 //    9 join, slab sum          the remaining slab sum(s) into the flat gradient
 //   10 mi_optimizer_step       gradient norm + Adam (its own entry point)
 #include "engine_ctx.h"
-#include "lanes.h"
 
 thread_local std::string g_err;
-thread_local hipStream_t tl_stream = nullptr;
-thread_local float* tl_ws = nullptr;
-thread_local size_t tl_ws_floats = 0;
+__thread hipStream_t tl_stream = nullptr;
+__thread float* tl_ws = nullptr;
+__thread size_t tl_ws_floats = 0;
 const char* mi_last_error(void) { return g_err.c_str(); }
 
 // ---- the HIP backend of every pool (devpool.h), and the process-wide counts of what the pools hold: device allocations, pinned
@@ -76,50 +78,17 @@ static const char* kProfNames[PC_COUNT] = {
     "maxpool_fwd", "maxpool_bwd", "gemm", "slab_reduce",
     "resblock_fwd_(unused)", "resblock_fwd_16_16_32", "resblock_fwd_(unused)", "resblock_fwd_32_32_16", "resblock_fwd_32_32_8",
     "resblock_dgrad_(unused)", "resblock_dgrad_16_16_32", "resblock_dgrad_(unused)", "resblock_dgrad_32_32_16", "resblock_dgrad_32_32_8"};
-// one step of one env group, as the submitting thread hands it to the group's worker
-struct GroupJob { int t; const void* frames; size_t bytes; bool pull; bool have_rd, last; const float* u; unsigned long long seed; unsigned ticket; };
-struct GroupWorker {
-    std::thread th; std::mutex mu; std::condition_variable cv;
-    std::atomic<unsigned> posted{0}, done{0}; std::atomic<bool> sleeping{false}, quit{false};
-    GroupJob job{}; int rc = 0; std::string err;
-};
 
 // the few lines every entry point used to spell out by hand
-static inline char* obs_stage(mi_ctx* c) { return c->stage_frames ? (char*)c->stage_frames : (char*)c->stage_obs; }   // staged observations [NB]
 struct GemmWs { float* p; size_t floats; };
 static inline GemmWs gemm_ws(mi_ctx* c) { return tl_ws ? GemmWs{tl_ws, tl_ws_floats} : GemmWs{c->gemm_ws, c->gemm_ws_floats}; }   // split-K workspace (a group worker: its slice)
-// ---- rollout lanes (lanes.h): one registry per device, streams at the greatest priority the device offers.  The runtime keeps a pool of
-// hardware queues per stream priority; the default stream, torch's streams and every context's own stream live in the normal pool, so
-// the lanes are the only tenants of theirs and four of them sit on four queues even where the normal pool's four are all taken.
-static constexpr int MAX_LANE_DEVICES = 64;
-static LaneRegistry* const g_lanes = new LaneRegistry[MAX_LANE_DEVICES];      // (never destructed: a context may be destroyed during process exit)
-static void* lane_make(int device, int, int* prio) {
-    int dev0 = 0, least = 0, greatest = 0;
-    hipStream_t s = nullptr;
-    if (hipGetDevice(&dev0) != hipSuccess || hipSetDevice(device) != hipSuccess) return nullptr;
-    const bool ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&
-                    hipStreamCreateWithPriority(&s, hipStreamNonBlocking, greatest) == hipSuccess &&
-                    hipStreamGetPriority(s, prio) == hipSuccess;
-    hipSetDevice(dev0);
-    if (!ok && s) { hipStreamDestroy(s); s = nullptr; }
-    return s;
-}
-static void lane_drop(void* s) { hipStreamDestroy((hipStream_t)s); }
-
 // the first env group's lane when there is one (idle during an update, joined by JOIN(); one hardware queue less in use), else an own stream
 static hipStream_t side_stream(mi_ctx* c) {
-    hipStream_t ss = (c->n_groups > 0 && c->gs[0]) ? c->gs[0] : c->side_stream;
+    hipStream_t ss = (c->n_groups > 0 && c->grp[0].stream) ? c->grp[0].stream : c->side_stream;
     if (!ss) { hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking); ss = c->side_stream; }
     return ss;
 }
 static int64_t gru_count(const mi_ctx* c) { return 2 * (int64_t)3 * c->H * c->H + 2 * (int64_t)3 * c->H; }      // floats of the four GRU tensors
-// the four GRU tensors {w_ih, w_hh, b_ih, b_hh}: device pointer, offset in the one vector of their gradients / Adam moments, length
-struct GruTensor { float* p; size_t off, len; };
-struct GruTensors { GruTensor t[4]; };
-static inline GruTensors gru_tensors(mi_ctx* c) {
-    const size_t H = c->H, W = 3 * H * H, B = 3 * H;
-    return GruTensors{{{c->gru_wih, 0, W}, {c->gru_whh, W, W}, {c->gru_bih, 2 * W, B}, {c->gru_bhh, 2 * W + B, B}}};
-}
 
 // ------------------------------------------------------------------------------------------ layout tables
 static void add_tensor(mi_ctx* c, const std::string& name, int64_t n, int kind, int co, int ci, int64_t& ref, int64_t dev) {
@@ -382,16 +351,10 @@ static int ctx_build(mi_ctx* c) {
 
 // The one teardown, of a context mi_create could not finish as of a live one.
 static void ctx_release(mi_ctx* c) {
-    for (int g = 0; g < mi_ctx::MAX_GROUPS; ++g)
-        if (c->gw[g]) {
-            GroupWorker* w = c->gw[g];
-            w->quit.store(true); { std::lock_guard<std::mutex> lk(w->mu); } w->cv.notify_one();
-            w->th.join(); delete w; c->gw[g] = nullptr;
-        }
-    for (int g = 0; g < mi_ctx::MAX_GROUPS; ++g) if (c->gs[g]) hipStreamSynchronize(c->gs[g]);
+    rollout_groups_stop(c);          // the groups' workers joined, then their streams synchronised
     if (c->stream) hipStreamSynchronize(c->stream);
     prof_harvest(c);
-    g_lanes[c->cfg.device].give_back(c, lane_drop);      // (waited for above; the streams go when the last holder of the device returns its lanes)
+    rollout_lanes_return(c);         // (waited for above; the streams go when the last holder of the device returns its lanes)
     mi_comm_destroy(c);
     // Nothing is let go while anything on the device may still read it: the side stream, the null stream's fills and copies and
     // streams of the caller's are not among the waits above.  (The hand-written teardown had this wait implicitly: its first
@@ -550,7 +513,7 @@ static hipEvent_t prof_event(mi_ctx* c) {
 static void prof_harvest(mi_ctx* c) {
     if (c->prof.pend.empty()) return;
     hipStreamSynchronize(c->stream);
-    for (int g = 0; g < mi_ctx::MAX_GROUPS; ++g) if (c->gs[g]) hipStreamSynchronize(c->gs[g]);
+    for (const RolloutGroup& G : c->grp) if (G.stream) hipStreamSynchronize(G.stream);
     for (auto& p : c->prof.pend) {
         float ms = 0.f;
         hipEventElapsedTime(&ms, p.a, p.b);
@@ -727,7 +690,7 @@ static void net_gru(mi_ctx* c, int n, int soff, bool keep_x) {
     launch_gru_gates(c->gru_gi + 3 * o, c->gru_gh + 3 * o, c->h_masked + o, c->h_state + o, c->feat + o, n, H, CUR(c));
 }
 
-static void fc_refresh(mi_ctx* c) {
+void fc_refresh(mi_ctx* c) {
     if (c->bf && !c->fc_packed_valid) {
         launch_repack_all(c->params, c->banks, c->d_bank_desc, c->n_banks, c->convs.empty() ? nullptr : c->params + c->convs[0].w_off,
                           c->convs.empty() ? nullptr : c->c1_bank, c->params + c->fc.w_off, c->fc_wp, c->fc_wt, c->H, CUR(c));
@@ -1040,7 +1003,7 @@ static const float* backward_impala_bf16(mi_ctx* c, const InputSrc& src, int n, 
 }
 
 // backward from dY (n x (A+1)), or from dfeat (o.from_dfeat); gradients accumulate into c->grads.  Returns what backward_* return.
-static const float* net_backward(mi_ctx* c, const InputSrc& src, int n, const BwdOpts& o) {
+const float* net_backward(mi_ctx* c, const InputSrc& src, int n, const BwdOpts& o) {
     const bool impala = c->cfg.arch == MI_ARCH_IMPALA;
     // (value saliency of a recurrent policy and mi_minibatch_rec come in with d / d (embedder output) in c->dfeat already: no heads step)
     if (!o.from_dfeat) {
@@ -1050,492 +1013,6 @@ static const float* net_backward(mi_ctx* c, const InputSrc& src, int n, const Bw
     if (!impala) return backward_mlp(c, n);
     if (!c->bf) return backward_impala_fp32(c, src, n, o);
     return backward_impala_bf16(c, src, n, o);
-}
-
-// ------------------------------------------------------------------------------------------ predict / forward
-// the caller's uniforms for rows [row0, row0 + rows), if given: *du = where the sampler reads them (null: it draws its own)
-static int upload_u(mi_ctx* c, const float* u, hipStream_t st, int row0, int rows, const float** du) {
-    *du = nullptr;
-    if (u) { HIPC(hipMemcpyAsync(c->d_u + row0, u, (size_t)rows * 4, hipMemcpyHostToDevice, st)); *du = c->d_u + row0; }
-    return 0;
-}
-// act / logp / value of the E envs to the caller through the pinned h_i / h_f, one stream wait: a field with a null device source is skipped,
-// one with a null destination is copied to the host but not handed out; extra: one more copy to the caller in front of the wait
-static int read_back_staged(mi_ctx* c, const int32_t* d_act, const float* d_logp, const float* d_val, int64_t* act_out, float* logp_out, float* value_out, void* extra_out = nullptr, const void* d_extra = nullptr, size_t extra_bytes = 0) {
-    const size_t E = c->E;
-    if (d_act) HIPC(hipMemcpyAsync(c->h_i, d_act, E * 4, hipMemcpyDeviceToHost, c->stream));
-    if (d_logp) HIPC(hipMemcpyAsync(c->h_f, d_logp, E * 4, hipMemcpyDeviceToHost, c->stream));
-    if (d_val) HIPC(hipMemcpyAsync(c->h_f + E, d_val, E * 4, hipMemcpyDeviceToHost, c->stream));
-    if (extra_out) HIPC(hipMemcpyAsync(extra_out, d_extra, extra_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    if (d_act && act_out) for (size_t e = 0; e < E; ++e) act_out[e] = c->h_i[e];
-    if (d_logp && logp_out) memcpy(logp_out, c->h_f, E * 4);
-    if (d_val && value_out) memcpy(value_out, c->h_f + E, E * 4);
-    return 0;
-}
-// the packed {act, logp, value} x n a head kernel wrote to pinned memory, to the caller (the bootstrap step has no action / log-prob)
-static inline void unpack_step(const float* pk, int n, bool last, int64_t* act_out, float* logp_out, float* value_out) {
-    for (int e = 0; e < n; ++e) {
-        if (act_out && !last) act_out[e] = (int64_t)pk[3 * e];
-        if (logp_out && !last) logp_out[e] = pk[3 * e + 1];
-        if (value_out) value_out[e] = pk[3 * e + 2];
-    }
-}
-// The last workgroup of the head kernel publishes the ticket after all results (h_pack) are visible to the host and all reads of
-// h_rd / u are done: spinning on it returns ~5 us earlier than hipStreamSynchronize (12.9 -> 8.1 us for launch + wait of a small
-// kernel, scratch/synclat.hip), 257 times per iteration.  gone(), probed every 2^20 spins: the kernel can no longer publish (finished
-// without a ticket, or failed); the caller then falls back to the stream wait, which reports the error.
-template <typename Gone>
-static inline bool wait_ticket(const volatile unsigned* flag, unsigned want, Gone gone) {
-    for (unsigned long long spin = 0; spin < (1ull << 34); ++spin) {
-        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == want) return true;
-        __builtin_ia32_pause();
-        if ((spin & 0xfffff) == 0xfffff && gone()) break;
-    }
-    return false;
-}
-
-// the launches of a policy step on ring slot t (forward, sample; du: the sampler's uniforms on the device or null), nothing else
-int issue_policy_step(mi_ctx* c, int32_t t, uint64_t seed, const float* du) {
-    const int E = c->E;
-    InputSrc src{obs_ring(c), nullptr, (long long)t * E};
-    c->prof.phase = 0;
-    net_forward(c, src, E, {.recurrent = true});
-    const bool last = (t == c->T);
-    launch_sample(c->hout, E, c->A, du, seed, (unsigned long long)t * E, last ? nullptr : c->act + (size_t)t * E,
-                  last ? nullptr : c->logp + (size_t)t * E, c->value + (size_t)t * E, c->stream, c->lse);
-    HIPC(hipGetLastError()); NETCHK(c);
-    return 0;
-}
-int mi_policy_step(mi_ctx* c, int32_t t, uint64_t seed, const float* u, int64_t* act_out, float* logp_out, float* value_out) {
-    ARG(c, "null"); JOIN(c); ARG(t >= 0 && t <= c->T, "t out of range");
-    const int E = c->E;
-    const float* du;
-    if (int r = upload_u(c, u, c->stream, 0, E, &du)) return r;
-    if (int r = issue_policy_step(c, t, seed, du)) return r;
-    const bool last = (t == c->T);
-    if (!act_out && !logp_out && !value_out) { if (u) HIPC(hipStreamSynchronize(c->stream)); return 0; }
-    const size_t o = (size_t)t * E;
-    return read_back_staged(c, (act_out && !last) ? c->act + o : nullptr, (logp_out && !last) ? c->logp + o : nullptr, value_out ? c->value + o : nullptr, act_out, logp_out, value_out);
-}
-
-int mi_rollout_step(mi_ctx* c, int32_t t, const float* rew_prev, const float* done_prev, uint64_t seed, const float* u,
-                    int64_t* act_out, float* logp_out, float* value_out) {
-    ARG(c, "null"); JOIN(c); ARG(t >= 0 && t <= c->T, "t out of range");
-    const int E = c->E;
-    if (rew_prev || done_prev) {
-        ARG(rew_prev && done_prev && t >= 1, "rew_prev/done_prev come together and belong to step t-1");
-        // pinned, device-visible staging: the head kernel reads {rew, done} straight from host memory and writes its
-        // packed result straight back -- no copy kernels on the step's critical path (the stream sync below fences both)
-        memcpy(c->h_rd, rew_prev, (size_t)E * 4); memcpy(c->h_rd + E, done_prev, (size_t)E * 4);
-        if (c->gru_on) HIPC(hipMemcpyAsync(c->d_done, c->h_rd + E, (size_t)E * 4, hipMemcpyHostToDevice, c->stream));
-    }
-    const bool have_rd = rew_prev != nullptr;
-    InputSrc src{obs_ring(c), nullptr, (long long)t * E};
-    const float* du;
-    if (int r = upload_u(c, u, c->stream, 0, E, &du)) return r;
-    c->prof.phase = 0;
-    net_forward(c, src, E, {.recurrent = true, .heads = false});
-    const bool last = (t == c->T);
-    launch_heads_sample(c->feat, c->params + c->wh_off, c->params + c->bh_off, E, c->H, c->A, du, seed, (unsigned long long)t * E,
-                        last ? nullptr : c->act + (size_t)t * E, last ? nullptr : c->logp + (size_t)t * E, c->value + (size_t)t * E,
-                        c->h_pack, nullptr, have_rd ? c->h_rd : nullptr, have_rd ? c->rew + (size_t)(t - 1) * E : nullptr,
-                        have_rd ? c->done + (size_t)(t - 1) * E : nullptr, c->stream, c->d_done_ctr, c->h_flag, ++c->roll_ticket, c->lse);
-    HIPC(hipGetLastError()); NETCHK(c);
-    if (!wait_ticket(c->h_flag, c->roll_ticket, [&] { return hipStreamQuery(c->stream) != hipErrorNotReady; })) HIPC(hipStreamSynchronize(c->stream));
-    unpack_step(c->h_pack, E, last, act_out, logp_out, value_out);
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------ pipelined rollout (env groups)
-// The reference's loop (agents/ppo.py:225-236) is strictly serial per step: obs -> H2D -> forward -> D2H act -> env.step.  An env's
-// next frame depends only on its OWN action, so the E envs split into G contiguous groups whose chains
-//     upload frames(t, g) -> forward + sample (t, g) -> actions on the host -> [env.step of group g on the host] -> upload frames(t+1, g)
-// are independent: group g's upload (PCIe, ~37 us for 128 frames) and forward run on stream gs[g] while the host waits for / steps
-// another group.  Per group: its own stream, rows [e0, e0 + E/G) of the activation buffers, its slice of the pinned hand-off
-// buffers, its own completion ticket.  Numbers are those of mi_rollout_step (same kernels, same Philox counters t*E + e).
-static void worker_drain(GroupWorker* w) {       // until the worker has issued everything that was posted to it
-    if (!w) return;
-    while (w->done.load(std::memory_order_acquire) != w->posted.load(std::memory_order_acquire)) __builtin_ia32_pause();
-}
-int join_groups(mi_ctx* c) {
-    for (int g = 0; g < c->n_groups; ++g) {
-        if (!c->gs[g]) continue;
-        worker_drain(c->gw[g]);
-        if (c->g_dirty[g]) {
-            HIPC(hipEventRecord(c->ev_join[g], c->gs[g]));
-            HIPC(hipStreamWaitEvent(c->main_stream, c->ev_join[g], 0));
-            c->g_dirty[g] = false;
-        }
-        c->g_forked[g] = false;          // the next submit of this group orders itself behind the main stream again
-    }
-    c->groups_live = false;
-    return 0;
-}
-
-// the device half of a group step, on the group's worker thread (tl_stream = the group's stream)
-static int group_issue(mi_ctx* c, int g, const GroupJob& j) {
-    const int E = c->E, ng = E / c->n_groups, e0 = g * ng;
-    hipStream_t st = tl_stream;
-    if (j.frames) {
-        char* dst = obs_ring(c) + ((size_t)j.t * E + e0) * c->obs_bytes_per_env;
-        // One upload at a time.  Uploads of several groups issued together share the PCIe link and all finish late and TOGETHER: the
-        // groups' chains then stay in lock-step and every step pays the shared-link copy time (two stable regimes were measured at
-        // E = 256, G = 4: 107 and 135-138 us per policy step).  Each upload reserves the link for bytes / rate from the moment the previous
-        // reservation ends (a few us of spinning on the worker thread, only when groups bunch), which puts the chains out of step again.
-        if (c->copy_rate_bytes_per_us > 0) {
-            const int64_t gap = (int64_t)((double)j.bytes * 1000.0 / c->copy_rate_bytes_per_us);
-            const auto clk = [] { return (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-            int64_t slot = c->copy_slot_ns.load(), start;
-            do { const int64_t now = clk(); start = now > slot ? now : slot; } while (!c->copy_slot_ns.compare_exchange_weak(slot, start + gap));
-            while (clk() < start) __builtin_ia32_pause();
-        }
-        // page-locked, device-visible frames are PULLED by a kernel on the group's stream: a DMA copy in front of the first conv costs the
-        // hand-over from the compute queue to the copy engine and back on top of the transfer (xfer.hip pull_i32_kernel)
-        if (j.pull) launch_pull_bytes(j.frames, dst, j.bytes, st);
-        else HIPC(hipMemcpyAsync(dst, j.frames, j.bytes, hipMemcpyHostToDevice, st));
-    }
-    float* h_rd = c->h_rd + 2 * e0;      // this group's {rew[ng], done[ng]} (pinned, device-visible), filled by the submitting thread
-    if (j.have_rd && c->gru_on) HIPC(hipMemcpyAsync(c->d_done + e0, h_rd + ng, (size_t)ng * 4, hipMemcpyHostToDevice, st));
-    const float* du;
-    if (int r = upload_u(c, j.u, st, e0, ng, &du)) return r;
-    InputSrc src{obs_ring(c), nullptr, (long long)j.t * E + e0};
-    net_forward(c, src, ng, {.heads = false, .soff = e0});
-    const float* hin = c->feat + (size_t)e0 * c->H;          // what the heads read: the embedder output, or h' of a GRU context
-    if (c->gru_on) {
-        // the GRU cell as ONE launch (gru_cell.hip gru_step_kernel): input state from hidden-ring slot t (mi_rec_begin's upload at t == 0, else
-        // step t-1's output), masked by the group's done (mi_rec_begin's at t == 0, else the copy above); h' -> h_state rows, and slot t+1
-        // unless this is the bootstrap step.  The heads read h' from h_state (the cell cannot overwrite feat, which its other workgroups read).
-        const size_t H = c->H;
-        float* slot = c->h_ring + ((size_t)j.t * E + e0) * H;
-        launch_gru_step(c->feat + (size_t)e0 * H, slot, c->d_done + e0, c->gru_wih, c->gru_whh, c->gru_bih, c->gru_bhh, c->h_state + (size_t)e0 * H,
-                        j.last ? nullptr : slot + (size_t)E * H, ng, c->H, st);
-        hin = c->h_state + (size_t)e0 * H;
-    }
-    const size_t o = (size_t)j.t * E + e0;
-    launch_heads_sample(hin, c->params + c->wh_off, c->params + c->bh_off, ng, c->H, c->A, du, j.seed, (unsigned long long)j.t * E + e0,
-                        j.last ? nullptr : c->act + o, j.last ? nullptr : c->logp + o, c->value + o, c->h_pack + 3 * e0, nullptr,
-                        j.have_rd ? h_rd : nullptr, j.have_rd ? c->rew + o - E : nullptr, j.have_rd ? c->done + o - E : nullptr, st,
-                        c->d_done_ctr + 1 + g, c->h_flag + 1 + g, j.ticket, c->lse);
-    HIPC(hipGetLastError());
-    if (const char* lf = mi_launch_failed_take()) return fail(-4, lf);      // (this worker thread's launchers)
-    return 0;
-}
-static void group_worker_main(mi_ctx* c, int g) {
-    GroupWorker* w = c->gw[g];
-    hipSetDevice(c->cfg.device);
-    tl_stream = c->gs[g];
-    tl_ws_floats = c->gemm_ws_floats / mi_ctx::MAX_GROUPS; tl_ws = c->gemm_ws + (size_t)g * tl_ws_floats;     // concurrent groups: disjoint split-K slabs
-    unsigned seen = 0;
-    for (;;) {
-        int spins = 0;
-        while (w->posted.load(std::memory_order_acquire) == seen && !w->quit.load()) {
-            if (++spins < 40000) __builtin_ia32_pause();
-            else {                                   // idle for a few hundred us (update phase): sleep until the next post
-                std::unique_lock<std::mutex> lk(w->mu);
-                w->sleeping.store(true);
-                w->cv.wait_for(lk, std::chrono::milliseconds(50), [&] { return w->posted.load() != seen || w->quit.load(); });
-                w->sleeping.store(false);
-                spins = 0;
-            }
-        }
-        if (w->quit.load()) return;
-        seen = w->posted.load(std::memory_order_acquire);
-        w->rc = group_issue(c, g, w->job);
-        if (w->rc) w->err = g_err;
-        w->done.store(seen, std::memory_order_release);
-    }
-}
-
-int mi_rollout_groups(mi_ctx* c, int32_t n_groups) {
-    ARG(c, "null"); ARG(n_groups >= 1 && n_groups <= mi_ctx::MAX_GROUPS, "1 .. 4 groups");
-    ARG(c->E % n_groups == 0, "n_envs must be divisible by the number of groups");
-    for (int g = 0; g < c->n_groups; ++g) ARG(!c->g_busy[g], "a group step is still in flight: mi_rollout_wait it first");
-    JOIN(c);
-    void* lane[mi_ctx::MAX_GROUPS]; int prio[mi_ctx::MAX_GROUPS];
-    const int have = [&] { int k = 0; while (k < mi_ctx::MAX_GROUPS && c->gs[k]) ++k; return k; }();
-    if (n_groups > have && !g_lanes[c->cfg.device].borrow(c, n_groups, c->cfg.device, lane_make, lane, prio))
-        return fail(-2, "no stream for an env group (hipStreamCreateWithPriority failed)");
-    for (int g = 0; g < n_groups; ++g)
-        if (!c->gs[g]) {
-            DevPool::Group both(c->pool);
-            HIPC(c->pool.event(&c->ev_fork[g], hipEventDisableTiming));
-            HIPC(c->pool.event(&c->ev_join[g], hipEventDisableTiming));
-            both.keep = true;
-            c->gs[g] = (hipStream_t)lane[g]; c->gs_prio[g] = prio[g];
-            c->gw[g] = new GroupWorker();
-            c->gw[g]->th = std::thread(group_worker_main, c, g);
-        }
-    c->n_groups = n_groups;
-    return 0;
-}
-
-int mi_rollout_lane_info(mi_ctx* c, int32_t* n, int32_t* prio, uint64_t* stream_id) {
-    ARG(c && n && prio && stream_id, "null");
-    *n = 0;
-    for (int g = 0; g < c->n_groups && c->gs[g]; ++g) { prio[g] = c->gs_prio[g]; stream_id[g] = (uint64_t)(uintptr_t)c->gs[g]; *n = g + 1; }
-    return 0;
-}
-
-int mi_rollout_submit(mi_ctx* c, int32_t t, int32_t g, const void* frames, size_t bytes, const float* rew_prev, const float* done_prev,
-                      uint64_t seed, const float* u) {
-    ARG(c, "null"); ARG(t >= 0 && t <= c->T, "t out of range"); ARG(g >= 0 && g < c->n_groups, "group out of range");
-    ARG(c->gs[g], "call mi_rollout_groups first"); ARG(!c->g_busy[g], "this group's previous step has not been waited for");
-    ARG(c->pending_n < 0, "a multirank minibatch is pending");
-    const int E = c->E, ng = E / c->n_groups, e0 = g * ng;
-    ARG(!frames || bytes == (size_t)ng * c->obs_bytes_per_env, "frames byte count != (E / groups) * bytes_per_env");
-    if (rew_prev || done_prev) ARG(rew_prev && done_prev && t >= 1, "rew_prev/done_prev come together and belong to step t-1");
-    if (c->gru_on) {
-        ARG(c->h_ring && (t > 0 || c->g_rec_ok[g]), "recurrent rollout: call mi_rec_begin before the groups' first step (t == 0) of every rollout");
-        if (t == 0) c->g_rec_ok[g] = false;
-    }
-    GroupWorker* w = c->gw[g];
-    worker_drain(w);
-    if (!c->g_forked[g]) {               // first step since the main stream last worked: parameters / packed banks must be in place
-        fc_refresh(c);
-        HIPC(hipEventRecord(c->ev_fork[g], c->main_stream));
-        HIPC(hipStreamWaitEvent(c->gs[g], c->ev_fork[g], 0));
-        c->g_forked[g] = true;
-    }
-    c->groups_live = true; c->g_dirty[g] = true;
-    const bool have_rd = rew_prev != nullptr;
-    if (have_rd) { float* h_rd = c->h_rd + 2 * e0; memcpy(h_rd, rew_prev, (size_t)ng * 4); memcpy(h_rd + ng, done_prev, (size_t)ng * 4); }
-    const bool last = (t == c->T);
-    bool pull = false;
-    // Pull only what is latency-bound: measured per policy step, E = 64 in 2 groups (393 KB each) 73-76 us pulled vs 84-86 us copied,
-    // E = 256 in 4 groups (786 KB each, four pulls competing) 121-135 vs 108-112 us -- shader reads of host memory move fewer bytes per
-    // second than the copy engine, so above 512 KB the DMA's hand-over is the smaller price.
-    if (frames && !c->no_pull && bytes <= (512u << 10) && (bytes & 15) == 0 && ((uintptr_t)frames & 15) == 0) {      // device-visible pinned memory? (asked once per buffer)
-        auto it = c->pull_ok.find(frames);
-        if (it == c->pull_ok.end()) {
-            hipPointerAttribute_t at{};
-            const bool ok = hipPointerGetAttributes(&at, frames) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer == frames;
-            if (!ok) (void)hipGetLastError();
-            if (c->pull_ok.size() > 64) c->pull_ok.clear();
-            it = c->pull_ok.emplace(frames, ok).first;
-        }
-        pull = it->second;
-    }
-    w->job = GroupJob{t, frames, bytes, pull, have_rd, last, u, seed, ++c->g_ticket[g]};
-    w->posted.fetch_add(1, std::memory_order_seq_cst);
-    if (w->sleeping.load()) { { std::lock_guard<std::mutex> lk(w->mu); } w->cv.notify_one(); }
-    c->g_busy[g] = true; c->g_last[g] = last;
-    return 0;
-}
-
-int mi_rollout_wait(mi_ctx* c, int32_t g, int64_t* act_out, float* logp_out, float* value_out) {
-    ARG(c, "null"); ARG(g >= 0 && g < c->n_groups, "group out of range"); ARG(c->g_busy[g], "nothing submitted for this group");
-    const int ng = c->E / c->n_groups, e0 = g * ng;
-    const unsigned want = c->g_ticket[g];
-    GroupWorker* w = c->gw[g];
-    const bool seen = wait_ticket(c->h_flag + 1 + g, want, [&] { return w->done.load() == w->posted.load() && hipStreamQuery(c->gs[g]) != hipErrorNotReady; });   // issued, finished, no ticket
-    worker_drain(w);
-    c->g_busy[g] = false;
-    if (w->rc) { const int rc = w->rc; w->rc = 0; return fail(rc, "group worker: " + w->err); }
-    if (!seen) HIPC(hipStreamSynchronize(c->gs[g]));
-    NETCHK(c);
-    unpack_step(c->h_pack + 3 * e0, ng, c->g_last[g], act_out, logp_out, value_out);
-    return 0;
-}
-
-int mi_predict_staged(mi_ctx* c, const void* obs, size_t bytes, uint64_t seed, uint64_t counter, const float* u,
-                      int64_t* act_out, float* logp_out, float* value_out) {
-    ARG(c && obs, "null"); JOIN(c);
-    const int E = c->E;
-    ARG(bytes == (size_t)E * c->obs_bytes_per_env, "obs byte count != E * bytes_per_env");
-    void* stage = obs_stage(c);
-    HIPC(hipMemcpyAsync(stage, obs, bytes, hipMemcpyHostToDevice, c->stream));
-    const float* du;
-    if (int r = upload_u(c, u, c->stream, 0, E, &du)) return r;
-    InputSrc src{stage, nullptr, 0};
-    net_forward(c, src, E, {.recurrent = true});
-    launch_sample(c->hout, E, c->A, du, seed, counter, c->s_act, c->s_logp, c->s_val, c->stream, c->lse);
-    HIPC(hipGetLastError()); NETCHK(c);
-    if (int r = read_back_staged(c, c->s_act, c->s_logp, c->s_val, act_out, logp_out, value_out)) return r;
-    c->staged_valid = true;
-    return 0;
-}
-
-// IPL.predict(obs, greedy=True) (agents/IPL.py:82-94): mi_predict_staged with the first arg-max in place of the sampler
-int mi_predict_greedy(mi_ctx* c, const void* obs, size_t bytes, int64_t* act_out, float* logp_out, float* value_out) {
-    ARG(c && obs, "null"); JOIN(c);
-    ARG(!c->gru_on, "mi_predict_greedy: a recurrent context (mi_set_gru) is not supported"); ARG(!c->lse, "mi_predict_greedy: value_from_logits is not supported");
-    const int E = c->E;
-    ARG(bytes == (size_t)E * c->obs_bytes_per_env, "obs byte count != E * bytes_per_env");
-    void* stage = obs_stage(c);
-    HIPC(hipMemcpyAsync(stage, obs, bytes, hipMemcpyHostToDevice, c->stream));
-    InputSrc src{stage, nullptr, 0};
-    net_forward(c, src, E, {});
-    launch_ipl_greedy(c->hout, E, c->A, c->s_act, c->s_logp, c->s_val, c->stream);
-    HIPC(hipGetLastError()); NETCHK(c);
-    if (int r = read_back_staged(c, c->s_act, c->s_logp, c->s_val, act_out, logp_out, value_out)) return r;
-    c->staged_valid = true;
-    return 0;
-}
-
-// PPO.predict_w_value_saliency (agents/ppo.py:83-94): predict + d value / d observation.  grad_out: IMPALA [E][64][64][3] (NHWC,
-// wrt the k/255 float frames), MLP [E][obs_dim].  Runs the training-mode forward and the whole backward pass with dY = e_value on
-// the E staged observations; the parameter gradients it produces on the way are discarded (the gradient buffer is zeroed again),
-// so it must not be called between mi_minibatch and mi_optimizer_step of an accumulating update.
-int mi_value_saliency(mi_ctx* c, const void* obs, size_t bytes, uint64_t seed, uint64_t counter, const float* u,
-                      int64_t* act_out, float* logp_out, float* value_out, float* grad_out) {
-    ARG(c && obs && grad_out, "null"); JOIN(c);
-    ARG(c->pending_n < 0, "a multirank minibatch is pending");
-    const int E = c->E;
-    const bool impala = c->cfg.arch == MI_ARCH_IMPALA;
-    ARG(bytes == (size_t)E * c->obs_bytes_per_env, "obs byte count != E * bytes_per_env");
-    void* stage = obs_stage(c);
-    HIPC(hipMemcpyAsync(stage, obs, bytes, hipMemcpyHostToDevice, c->stream));
-    const float* du;
-    if (int r = upload_u(c, u, c->stream, 0, E, &du)) return r;
-    InputSrc src{stage, nullptr, 0};
-    c->prof.phase = 0;
-    const bool rec = c->gru_on;
-    if (rec && !c->gru_x) { DevPool::Group both(c->pool); HIPC(c->pool.dev(&c->gru_x, (size_t)E * c->H)); HIPC(c->pool.dev(&c->gru_dg, (size_t)E * 3 * c->H)); both.keep = true; }
-    net_forward(c, src, E, {.recurrent = rec, .train = true, .keep_gru_x = rec});          // recurrent: h' = GRU(embedder output, h (1 - done)) as a policy step does, heads on h'
-    launch_sample(c->hout, E, c->A, du, seed, counter, c->s_act, c->s_logp, c->s_val, c->stream, c->lse);
-    const float* g1;      // where the backward pass leaves the gradient of the first layer's output
-    if (rec) {
-        // value = w_v . h' + b_v: back through the GRU cell to its input x (common/model.py:219-225 under autograd, agents/ppo.py:88-89), then
-        // through the embedder's final ReLU (IMPALA) -- d value / d x = dgates W_ih -- and on down the usual backward pass from dfeat
-        // (value_from_logits: value = logsumexp(W_pi h' + b_pi), so the seed into the cell is per row, softmax(logits) W_pi; dfeat carries it)
-        if (c->lse) {
-            launch_lse_hidden_seed(c->hout, c->params + c->wh_off, c->dfeat, E, c->H, c->A, c->stream);
-            launch_gru_value_bwd(c->gru_gi, c->gru_gh, c->h_masked, c->dfeat, c->gru_dg, E, c->H, c->stream, 1);
-        } else
-        launch_gru_value_bwd(c->gru_gi, c->gru_gh, c->h_masked, c->params + c->wh_off + (size_t)c->A * c->H, c->gru_dg, E, c->H, c->stream);
-        linear_dgrad(c, c->gru_dg, c->gru_wih, impala ? c->gru_x : nullptr, c->dfeat, E, c->H, 3 * c->H);
-        g1 = net_backward(c, src, E, {.from_dfeat = true});
-    } else {
-        if (c->lse) launch_lse_value_seed(c->hout, c->dY, E, c->A, c->stream);
-        else launch_value_seed(c->dY, E, c->A, c->stream);
-        g1 = net_backward(c, src, E, {});
-    }
-    ARG(g1, "backward did not reach the first layer");
-    const size_t gfloats = impala ? (size_t)E * 64 * 64 * 3 : (size_t)E * c->cfg.obs_dim;
-    if (!c->sal_dx) HIPC(c->pool.dev(&c->sal_dx, impala ? (size_t)c->NB * 64 * 64 * 3 : (size_t)c->NB * c->cfg.obs_dim));
-    if (impala) {
-        const void* dC = g1;
-        if (c->bf) {                                       // the conv-output gradient is not materialised in bf16 mode: rebuild it from the pooled one
-            if (!c->sal_dc) HIPC(c->pool.dev_raw(&c->sal_dc, (size_t)c->NB * 64 * 64 * 16 * 2 + 256));
-            launch_maxpool_bwd_bf16(g1, c->blk[0].PI, c->sal_dc, E, 64, 16, c->stream);
-            dC = c->sal_dc;
-        }
-        launch_conv1_input_grad(dC, c->bf, c->params + c->convs[0].w_off, c->sal_dx, E, c->stream);
-    } else {
-        linear_dgrad(c, g1, c->params + c->mlp[0].w_off, nullptr, c->sal_dx, E, c->mlp[0].in, c->mlp[0].out);
-    }
-    launch_fill(c->grads, c->n_params, 0.f, c->stream);    // discard the parameter gradients of this pass
-    HIPC(hipGetLastError()); NETCHK(c);
-    if (int r = read_back_staged(c, c->s_act, c->s_logp, c->s_val, act_out, logp_out, value_out, grad_out, c->sal_dx, gfloats * 4)) return r;
-    c->staged_valid = true;
-    return 0;
-}
-
-int mi_commit_staged(mi_ctx* c, int32_t t) {
-    ARG(c, "null"); JOIN(c); ARG(t >= 0 && t <= c->T, "t out of range"); ARG(c->staged_valid, "nothing staged: call mi_predict_staged first");
-    const size_t E = c->E, ob = E * c->obs_bytes_per_env;
-    HIPC(hipMemcpyAsync(obs_ring(c) + (size_t)t * ob, obs_stage(c), ob, hipMemcpyDeviceToDevice, c->stream));
-    if (t < c->T) {
-        HIPC(hipMemcpyAsync(c->act + t * E, c->s_act, E * 4, hipMemcpyDeviceToDevice, c->stream));
-        HIPC(hipMemcpyAsync(c->logp + t * E, c->s_logp, E * 4, hipMemcpyDeviceToDevice, c->stream));
-    }
-    HIPC(hipMemcpyAsync(c->value + t * E, c->s_val, E * 4, hipMemcpyDeviceToDevice, c->stream));
-    return 0;
-}
-
-int mi_set_gru(mi_ctx* c, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh) {
-    ARG(c && w_ih && w_hh && b_ih && b_hh, "null"); JOIN(c);
-    const size_t H = c->H, E = c->E;
-    if (!c->gru_wih) {
-        DevPool& m = c->pool; DevPool::Group all(m);
-        HIPC(m.dev(&c->gru_wih, 3 * H * H)); HIPC(m.dev(&c->gru_whh, 3 * H * H)); HIPC(m.dev(&c->gru_bih, 3 * H)); HIPC(m.dev(&c->gru_bhh, 3 * H));
-        HIPC(m.dev(&c->h_state, E * H)); HIPC(m.dev(&c->h_masked, E * H)); HIPC(m.dev(&c->gru_gi, E * 3 * H)); HIPC(m.dev(&c->gru_gh, E * 3 * H));
-        HIPC(m.dev(&c->d_done, E));
-        all.keep = true;
-    }
-    const GruTensors g = gru_tensors(c);
-    const float* src[4] = {w_ih, w_hh, b_ih, b_hh};
-    for (int k = 0; k < 4; ++k) HIPC(hipMemcpy(g.t[k].p, src[k], g.t[k].len * 4, hipMemcpyHostToDevice));
-    c->gru_on = true;
-    return 0;
-}
-int mi_rec_state(mi_ctx* c, const float* hidden, const float* done) {
-    ARG(c, "null"); JOIN(c); ARG(c->gru_on, "no GRU set: call mi_set_gru first");
-    const size_t H = c->H, E = c->E;
-    if (hidden) HIPC(hipMemcpyAsync(c->h_state, hidden, E * H * 4, hipMemcpyHostToDevice, c->stream));
-    if (done) HIPC(hipMemcpyAsync(c->d_done, done, E * 4, hipMemcpyHostToDevice, c->stream));
-    else HIPC(hipMemsetAsync(c->d_done, 0, E * 4, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    return 0;
-}
-int mi_rec_begin(mi_ctx* c, const float* hidden, const float* done) {
-    ARG(c, "null"); JOIN(c); ARG(c->gru_on, "no GRU set: call mi_set_gru first");
-    const size_t H = c->H, E = c->E;
-    if (!c->h_ring) {                                     // only contexts that run grouped recurrent rollouts pay for the ring (67 MB at T = E = H = 256)
-        DevPool& m = c->pool; DevPool::Group all(m);
-        HIPC(m.dev(&c->h_ring, (size_t)(c->T + 1) * E * H));
-        HIPC(m.pinned(&c->h_rec_stage, (E * H + E) * 4, hipHostMallocDefault));
-        HIPC(m.event(&c->ev_rec, hipEventDisableTiming));
-        all.keep = true;
-    } else
-        HIPC(hipEventSynchronize(c->ev_rec));             // the previous call's upload has left the staging buffer (long since, normally)
-    if (hidden) {
-        memcpy(c->h_rec_stage, hidden, E * H * 4);
-        HIPC(hipMemcpyAsync(c->h_ring, c->h_rec_stage, E * H * 4, hipMemcpyHostToDevice, c->stream));
-        HIPC(hipMemcpyAsync(c->h_state, c->h_ring, E * H * 4, hipMemcpyDeviceToDevice, c->stream));
-    } else
-        HIPC(hipMemcpyAsync(c->h_ring, c->h_state, E * H * 4, hipMemcpyDeviceToDevice, c->stream));
-    if (done) {
-        memcpy(c->h_rec_stage + E * H, done, E * 4);
-        HIPC(hipMemcpyAsync(c->d_done, c->h_rec_stage + E * H, E * 4, hipMemcpyHostToDevice, c->stream));
-    } else
-        HIPC(hipMemsetAsync(c->d_done, 0, E * 4, c->stream));
-    HIPC(hipEventRecord(c->ev_rec, c->stream));
-    for (bool& b : c->g_rec_ok) b = true;
-    return 0;
-}
-int mi_get_hidden_ring(mi_ctx* c, int32_t t0, int32_t t1, float* out) {
-    ARG(c && out, "null"); JOIN(c); ARG(c->h_ring, "no hidden ring: mi_rec_begin has not run");
-    ARG(t0 >= 0 && t0 < t1 && t1 <= c->T + 1, "need 0 <= t0 < t1 <= T + 1");
-    const size_t slot = (size_t)c->E * c->H;
-    HIPC(hipMemcpyAsync(out, c->h_ring + (size_t)t0 * slot, (size_t)(t1 - t0) * slot * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    return 0;
-}
-int mi_get_hidden(mi_ctx* c, float* hidden) {
-    ARG(c && hidden, "null"); JOIN(c); ARG(c->gru_on, "no GRU set");
-    HIPC(hipMemcpyAsync(hidden, c->h_state, (size_t)c->E * c->H * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-static int forward_common(mi_ctx* c, const void* obs, int32_t n, bool recurrent, float* logp_all, float* value, float* feat);
-int mi_forward_rec(mi_ctx* c, const void* obs, float* logp_all, float* value, float* hidden_out) {
-    ARG(c && obs, "null"); ARG(c->gru_on, "no GRU set");
-    int r = forward_common(c, obs, c->E, true, logp_all, value, hidden_out);   // feat == h' after the GRU
-    return r;
-}
-int mi_forward(mi_ctx* c, const void* obs, int32_t n, float* logp_all, float* value, float* feat) {
-    return forward_common(c, obs, n, false, logp_all, value, feat);
-}
-static int forward_common(mi_ctx* c, const void* obs, int32_t n, bool recurrent, float* logp_all, float* value, float* feat) {
-    ARG(c && obs, "null"); JOIN(c); ARG(n >= 1 && n <= c->NB, "n must be in [1, max_batch]");
-    c->staged_valid = false;
-    void* stage = obs_stage(c);
-    HIPC(hipMemcpyAsync(stage, obs, (size_t)n * c->obs_bytes_per_env, hipMemcpyHostToDevice, c->stream));
-    InputSrc src{stage, nullptr, 0};
-    net_forward(c, src, n, {.recurrent = recurrent});
-    launch_logp_all(c->hout, n, c->A, c->d_lp, c->lse ? c->d_val : nullptr, c->stream, c->lse);
-    HIPC(hipGetLastError()); NETCHK(c);
-    if (logp_all) HIPC(hipMemcpyAsync(logp_all, c->d_lp, (size_t)n * c->A * 4, hipMemcpyDeviceToHost, c->stream));
-    if (feat) HIPC(hipMemcpyAsync(feat, c->feat, (size_t)n * c->H * 4, hipMemcpyDeviceToHost, c->stream));
-    std::vector<float> h;
-    if (value && c->lse) HIPC(hipMemcpyAsync(value, c->d_val, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));      // (column A of hout is fc_value's output, not the value)
-    else if (value) { h.resize((size_t)n * (c->A + 1)); HIPC(hipMemcpyAsync(h.data(), c->hout, h.size() * 4, hipMemcpyDeviceToHost, c->stream)); }
-    HIPC(hipStreamSynchronize(c->stream));
-    if (value && !c->lse) for (int k = 0; k < n; ++k) value[k] = h[(size_t)k * (c->A + 1) + c->A];
-    return 0;
 }
 
 // ------------------------------------------------------------------------------------------ estimates

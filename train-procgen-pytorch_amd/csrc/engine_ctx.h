@@ -1,6 +1,8 @@
-// Internal header of the engine's translation units (engine.hip: context, network program, C ABI; engine_ops.hip: the op-level
-// and debug entry points that only tests and micro-benchmarks call; env_device.hip: the device-resident envs and their mi_env_* entries; env_resident.hip: their one-launch rollout; env_evaluate.hip: their one-launch evaluation).  It holds what both need and nothing else: the context, the error
-// plumbing, and the few engine.hip functions the op code calls.
+// Internal header of the engine's translation units (engine.hip: context, network program, update entries; rollout.hip: rollout steps,
+// env groups, staged and recurrent entries; engine_ops.hip: the op-level and debug entry points that only tests and micro-benchmarks
+// call; env_device.hip: the device-resident envs and their mi_env_* entries; env_resident.hip: their one-launch rollout;
+// env_evaluate.hip: their one-launch evaluation).  It holds what they share and nothing else: the context, the error plumbing, and the
+// few functions of engine.hip and rollout.hip that another file calls.
 #pragma once
 #include "common.h"
 #include "devpool.h"
@@ -18,6 +20,9 @@
 #include <deque>
 #include <mutex>
 #include <thread>
+#pragma GCC visibility push(hidden)      // (the member functions of a template would be exported otherwise)
+#include "group_worker.h"
+#pragma GCC visibility pop
 
 #pragma clang diagnostic ignored "-Wc++20-designator"      // FwdOpts and BwdOpts are filled by name at every call site
 #define MI_INTERNAL __attribute__((visibility("hidden")))      // shared by the two files, not part of the library's ABI
@@ -25,9 +30,11 @@
 MI_INTERNAL extern thread_local std::string g_err;
 // A worker thread of the pipelined rollout issues one env group's pass on that group's stream with that group's slice of the split-K
 // workspace: the network program reads both through these thread-local overrides (null on every other thread: the context's own).
-MI_INTERNAL extern thread_local hipStream_t tl_stream;
-MI_INTERNAL extern thread_local float* tl_ws;
-MI_INTERNAL extern thread_local size_t tl_ws_floats;
+// (__thread, not thread_local: a file other than the defining one reaches an extern thread_local through an init-function check, and for
+// these three, which have none, that check is a hidden weak undefined symbol -- its address is not null once the library is loaded)
+MI_INTERNAL extern __thread hipStream_t tl_stream;
+MI_INTERNAL extern __thread float* tl_ws;
+MI_INTERNAL extern __thread size_t tl_ws_floats;
 #define CUR(c) (tl_stream ? tl_stream : (c)->stream)
 static inline int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
@@ -133,6 +140,19 @@ struct DeviceEnv {
     int32_t* s_act = nullptr; float *s_obs = nullptr, *s_rew = nullptr, *s_done = nullptr;
 };
 
+// ---- one env group of the pipelined rollout (rollout.hip).  GroupJob: one step of the group, as the submitting thread hands it to the
+// group's worker (group_worker.h: one host thread per group issues that group's copies + launches; a step is ~9 API calls = ~30 us of
+// host time).  stream: a lane borrowed from the process-wide registry (lanes.h, g_lanes in rollout.hip), never a stream of the
+// context's own.  forked: the stream is ordered behind the main stream's work; dirty: it has work the main stream has not been ordered
+// behind yet; busy / last / ticket: the step in flight; rec_ok: mi_rec_begin has run since the group last started a rollout (t == 0).
+struct GroupJob { int t; const void* frames; size_t bytes; bool pull; bool have_rd, last; const float* u; unsigned long long seed; unsigned ticket; };
+struct RolloutGroup {
+    hipStream_t stream = nullptr; int prio = 0; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    bool forked = false, busy = false, last = false, dirty = false, rec_ok = false; unsigned ticket = 0;
+    GroupWorker<GroupJob, mi_ctx>* worker = nullptr;
+};
+static constexpr int MAX_LANE_DEVICES = 64;      // one lane registry per device (rollout.hip)
+
 MI_INTERNAL const DevPool::Backend* hip_pool();      // engine.hip: hipMalloc / hipHostMalloc / hipEventCreateWithFlags and their frees, counted
 struct mi_ctx {
     Profiler prof;
@@ -194,10 +214,7 @@ struct mi_ctx {
     // pipelined rollout (mi_rollout_submit / mi_rollout_wait): contiguous env groups, each on its own stream with its own rows of the
     // activation buffers, so that one group's frame upload + forward runs beside the host's wait for another group's actions
     static constexpr int MAX_GROUPS = 4;
-    // gs[g]: a lane borrowed from the process-wide registry (lanes.h, g_lanes in engine.hip), never a stream of the context's own
-    int n_groups = 1; hipStream_t main_stream = nullptr, gs[MAX_GROUPS] = {}; int gs_prio[MAX_GROUPS] = {}; hipEvent_t ev_fork[MAX_GROUPS] = {}, ev_join[MAX_GROUPS] = {};
-    bool g_forked[MAX_GROUPS] = {}, g_busy[MAX_GROUPS] = {}, g_last[MAX_GROUPS] = {}, g_dirty[MAX_GROUPS] = {}; unsigned g_ticket[MAX_GROUPS] = {}; bool groups_live = false;
-    struct GroupWorker* gw[MAX_GROUPS] = {};      // one host thread per group issues that group's copies + launches (a step is ~9 API calls = ~30 us of host time)
+    int n_groups = 1; hipStream_t main_stream = nullptr; RolloutGroup grp[MAX_GROUPS]; bool groups_live = false;
     std::atomic<int64_t> copy_slot_ns{0}; double copy_rate_bytes_per_us = 40000.0;      // uploads of the env groups take turns on the PCIe link (group_issue)
     std::unordered_map<const void*, bool> pull_ok; bool no_pull = false;      // frame buffers a kernel may read (mi_debug_flags bit 2: always DMA)
     // Side stream of a minibatch pass: the logged statistics (feature-sparsity metric, loss records) and embedder.fc's weight / bias
@@ -219,8 +236,8 @@ struct mi_ctx {
     std::string net_err; std::mutex net_err_mu;   // set by the (void) network program on an unsupported launch (any thread); every entry point reports it as -4
     // recurrent policies on the pipelined rollout (mi_rec_begin, group_issue): hidden ring [T+1][E][H] -- slot t = the input hidden state of step t (slot 0 from
     // mi_rec_begin, slot t+1 written by step t's fused cell); pinned staging of mi_rec_begin's upload {hidden [E][H], done [E]} and the event
-    // that frees it; g_rec_ok[g]: mi_rec_begin has run since group g last started a rollout (t == 0)
-    float *h_ring = nullptr, *h_rec_stage = nullptr; hipEvent_t ev_rec = nullptr; bool g_rec_ok[MAX_GROUPS] = {};
+    // that frees it (RolloutGroup::rec_ok: mi_rec_begin has run since the group last started a rollout)
+    float *h_ring = nullptr, *h_rec_stage = nullptr; hipEvent_t ev_rec = nullptr;
     // GRU training (mi_gru_train, mi_minibatch_rec: algo ppo-pure): gradients and Adam moments of the four GRU tensors as ONE vector
     // {w_ih, w_hh, b_ih, b_hh} beside the flat ones, the partial sums of the global gradient norm (128 flat + 128 GRU), and the buffers of a
     // recurrent minibatch pass, max_batch rows each: the embedder output x (the sequence forward overwrites feat with h_t), gi, the saved
@@ -271,7 +288,7 @@ static inline ResidentNet resident_net(const mi_ctx* c) {
 MI_INTERNAL std::string net_err_take(mi_ctx* c);                 // (the network program also runs on the env-group worker threads: guarded)
 MI_INTERNAL void net_err_set(mi_ctx* c, const std::string& m);
 MI_INTERNAL void sae_release(mi_ctx* c);                         // (defined in sae.hip; mi_destroy releases a live SAE through it)
-MI_INTERNAL int join_groups(mi_ctx* c);
+MI_INTERNAL int join_groups(mi_ctx* c);                          // (defined in rollout.hip: JOIN)
 MI_INTERNAL void to_device_layout(const TensorDesc& t, const float* ref, float* dev);
 MI_INTERNAL void to_ref_layout(const TensorDesc& t, const float* dev, float* ref);
 MI_INTERNAL std::vector<uint16_t> host_to_bf16(const float* x, size_t n);      // (defined in engine_ops.hip; mi_create builds the uint8 -> bf16 table with it)
@@ -288,7 +305,22 @@ struct SideJob { LossArgs a; SegTab st; int mode; float* ring; float* fsr; float
 // already, no heads step.  fs_coef != 0: + fs_coef * d(feature sparsity) / d(block-3 output), over fs_groups row groups per segment, or
 // (fs_from_keys) from the all-reduced keys of multirank mode 1.  side: the job of a pass that forks the side stream, on the caller's stack.
 struct BwdOpts { bool from_dfeat = false; float fs_coef = 0.f; int fs_groups = 0; bool fs_from_keys = false; const SideJob* side = nullptr; };
-// mi_env_rollout (env_device.hip) chains T + 1 policy steps with its env steps
+// ---- engine.hip functions rollout.hip calls: the value saliency runs a whole backward pass (returns where it left the gradient of the
+// first layer's output); a group's first step since the main stream last worked puts the packed bf16 filter images in place
+MI_INTERNAL const float* net_backward(mi_ctx* c, const InputSrc& src, int n, const BwdOpts& o);
+MI_INTERNAL void fc_refresh(mi_ctx* c);
+static inline char* obs_stage(mi_ctx* c) { return c->stage_frames ? (char*)c->stage_frames : (char*)c->stage_obs; }   // staged observations [NB]
+// the four GRU tensors {w_ih, w_hh, b_ih, b_hh}: device pointer, offset in the one vector of their gradients / Adam moments, length
+struct GruTensor { float* p; size_t off, len; };
+struct GruTensors { GruTensor t[4]; };
+static inline GruTensors gru_tensors(mi_ctx* c) {
+    const size_t H = c->H, W = 3 * H * H, B = 3 * H;
+    return GruTensors{{{c->gru_wih, 0, W}, {c->gru_whh, W, W}, {c->gru_bih, 2 * W, B}, {c->gru_bhh, 2 * W + B, B}}};
+}
+// ---- rollout.hip functions other files call.  ctx_release: the groups' workers joined, then their streams synchronised; later, the
+// lanes given back to the registry.  mi_env_rollout (env_device.hip) chains T + 1 policy steps with its env steps
+MI_INTERNAL void rollout_groups_stop(mi_ctx* c);
+MI_INTERNAL void rollout_lanes_return(mi_ctx* c);
 MI_INTERNAL int issue_policy_step(mi_ctx* c, int32_t t, uint64_t seed, const float* du);
 MI_INTERNAL void linear_fwd(mi_ctx* c, const float* X, int relu_x, const float* W, const float* b, float* Y, int n, int in, int out, int relu_out, int x_bf16 = 0);
 MI_INTERNAL void linear_dgrad(mi_ctx* c, const float* dY, const float* W, const float* mask, float* dX, int n, int in, int out, int x_bf16 = 0);

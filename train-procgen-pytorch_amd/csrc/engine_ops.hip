@@ -437,12 +437,12 @@ __global__ void __launch_bounds__(64) lane_probe_kernel(int iters) {
 int mi_debug_lane_probe(mi_ctx* c, int32_t mask, int32_t iters, float* usec) {
     ARG(c && usec, "null"); JOIN(c);
     ARG(mask > 0 && mask < (1 << c->n_groups) && iters >= 1, "mask (bits of this context's groups) / iters");
-    for (int g = 0; g < c->n_groups; ++g) ARG(c->gs[g] && !c->g_busy[g], "call mi_rollout_groups first; no group step in flight");
+    for (int g = 0; g < c->n_groups; ++g) ARG(c->grp[g].stream && !c->grp[g].busy, "call mi_rollout_groups first; no group step in flight");
     if (iters > 4096) iters = 4096;
-    for (int g = 0; g < c->n_groups; ++g) if (mask >> g & 1) HIPC(hipStreamSynchronize(c->gs[g]));
+    for (int g = 0; g < c->n_groups; ++g) if (mask >> g & 1) HIPC(hipStreamSynchronize(c->grp[g].stream));
     const auto t0 = std::chrono::steady_clock::now();
-    for (int g = 0; g < c->n_groups; ++g) if (mask >> g & 1) lane_probe_kernel<<<1, 64, 0, c->gs[g]>>>(iters);
-    for (int g = 0; g < c->n_groups; ++g) if (mask >> g & 1) HIPC(hipStreamSynchronize(c->gs[g]));
+    for (int g = 0; g < c->n_groups; ++g) if (mask >> g & 1) lane_probe_kernel<<<1, 64, 0, c->grp[g].stream>>>(iters);
+    for (int g = 0; g < c->n_groups; ++g) if (mask >> g & 1) HIPC(hipStreamSynchronize(c->grp[g].stream));
     const auto t1 = std::chrono::steady_clock::now();
     HIPC(hipGetLastError());
     *usec = (float)(std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count() / 1e3);

@@ -59,7 +59,7 @@ void launch_gru_gates(const float* gi, const float* gh, const float* hm, float* 
     if (n <= 0) return;
     hipLaunchKernelGGL(gru_gates_kernel, dim3((n * H + 255) / 256), dim3(256), 0, st, gi, gh, hm, h_out, feat_out, n, H);
 }
-// One GRU step of an env group in ONE launch (the pipelined rollout's cell, engine.hip group_issue; common/model.py:212-225 for one step):
+// One GRU step of an env group in ONE launch (the pipelined rollout's cell, rollout.hip group_issue; common/model.py:212-225 for one step):
 //   hm = h_in (1 - done[row]);  gi = W_ih x + b_ih;  gh = W_hh hm + b_hh;  r, z, n as gru_gates_kernel;  h' = (1 - z) n + z hm  -> h_out, h_copy
 // It replaces mask_rows + two linear_fwd + gru_gates.  Workgroup = 4 waves = hidden units j0 .. j0+3 (one per wave) x 64 rows (one per
 // lane); its 24 weight rows (gates r, z, n of W_ih and W_hh for those units) sit in LDS and are read as wave-uniform broadcasts, the

@@ -6,7 +6,7 @@
 // queues; four lanes per process, created at the greatest stream priority, have the high-priority pool to themselves.
 //
 // This file is the bookkeeping only, plain C++ over opaque handles (the stand-alone host test drives it with fake ones): which lanes
-// exist, who holds which, which one a new group gets.  engine.hip supplies the two callbacks that create and destroy a stream.
+// exist, who holds which, which one a new group gets.  rollout.hip supplies the two callbacks that create and destroy a stream.
 #pragma once
 #include <mutex>
 #include <utility>
