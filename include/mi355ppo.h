@@ -419,6 +419,37 @@ int mi_op_ipl_loss(mi_ctx* ctx, int32_t n, int32_t A, const float* hout, const f
 /* op-level test hook: the greedy action of n head rows hout [n][A+1] -> act [n] (lowest index among equal maxima) */
 int mi_op_ipl_greedy(mi_ctx* ctx, int32_t n, int32_t A, const float* hout, int32_t* act_out);
 
+/* ---- policy distillation (the reference's distill.py:128-234: a student is fitted with MSELoss + Adam to the normalised logits a trained
+ *      teacher gives on the observations the STUDENT visited) on plain contexts: the same rings, network passes and parameter vectors as
+ *      PPO; mi_get/set_params, mi_get/set_adam_state, mi_get_grads and mi_loss_log_read are reused unchanged.  The loss arithmetic is fp32
+ *      in both precision modes.  Non-recurrent, one rank; the value head takes no part (its gradient is exactly 0).
+ *      mi_distill_label(data, teacher): the teacher's forward pass -- its own network program and precision -- over all T * E observation
+ *      rows of data's ring, read in place in chunks of the teacher's max_batch; the normalised log-probabilities (the rows mi_forward
+ *      hands out, bit for bit) go to data's target ring [T * E][A], allocated by the first call.  data == teacher is allowed (the
+ *      validation set labels itself).  The teacher's stream waits for data's ring and data's stream for the labels; asynchronous.
+ *      mi_distill_minibatch(student, idx, n, n_global): one minibatch on ring rows idx (flat t*E + e) of the student's own ring and target
+ *      ring: forward, lp = the twice-normalised log-probabilities, loss = sum (lp - y)^2 / (n_global * A), backward through both
+ *      normalisations.  Gradients ACCUMULATE into the flat gradient buffer like mi_minibatch's; one record {loss, 0, 0, 0, loss, 0, 0, 0}
+ *      is appended to the loss log.
+ *      mi_distill_loss(student, data, loss_out): forward only -- the student on all of data's rows in chunks of the student's max_batch
+ *      against data's targets, one fp64 sum in a fixed order -> the mean over T * E * A elements.  Changes neither the gradient buffer nor
+ *      the loss log.  Synchronises.
+ *      Refused, each message starting with the entry's name, before any launch and before the loss log, the index ring or the gradient
+ *      buffer change: a context with a GRU set on either side; value_from_logits on the student; multirank mode != 0 or an armed gradient
+ *      exchange; two contexts of different observation kind, obs_dim, n_actions or device; n > max_batch; mi_distill_minibatch /
+ *      mi_distill_loss before any label call has filled the target ring they read. */
+int mi_distill_label(mi_ctx* data, mi_ctx* teacher);
+int mi_distill_minibatch(mi_ctx* student, const int64_t* idx, int32_t n, int32_t n_global);
+int mi_distill_loss(mi_ctx* student, mi_ctx* data, float* loss_out);
+/* read-back of data's target ring, [T * E][A] floats (n = their number), for tests and for callers that keep the labels; synchronises */
+int mi_distill_targets(mi_ctx* data, float* out, int64_t n);
+/* mi_optimizer_step with the caller's Adam eps (the distiller: torch's default 1e-8).  max_grad_norm = +inf switches the clip off: the
+ * kernel's coefficient min(max_grad_norm / (norm + 1e-6), 1) is then exactly 1. */
+int mi_optimizer_step_eps(mi_ctx* ctx, float lr, float max_grad_norm, float eps, int32_t adam_step, float* grad_norm_out);
+/* op-level test hook: only the distillation loss kernels on caller arrays -- hout [n][A+1], target [n][A].  Out (either may be NULL): rec8
+ * the record, dY [n][A+1] the backward seed (value column exactly 0).  n in [1, 65536], A in [1, 16], the mean over n_global * A. */
+int mi_op_distill_loss(mi_ctx* ctx, int32_t n, int32_t A, const float* hout, const float* target, int32_t n_global, float* rec8_out, float* dY_out);
+
 /* ---- data-parallel collectives inside the boundary: RCCL over xGMI, one communicator per context (SURVEY 8(b) mi_allreduce_grads,
  *      8(e) C1-C3).  Rank 0 obtains a 128-byte id (mi_comm_unique_id) and hands it to every rank by any host channel
  *      (mi355/dist.py uses torch.distributed.broadcast_object_list); every rank then calls mi_comm_init(id, rank, world).

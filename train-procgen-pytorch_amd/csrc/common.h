@@ -237,6 +237,20 @@ void launch_ipl_next_seed(const float* g_next, float* dY, int n, int A, hipStrea
 void launch_ipl_shift_idx(const int32_t* idx, int32_t* idx2, int n, int shift, hipStream_t st);
 void launch_ipl_greedy(const float* hout, int n, int A, int32_t* act, float* logp, float* value, hipStream_t st);
 
+// ---------------------------------------------------------------- distill.hip: the distillation loss (the reference's distill.py)
+struct DistillArgs {
+    const float* hout;        // [n][A+1] of the student's pass
+    const int32_t* idx;       // [n] target rows, or null: row s itself
+    const float* target;      // [rows][A] the teacher's normalised log-probabilities
+    float* dY;                // [n][A+1] seed of the backward pass (value column exactly 0), or null: forward only
+    double* partial;          // [distill_blocks(n)] per-block sum of (lp - y)^2
+    int n, A;
+    float scale;              // 1 / (n_global * A): MSELoss's mean over all elements
+};
+int  distill_blocks(int n);
+// loss kernel + finaliser: rec8 (or null) <- {loss, 0, 0, 0, loss, 0, 0, 0} with loss = sum * inv_count; acc (or null): running fp64 sum
+void launch_distill_loss(const DistillArgs& a, double inv_count, float* rec8, double* acc, int acc_reset, hipStream_t st);
+
 // ---------------------------------------------------------------- estimates.hip: GAE, advantage normalisation
 void launch_gae(const float* rew, const float* done, const float* value, float* adv, float* ret, int T, int E,
                 float gamma, float lmbda, int use_gae, hipStream_t st);

@@ -1324,9 +1324,11 @@ int mi_ipl_read_pred(mi_ctx* c, float* pred_out, float* rew_out, int32_t n) {
     return 0;
 }
 
-int mi_optimizer_step(mi_ctx* c, float lr, float max_norm, int32_t step, float* gnorm_out) {
+// clip + Adam + zero_grad with the caller's eps.  max_norm = +inf switches the clip off: adam_kernel's coef = min(max_norm / (norm + 1e-6), 1)
+// is then inf > 1 -> exactly 1 for every finite norm, and g * 1 is g.
+static int optimizer_step(mi_ctx* c, float lr, float max_norm, float eps, int32_t step, float* gnorm_out) {
     ARG(c, "null"); JOIN(c); ARG(step >= 1, "adam_step is 1-based");
-    const AdamScalars a = adam_scalars(lr, step);
+    const AdamScalars a = adam_scalars(lr, step, eps);
     if (c->ar_inflight) { HIPC(hipStreamWaitEvent(c->stream, c->ev_ar_done, 0)); c->ar_inflight = false; }
     c->ar_issued = false; c->ar_armed = false;
     if (c->gru_train) {
@@ -1352,6 +1354,118 @@ int mi_optimizer_step(mi_ctx* c, float lr, float max_norm, int32_t step, float* 
         HIPC(hipStreamSynchronize(c->stream));
         *gnorm_out = c->h_f[0];
     }
+    return 0;
+}
+int mi_optimizer_step(mi_ctx* c, float lr, float max_norm, int32_t step, float* gnorm_out) {
+    return optimizer_step(c, lr, max_norm, 1e-5f, step, gnorm_out);
+}
+int mi_optimizer_step_eps(mi_ctx* c, float lr, float max_norm, float eps, int32_t step, float* gnorm_out) {
+    ARG(eps >= 0.f, "mi_optimizer_step_eps: eps must not be negative (or NaN)");
+    ARG(max_norm > 0.f, "mi_optimizer_step_eps: max_grad_norm must be positive (+inf: no clipping)");
+    return optimizer_step(c, lr, max_norm, eps, step, gnorm_out);
+}
+
+// ------------------------------------------------------------------------------------------ policy distillation (distill.py)
+// The reference's distill.py:164-204 on the device: a teacher context labels every observation row of a data context's ring with its
+// normalised log-probabilities (mi_distill_label), the student is fitted to them with MSELoss (mi_distill_minibatch: forward, loss
+// kernels of distill.hip, backward; mi_optimizer_step_eps is its Adam) and scored forward-only (mi_distill_loss).
+#define DST_ARG(entry, cond, msg) do { if (!(cond)) return fail(-1, std::string(entry ": ") + msg); } while (0)
+// what both sides of a distillation call must be: non-recurrent, on one rank, with no gradient exchange armed
+#define DST_SIDE(entry, c, who)                                                                                          \
+    do {                                                                                                                 \
+        DST_ARG(entry, !(c)->gru_on, "a recurrent context (mi_set_gru) is not supported (" who ")");                     \
+        DST_ARG(entry, (c)->multirank == 0, "multirank mode must be 0 (" who "): distillation runs on one rank");        \
+        DST_ARG(entry, !(c)->ar_armed && !(c)->ar_inflight, "an armed gradient exchange (mi_allreduce_arm) is not supported (" who ")"); \
+    } while (0)
+// the two contexts of a call read the same kind of observation rows and name the same actions, on one device
+#define DST_PAIR(entry, a, b, who_b)                                                                                     \
+    do {                                                                                                                 \
+        DST_ARG(entry, ((a)->frames != nullptr) == ((b)->frames != nullptr), "the " who_b " reads another kind of observation (frames / rows) than the data context holds"); \
+        DST_ARG(entry, (a)->obs_bytes_per_env == (b)->obs_bytes_per_env, "obs_dim of the " who_b " differs from the data context's"); \
+        DST_ARG(entry, (a)->A == (b)->A, "n_actions of the " who_b " differs from the data context's");                   \
+        DST_ARG(entry, (a)->cfg.device == (b)->cfg.device, "the " who_b " lives on another device than the data context"); \
+    } while (0)
+static int distill_alloc(mi_ctx* c, bool target) {
+    DevPool& m = c->pool; DevPool::Group all(m);
+    if (target && !c->dst_target) HIPC(m.dev(&c->dst_target, (size_t)c->T * c->E * c->A));
+    if (!target && !c->dst_partial) { HIPC(m.dev(&c->dst_partial, (size_t)distill_blocks(c->NB))); HIPC(m.dev(&c->dst_acc, 1)); }
+    all.keep = true;
+    return 0;
+}
+// b's stream waits for what a's stream holds now (the events go back to the runtime on every return path, as in mi_copy_params)
+static int order_behind(mi_ctx* a, mi_ctx* b) {
+    if (a->stream == b->stream) return 0;
+    hipEvent_t ev = nullptr;
+    DevPool evs(hip_pool());
+    HIPC(evs.event(&ev, hipEventDisableTiming));
+    HIPC(hipEventRecord(ev, a->stream));
+    HIPC(hipStreamWaitEvent(b->stream, ev, 0));
+    return 0;
+}
+int mi_distill_label(mi_ctx* data, mi_ctx* teacher) {
+    DST_ARG("mi_distill_label", data && teacher, "null context"); JOIN(data); JOIN(teacher);
+    DST_SIDE("mi_distill_label", data, "data"); DST_SIDE("mi_distill_label", teacher, "teacher");
+    DST_PAIR("mi_distill_label", data, teacher, "teacher");
+    if (int r = distill_alloc(data, true)) return r;
+    if (int r = order_behind(data, teacher)) return r;          // the rollout that filled data's ring
+    const int rows = data->T * data->E;
+    for (int r0 = 0; r0 < rows; r0 += teacher->NB) {
+        const int n = std::min(teacher->NB, rows - r0);
+        net_forward(teacher, InputSrc{obs_ring(data), nullptr, (long long)r0}, n, {});
+        // the rows mi_forward hands out (same launcher, same arguments), written at their place in the ring instead of d_lp
+        launch_logp_all(teacher->hout, n, teacher->A, data->dst_target + (size_t)r0 * data->A, teacher->lse ? teacher->d_val : nullptr, teacher->stream, teacher->lse);
+    }
+    HIPC(hipGetLastError()); NETCHK(teacher);
+    if (int r = order_behind(teacher, data)) return r;          // data's passes read the labels; its next rollout must not overtake the teacher's reads
+    data->dst_labelled = true;
+    return 0;
+}
+int mi_distill_targets(mi_ctx* data, float* out, int64_t n) {
+    DST_ARG("mi_distill_targets", data && out, "null argument"); JOIN(data);
+    DST_ARG("mi_distill_targets", data->dst_labelled, "no mi_distill_label has filled this context's target ring");
+    DST_ARG("mi_distill_targets", n == (int64_t)data->T * data->E * data->A, "n != T * E * n_actions");
+    HIPC(hipMemcpyAsync(out, data->dst_target, (size_t)n * 4, hipMemcpyDeviceToHost, data->stream));
+    HIPC(hipStreamSynchronize(data->stream));
+    return 0;
+}
+int mi_distill_minibatch(mi_ctx* c, const int64_t* idx, int32_t n, int32_t n_global) {
+    DST_ARG("mi_distill_minibatch", c && idx, "null argument"); JOIN(c);
+    DST_SIDE("mi_distill_minibatch", c, "student");
+    DST_ARG("mi_distill_minibatch", !c->lse, "value_from_logits on the student is not supported");
+    DST_ARG("mi_distill_minibatch", n <= c->NB, "n > max_batch");
+    DST_ARG("mi_distill_minibatch", n >= 1, "n must be at least 1"); DST_ARG("mi_distill_minibatch", n_global >= 1, "n_global must be at least 1");
+    DST_ARG("mi_distill_minibatch", c->dst_labelled, "no mi_distill_label has filled this context's target ring");
+    if (int r = distill_alloc(c, false)) return r;
+    if (int r = begin_pass(c, "mi_distill_minibatch: ", idx, n, (int64_t)c->T * c->E, "minibatch index out of range", 1, n, copy_indices(idx, n))) return r;
+    const InputSrc src = minibatch_src(c);
+    net_forward(c, src, n, {.train = true});
+    DistillArgs a{c->hout, c->d_idx, c->dst_target, c->dY, c->dst_partial, n, c->A, (float)(1.0 / ((double)n_global * c->A))};
+    launch_distill_loss(a, 1.0 / ((double)n_global * c->A), log_slot(c).log, nullptr, 0, c->stream);
+    c->log_count += 1;
+    net_backward(c, src, n, {});
+    HIPC(hipGetLastError()); NETCHK(c);
+    return 0;
+}
+int mi_distill_loss(mi_ctx* c, mi_ctx* data, float* loss_out) {
+    DST_ARG("mi_distill_loss", c && data && loss_out, "null argument"); JOIN(c); JOIN(data);
+    DST_SIDE("mi_distill_loss", c, "student"); DST_SIDE("mi_distill_loss", data, "data");
+    DST_ARG("mi_distill_loss", !c->lse, "value_from_logits on the student is not supported");
+    DST_PAIR("mi_distill_loss", data, c, "student");
+    DST_ARG("mi_distill_loss", data->dst_labelled, "no mi_distill_label has filled the data context's target ring");
+    if (int r = distill_alloc(c, false)) return r;
+    if (int r = order_behind(data, c)) return r;                // the labels (and the ring) are complete
+    const int rows = data->T * data->E;
+    for (int r0 = 0; r0 < rows; r0 += c->NB) {
+        const int n = std::min(c->NB, rows - r0);
+        net_forward(c, InputSrc{obs_ring(data), nullptr, (long long)r0}, n, {});
+        DistillArgs a{c->hout, nullptr, data->dst_target + (size_t)r0 * data->A, nullptr, c->dst_partial, n, c->A, 0.f};
+        launch_distill_loss(a, 0.0, nullptr, c->dst_acc, r0 == 0, c->stream);
+    }
+    HIPC(hipGetLastError()); NETCHK(c);
+    double* h = (double*)c->h_f;
+    HIPC(hipMemcpyAsync(h, c->dst_acc, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));                       // (so data's next rollout cannot overtake the reads of its ring)
+    *loss_out = (float)(h[0] / ((double)rows * c->A));
     return 0;
 }
 

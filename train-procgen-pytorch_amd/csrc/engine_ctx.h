@@ -251,7 +251,11 @@ struct mi_ctx {
     // the fused MLP pass (mi_minibatch_fused; allocated by its first call, max_batch rows each): the output gradients of the layers below the
     // last (the last layer's is dfeat) and the per-sample loss terms
     float *fu_g[RES_MAX_LAYERS] = {}, *fu_terms = nullptr;
-    DeviceEnv env;                    // the device-resident env, if any (env_device.hip)
+    // distillation (mi_distill_*; each allocated by the first call that needs it): the target ring [T * E][A] -- the teacher's normalised
+    // log-probabilities of this context's observation rows, valid once a label call has filled it (dst_labelled) --, the loss kernel's
+    // block partials (max_batch rows' worth) and the running fp64 sum of mi_distill_loss
+    float* dst_target = nullptr; double *dst_partial = nullptr, *dst_acc = nullptr; bool dst_labelled = false;
+    DeviceEnv env;                   // the device-resident env, if any (env_device.hip)
     struct mi_sae* sae = nullptr;     // the sparse-autoencoder agent's state (sae.hip: mi_sae_create; released by mi_sae_destroy or mi_destroy)
     // Every device buffer, pinned buffer and event above belongs to a pool (declared last: destroyed first, while the pointers it
     // nulls still exist).  ctx_release is the one place that lets go of them.
@@ -328,9 +332,10 @@ MI_INTERNAL void linear_wgrad(mi_ctx* c, const float* dY, const float* X, int re
 
 // The host scalars of one Adam step (lr, 1-based step): the one place they are computed, for mi_optimizer_step, mi_sae_optimizer_step and
 // the op-level hook mi_op_adam alike.  beta1 / beta2 go to adam_kernel (which forms 1 - beta in fp32), w1 / w2 to sae_adam_kernel.
+// eps: the agents' Adam(eps=1e-5) unless the caller says otherwise (mi_optimizer_step_eps: the distiller's torch default, 1e-8).
 struct AdamScalars { float beta1, beta2, w1, w2, eps, step_size, bc2_sqrt; };
-static inline AdamScalars adam_scalars(float lr, int step) {
+static inline AdamScalars adam_scalars(float lr, int step, float eps = 1e-5f) {
     const double b1 = 0.9, b2 = 0.999;
     const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
-    return AdamScalars{(float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), 1e-5f, (float)((double)lr / bc1), (float)sqrt(bc2)};
+    return AdamScalars{(float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), eps, (float)((double)lr / bc1), (float)sqrt(bc2)};
 }

@@ -751,6 +751,27 @@ int mi_op_ipl_greedy(mi_ctx* c, int32_t n, int32_t A, const float* hout, int32_t
     return 0;
 }
 
+// The distillation loss kernels alone (distill.hip) on caller arrays: what mi_distill_minibatch launches between its network passes.
+// hout [n][A+1], target [n][A] (row s belongs to sample s); the mean runs over n_global * A elements.
+int mi_op_distill_loss(mi_ctx* c, int32_t n, int32_t A, const float* hout, const float* target, int32_t n_global, float* rec8_out, float* dY_out) {
+    ARG(c && hout && target, "null"); JOIN(c);
+    ARG(n >= 1 && n <= 65536, "n must be in [1, 65536]"); ARG(A >= 1 && A <= 16, "A must be in [1, 16]"); ARG(n_global >= 1, "n_global must be at least 1");
+    OpMem m("mi_op_distill_loss", c->stream);
+    const size_t nh = (size_t)n * (A + 1);
+    float *dh = nullptr, *dt = nullptr, *rec = nullptr;
+    if (int r = upload(m, hout, nh * 4, (void**)&dh)) return r;
+    if (int r = upload(m, target, (size_t)n * A * 4, (void**)&dt)) return r;
+    DistillArgs a{};
+    HIPC(m.out(&a.dY, nh * 4, "dY")); HIPC(m.out(&a.partial, (size_t)distill_blocks(n) * 8, "the block partials")); HIPC(m.out(&rec, 8 * 4, "the record"));
+    const double inv_count = 1.0 / ((double)n_global * A);
+    a.hout = dh; a.idx = nullptr; a.target = dt; a.n = n; a.A = A; a.scale = (float)inv_count;
+    launch_distill_loss(a, inv_count, rec, nullptr, 0, c->stream);
+    if (int r = op_finish(c, m)) return r;
+    if (rec8_out) HIPC(hipMemcpy(rec8_out, rec, 8 * 4, hipMemcpyDeviceToHost));
+    if (dY_out) HIPC(hipMemcpy(dY_out, a.dY, nh * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // The policy / value heads at update size (heads.hip) on caller data through the production launchers; independent of the context's sizes.
 //   mode 0: launch_heads_fwd: out = hout [n][O] = feat [n][256] Wh^T + bh.  H must be 256.
 //   mode 1: launch_heads_bwd with its slab sum: out = dfeat [n][H] = (dY [n][O] Wh) * (feat > 0 if relu_mask); gW [O][H] and gb [O] are in / out

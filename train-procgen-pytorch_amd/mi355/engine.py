@@ -69,6 +69,7 @@ EXPORTS = ("mi_last_error mi_create mi_destroy mi_sync mi_host_alloc mi_host_fre
            "mi_sae_create mi_sae_destroy mi_sae_param_count mi_sae_set_params mi_sae_get_params mi_sae_get_grads mi_sae_set_adam_state mi_sae_get_adam_state mi_sae_put_ring "
            "mi_sae_get_hidden mi_sae_get_logits mi_sae_step mi_sae_minibatch mi_sae_probe_minibatch mi_sae_optimizer_step mi_sae_debug_forward "
            "mi_ipl_minibatch mi_ipl_read_pred mi_predict_greedy mi_op_ipl_loss mi_op_ipl_greedy "
+           "mi_distill_label mi_distill_minibatch mi_distill_loss mi_optimizer_step_eps mi_op_distill_loss mi_distill_targets "
            "mi_env_cartpole_create mi_env_cartpole_swing_create mi_env_mountain_car_create mi_env_reset mi_env_step mi_env_rollout mi_env_rollout_resident mi_env_evaluate mi_env_get_state mi_env_set_state").split()
 
 
@@ -658,8 +659,51 @@ class Engine:
         self._chk(self.lib.mi_op_ipl_greedy(self._ctx, C.c_int32(hout.shape[0]), C.c_int32(hout.shape[1] - 1), _fp(hout), _fp(act)))
         return act
 
+    # ------------------------------------------------------------------ policy distillation (distill.py)
+    def distill_label(self, teacher):
+        """The teacher engine's normalised log-probabilities of all T * E observation rows of THIS engine's ring -> this engine's target
+        ring (mi_distill_label); `teacher` may be this engine itself.  Asynchronous, ordered on both streams."""
+        self._chk(self.lib.mi_distill_label(self._ctx, teacher._ctx))
+
+    def distill_targets(self):
+        """This engine's target ring (T * E, A) as the last distill_label left it (mi_distill_targets)."""
+        out = np.empty((self.T * self.E, self.A), np.float32)
+        self._chk(self.lib.mi_distill_targets(self._ctx, _fp(out), C.c_int64(out.size)))
+        return out
+
+    def distill_minibatch(self, idx, n_global):
+        """One minibatch of the distiller's fit on ring rows idx (mi_distill_minibatch): MSE of the twice-normalised log-probabilities against
+        the target ring; gradients accumulate, one record {loss, 0, 0, 0, loss, 0, 0, 0} in the loss log."""
+        idx = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        self._chk(self.lib.mi_distill_minibatch(self._ctx, _fp(idx), C.c_int32(idx.size), C.c_int32(n_global)))
+
+    def distill_loss(self, data):
+        """Forward only: this engine's policy on all rows of `data`'s ring against data's target ring -> the mean squared error
+        (mi_distill_loss).  Changes neither the gradients nor the loss log."""
+        out = C.c_float(0)
+        self._chk(self.lib.mi_distill_loss(self._ctx, data._ctx, C.byref(out)))
+        return out.value
+
+    def optimizer_step_eps(self, lr, max_grad_norm, eps, adam_step, want_norm=False):
+        """optimizer_step with the caller's Adam eps (mi_optimizer_step_eps); max_grad_norm = inf: no clipping."""
+        g = C.c_float(0)
+        self._chk(self.lib.mi_optimizer_step_eps(self._ctx, C.c_float(lr), C.c_float(max_grad_norm), C.c_float(eps), C.c_int32(adam_step),
+                                                 C.byref(g) if want_norm else None))
+        return g.value if want_norm else None
+
+    def op_distill_loss(self, hout, target, n_global=None):
+        """The distillation loss kernels alone on caller arrays (mi_op_distill_loss): hout (n, A + 1), target (n, A) ->
+        (record (8,), dY (n, A + 1)); the mean runs over n_global * A elements (default: n)."""
+        hout = _f32(hout)
+        n, A = hout.shape[0], hout.shape[1] - 1
+        target = _f32(target).reshape(n, A)
+        rec, dY = np.empty(8, np.float32), np.empty((n, A + 1), np.float32)
+        self._chk(self.lib.mi_op_distill_loss(self._ctx, C.c_int32(n), C.c_int32(A), _fp(hout), _fp(target),
+                                              C.c_int32(n if n_global is None else n_global), _fp(rec), _fp(dY)))
+        return rec, dY
+
     # ------------------------------------------------------------------ sparse-autoencoder agent (algo: sae)
-    SAE, PROBE = 0, 1                      # `which` of the mi_sae_* entry points
+    SAE, PROBE = 0, 1                     # `which` of the mi_sae_* entry points
     SAE_INPUT_DIM = 2048                   # ImpalaModel.encoded_dim
     SAE_DIMS = tuple(range(64, 4097, 64))
 

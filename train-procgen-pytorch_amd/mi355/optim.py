@@ -12,8 +12,8 @@ from . import layout
 
 
 class DeviceAdam:
-    def __init__(self, policy, engine, lr, eps=1e-5):
-        self.policy, self.engine = policy, engine
+    def __init__(self, policy, engine, lr, eps=1e-5, stateless=()):
+        self.policy, self.engine, self.eps = policy, engine, eps
         self._params = [p for n, p in policy.named_parameters() if not n.startswith("gru.")]
         self._names = [n for n, _ in policy.named_parameters() if not n.startswith("gru.")]
         # the container spans ALL policy parameters like the reference's optim.Adam(policy.parameters()) (a frozen GRU
@@ -23,6 +23,8 @@ class DeviceAdam:
         # logsumexp_logits_is_v: fc_value never receives a gradient (policy.py:77-78), so torch's Adam never creates state for it -- like
         # the frozen GRU it stays in param_groups and out of `state`; the device moments of its slice are and stay zero
         self._stateless = {"fc_value.weight", "fc_value.bias"} if getattr(policy, "logsumexp_logits_is_v", False) else set()
+        # `stateless`: further tensors the caller's loss never reaches (the distiller's MSE leaves fc_value.grad None in the reference)
+        self._stateless |= set(stateless)
 
     @property
     def param_groups(self):
@@ -38,6 +40,13 @@ class DeviceAdam:
     def step(self, max_grad_norm, want_norm=False):
         self.step_count += 1
         out = self.engine.optimizer_step(self.lr, max_grad_norm, self.step_count, want_norm)
+        self.policy.mark_device_updated()
+        return out
+
+    def step_eps(self, max_grad_norm=float("inf"), want_norm=False):
+        """step() with this optimizer's own eps (mi_optimizer_step_eps; step() is the agents' Adam(eps=1e-5)); inf: no clipping."""
+        self.step_count += 1
+        out = self.engine.optimizer_step_eps(self.lr, max_grad_norm, self.eps, self.step_count, want_norm)
         self.policy.mark_device_updated()
         return out
 
