@@ -528,6 +528,25 @@ int mi_op_gemm(mi_ctx* ctx, int32_t M, int32_t N, int32_t K, const float* A, int
  * Outputs are poisoned and followed by canary bands as in mi_op_resblock. */
 int mi_op_fc_bf16(mi_ctx* ctx, int32_t mode, int32_t n, int32_t D, const float* x, const float* W, const float* b, const float* dy,
                   float* out, float* out_b);
+/* op-level: the generic GEMM of the linear layers (csrc/gemm.hip, direct and split-K with its reduce) on caller data through the production
+ * launchers; independent of the context's sizes and precision.  d0, d1, d2 = (n, in, out) for forms 0 .. 2, (M, N, K) for form 3.
+ * form 0: linear_fwd.   A = X [n][in], B = W [out][in], bias [out] or NULL -> C = Y [n][out] = relu?(relu?(X) W^T + b).  Flags RELU_X, RELU_OUT, X_BF16.
+ * form 1: linear_dgrad. A = dY [n][out], B = W [out][in], mask [n][in] or NULL -> C = dX [n][in] = (dY W) * (mask > 0).  Flag X_BF16.
+ * form 2: linear_wgrad. A = dY [n][out], B = X [n][in]; C = gW [out][in] and gb [out] (out <= 4096) in / out: += dY^T relu?(X), += colsum(dY).
+ *         Flags RELU_X, X_BF16.
+ * form 3: launch_gemm itself.  strides5 = {sam, sak, sbk, sbn, ldc}: A(m, k) = A[m sam + k sak], B(k, n) = B[k sbk + n sbn]; C and mask are
+ *         [M][ldc] (ldc >= N), bias [N] or NULL.  Flags RELU_OUT, ACCUMULATE (C in / out), USE_WS (without it the workspace is NULL and K is
+ *         never split, as the SAE's calls).  ws_floats < 0: the context's workspace size; otherwise an override no larger than it.
+ * X_BF16: the activation-typed operands (X; for form 1 the mask and dX) are bf16 on the device: they go up rounded on the host and dX
+ * comes back widened.  strides5 is NULL and ws_floats negative outside form 3.
+ * plan2 = {split, k_chunk}: the number of K slabs the call ran (1 = one launch without the reduce) and K per slab.
+ * Outputs are poisoned and followed by canary bands as in mi_op_resblock, in / out targets start from the caller's values, and the slabs of
+ * a split call are poisoned too; with ldc > N, columns N .. ldc - 1 of C come back as the poison (all-ones words) or the call fails with -4.
+ * Refused (-1): a size below 1 or above 65536, a tensor above 2^26 elements (the limits only keep the hook's allocations sane), ws_floats
+ * above the context's, a flag or operand the form does not have. */
+enum { MI_LIN_RELU_X = 1, MI_LIN_RELU_OUT = 2, MI_LIN_X_BF16 = 4, MI_LIN_ACCUMULATE = 8, MI_LIN_USE_WS = 16 };
+int mi_op_linear(mi_ctx* ctx, int32_t form, int32_t d0, int32_t d1, int32_t d2, const int64_t* strides5, int32_t flags, int64_t ws_floats,
+                 const float* A, const float* B, const float* bias, const float* mask, float* C, float* gb, int32_t* plan2);
 /* op-level: the fixed-order sums behind every weight and bias gradient (csrc/reduce.hip) on caller data through the production launchers,
  * any context.  The targets are in / out (the kernels accumulate) and sit in poisoned, canary-banded buffers as in mi_op_resblock.
  * mode 0: launch_reduce_slabs.  src [a = nslab][b = slab_len] (src_len = a * b); dst_w [n_w] += the sums of elements [0, n_w), dst_b [n_b] +=

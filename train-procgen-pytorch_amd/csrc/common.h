@@ -137,6 +137,9 @@ struct GemmArgs {
     float* ws; size_t ws_floats;             // split-K slab workspace of the calling context (null: never split)
 };
 void launch_gemm(const GemmArgs& g, hipStream_t st);
+// the plan launch_gemm runs for g (M, N, K, ws, ws_floats): split = the number of K slabs (1: one launch, no reduce), k_chunk = K per slab
+struct GemmPlan { int split, k_chunk; };
+GemmPlan gemm_plan(const GemmArgs& g);
 
 // ---------------------------------------------------------------- pool.hip: stand-alone MaxPool2d(3,2,1)
 void launch_maxpool_fwd(const float* in, float* out, uint8_t* arg, int n, int hw, int c, hipStream_t st);

@@ -578,6 +578,122 @@ int mi_op_fc_bf16(mi_ctx* c, int32_t mode, int32_t n, int32_t D, const float* x,
     return 0;
 }
 
+// The generic GEMM (gemm.hip: gemm_kernel, gemm_splitk_reduce) on caller data through the production launchers; independent of the
+// context's sizes and precision.  d0, d1, d2 = (n, in, out) for forms 0 .. 2 and (M, N, K) for form 3.
+//   form 0: linear_fwd    A = X [n][in], B = W [out][in], bias [out] or null -> C = Y [n][out]       flags: RELU_X, RELU_OUT, X_BF16
+//   form 1: linear_dgrad  A = dY [n][out], B = W [out][in], mask [n][in] or null -> C = dX [n][in]   flags: X_BF16 (mask up as bf16, dX back widened)
+//   form 2: linear_wgrad  A = dY [n][out], B = X [n][in]; C = gW [out][in] and gb [out] in / out     flags: RELU_X, X_BF16
+//   form 3: launch_gemm itself with strides5 = {sam, sak, sbk, sbn, ldc}: A(m, k) = A[m sam + k sak], B(k, n) = B[k sbk + n sbn], C and mask
+//           [M][ldc], bias [N] or null.  flags: RELU_OUT, ACCUMULATE (C in / out: its [M][N] part goes up), USE_WS (else a null workspace:
+//           never split).  ws_floats < 0: the context's own; otherwise an override no larger than it.  Columns N .. ldc - 1 of C must
+//           come back as poison: a write there fails with -4.
+// plan2 = {split, k_chunk} of gemm_plan for the call.  The slabs of a split call are poisoned as well: the reduce reads what the GEMM wrote.
+int mi_op_linear(mi_ctx* c, int32_t form, int32_t d0, int32_t d1, int32_t d2, const int64_t* strides5, int32_t flags, int64_t ws_floats,
+                 const float* A, const float* B, const float* bias, const float* mask, float* C, float* gb, int32_t* plan2) {
+    ARG(c && A && B && C && plan2, "null"); JOIN(c);
+    ARG(form >= 0 && form <= 3, "form");
+    ARG(d0 >= 1 && d1 >= 1 && d2 >= 1, "sizes must be positive");
+    constexpr int64_t LIM = (int64_t)1 << 26;
+    ARG(d0 <= 65536 && d1 <= 65536 && d2 <= 65536 && (int64_t)d0 * d1 <= LIM && (int64_t)d1 * d2 <= LIM && (int64_t)d0 * d2 <= LIM,
+        "sizes: each at most 65536, every tensor at most 2^26 elements (the limit only keeps the hook's allocations sane)");
+    static const int allowed[4] = {MI_LIN_RELU_X | MI_LIN_RELU_OUT | MI_LIN_X_BF16, MI_LIN_X_BF16, MI_LIN_RELU_X | MI_LIN_X_BF16,
+                                   MI_LIN_RELU_OUT | MI_LIN_ACCUMULATE | MI_LIN_USE_WS};
+    ARG(!(flags & ~allowed[form]), "flags: an option this form does not have");
+    ARG(form == 3 || (!strides5 && ws_floats < 0), "strides5 and ws_floats belong to form 3");
+    ARG(form != 0 || !mask, "form 0 has no mask");
+    ARG(form != 1 || !bias, "form 1 has no bias");
+    ARG(form != 2 || (gb && !bias && !mask && d2 <= COLSUM_MAX_N), "form 2: gb, no bias, no mask, out <= 4096");
+    const bool bf = flags & MI_LIN_X_BF16, relu_x = flags & MI_LIN_RELU_X, relu_out = flags & MI_LIN_RELU_OUT;
+    const std::string hook = "mi_op_linear form " + std::to_string(form);
+    OpMem m(hook.c_str(), c->stream);
+    auto up = [&](const float* h, size_t cnt, bool as_bf16, void** d) -> int {
+        if (as_bf16) { const auto v = host_to_bf16(h, cnt); return upload(m, v.data(), cnt * 2, d); }
+        return upload(m, h, cnt * 4, d);
+    };
+    GemmArgs g{};          // forms 0 .. 2: the sizes and the workspace linear_* will pass, for the plan alone
+    g.ws = c->gemm_ws; g.ws_floats = c->gemm_ws_floats;
+    void *dA = nullptr, *dB = nullptr, *dbias = nullptr, *dmask = nullptr;
+    auto poison_slabs = [&](const GemmPlan& p) -> int {
+        plan2[0] = p.split; plan2[1] = p.k_chunk;
+        if (p.split > 1) HIPC(hipMemsetAsync(g.ws, 0xFF, (size_t)p.split * g.M * g.N * 4, c->stream));
+        return 0;
+    };
+    if (form != 3) {
+        const int n = d0, in = d1, out = d2;
+        const size_t nx = (size_t)n * in, ny = (size_t)n * out, nw = (size_t)out * in;
+        if (form == 0) { g.M = n; g.N = out; g.K = in; } else if (form == 1) { g.M = n; g.N = in; g.K = out; } else { g.M = out; g.N = in; g.K = n; }
+        if (int r = poison_slabs(gemm_plan(g))) return r;
+        if (form == 0) {
+            float* y = nullptr;
+            if (int r = up(A, nx, bf, &dA)) return r;
+            if (int r = upload(m, B, nw * 4, &dB)) return r;
+            if (bias) { if (int r = upload(m, bias, (size_t)out * 4, &dbias)) return r; }
+            HIPC(m.out(&y, ny * 4, "Y"));
+            linear_fwd(c, (const float*)dA, relu_x, (const float*)dB, (const float*)dbias, y, n, in, out, relu_out, bf);
+            if (int r = op_finish(c, m)) return r;
+            HIPC(hipMemcpy(C, y, ny * 4, hipMemcpyDeviceToHost));
+            return 0;
+        }
+        if (form == 1) {
+            void* dx = nullptr;
+            if (int r = upload(m, A, ny * 4, &dA)) return r;
+            if (int r = upload(m, B, nw * 4, &dB)) return r;
+            if (mask) { if (int r = up(mask, nx, bf, &dmask)) return r; }
+            HIPC(m.out(&dx, nx * (bf ? 2 : 4), "dX"));
+            linear_dgrad(c, (const float*)dA, (const float*)dB, (const float*)dmask, (float*)dx, n, in, out, bf);
+            if (int r = op_finish(c, m)) return r;
+            if (!bf) { HIPC(hipMemcpy(C, dx, nx * 4, hipMemcpyDeviceToHost)); return 0; }
+            std::vector<uint16_t> h(nx);
+            HIPC(hipMemcpy(h.data(), dx, nx * 2, hipMemcpyDeviceToHost));
+            host_from_bf16(h.data(), C, nx);
+            return 0;
+        }
+        float *gw = nullptr, *dgb = nullptr;
+        if (int r = upload(m, A, ny * 4, &dA)) return r;
+        if (int r = up(B, nx, bf, &dB)) return r;
+        HIPC(m.out(&gw, nw * 4, "gW")); HIPC(m.out(&dgb, (size_t)out * 4, "gb"));
+        HIPC(hipStreamSynchronize(c->stream));          // (the fills run on the context's stream, the copies on the null stream)
+        HIPC(hipMemcpy(gw, C, nw * 4, hipMemcpyHostToDevice)); HIPC(hipMemcpy(dgb, gb, (size_t)out * 4, hipMemcpyHostToDevice));
+        linear_wgrad(c, (const float*)dA, (const float*)dB, relu_x, gw, dgb, n, in, out, bf);
+        if (int r = op_finish(c, m)) return r;
+        HIPC(hipMemcpy(C, gw, nw * 4, hipMemcpyDeviceToHost)); HIPC(hipMemcpy(gb, dgb, (size_t)out * 4, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    ARG(strides5, "form 3 needs strides5");
+    const int M = d0, N = d1, K = d2;
+    const int64_t sam = strides5[0], sak = strides5[1], sbk = strides5[2], sbn = strides5[3], ldc = strides5[4];
+    ARG(sam >= 1 && sak >= 1 && sbk >= 1 && sbn >= 1 && ldc >= N, "form 3: positive strides, ldc >= N");
+    ARG(sam <= LIM && sak <= LIM && sbk <= LIM && sbn <= LIM && ldc <= LIM, "form 3: a stride above 2^26");
+    const int64_t na = (M - 1) * sam + (K - 1) * sak + 1, nb = (K - 1) * sbk + (N - 1) * sbn + 1, nc = (int64_t)M * ldc;
+    ARG(na <= LIM && nb <= LIM && nc <= LIM, "form 3: an operand spans more than 2^26 elements");
+    ARG(ws_floats < 0 || (size_t)ws_floats <= c->gemm_ws_floats, "ws_floats above the context's workspace");
+    float* dc = nullptr;
+    if (int r = upload(m, A, (size_t)na * 4, &dA)) return r;
+    if (int r = upload(m, B, (size_t)nb * 4, &dB)) return r;
+    if (bias) { if (int r = upload(m, bias, (size_t)N * 4, &dbias)) return r; }
+    if (mask) { if (int r = upload(m, mask, (size_t)nc * 4, &dmask)) return r; }
+    HIPC(m.out(&dc, (size_t)nc * 4, "C"));
+    if (flags & MI_LIN_ACCUMULATE) {
+        HIPC(hipStreamSynchronize(c->stream));          // (the fill runs on the context's stream, the copy on the null stream)
+        HIPC(hipMemcpy2D(dc, (size_t)ldc * 4, C, (size_t)ldc * 4, (size_t)N * 4, M, hipMemcpyHostToDevice));
+    }
+    g.ws = (flags & MI_LIN_USE_WS) ? c->gemm_ws : nullptr;
+    g.ws_floats = !g.ws ? 0 : ws_floats < 0 ? c->gemm_ws_floats : (size_t)ws_floats;
+    g.A = (const float*)dA; g.B = (const float*)dB; g.C = dc; g.M = M; g.N = N; g.K = K;
+    g.sam = sam; g.sak = sak; g.sbk = sbk; g.sbn = sbn; g.ldc = ldc;
+    g.bias = (const float*)dbias; g.mask = (const float*)dmask; g.relu_out = relu_out; g.accumulate = (flags & MI_LIN_ACCUMULATE) ? 1 : 0;
+    if (int r = poison_slabs(gemm_plan(g))) return r;
+    launch_gemm(g, c->stream);
+    if (int r = op_finish(c, m)) return r;
+    HIPC(hipMemcpy(C, dc, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    for (int r = 0; r < M; ++r)
+        for (int64_t q = N; q < ldc; ++q) {
+            uint32_t u; memcpy(&u, C + (size_t)r * ldc + q, 4);
+            if (u != 0xFFFFFFFFu) return fail(-4, hook + ": a kernel wrote into the padding of C (row " + std::to_string(r) + ", column " + std::to_string(q) + ")");
+        }
+    return 0;
+}
+
 // The fixed-order sums of reduce.hip on caller data through the production launchers; independent of the context's sizes.  Every
 // accumulation target is an OpMem::out buffer that starts from the caller's values, so an element written past its end trips a band.
 //   mode 0: launch_reduce_slabs(src [a = nslab][b = slab_len], dst_w [n_w], dst_b [n_b] or null with n_b = 0)

@@ -123,27 +123,35 @@ __global__ void gemm_splitk_reduce(const float* ws, int split, GemmArgs g) {
     g.C[o] = v;
 }
 
-// split-K slabs live in the caller's workspace (GemmArgs.ws, one per context: two contexts on two streams must not share it)
-void launch_gemm(const GemmArgs& g, hipStream_t st) {
-    if (g.M <= 0 || g.N <= 0) return;
+// The split plan of one call, from the sizes and the workspace alone (launch_gemm and the op-level hook mi_op_linear both take it from
+// here).  Few output tiles and a long K (weight gradients: K = batch; rollout-sized forward GEMMs: M = n_envs): K is split over
+// workgroups, slabs summed in a fixed order by the reduce kernel (which carries the epilogue).  split = min(512 / tiles, K / 128), lowered
+// until the slabs fit the workspace; k_chunk is rounded up to the K tile, so the run can have fewer slabs than first planned.
+GemmPlan gemm_plan(const GemmArgs& g) {
     const int tm = (g.M + 63) / 64, tn = (g.N + 63) / 64;
     int split = 1;
-    // few output tiles and a long K (weight gradients: K = batch; rollout-sized forward GEMMs: M = n_envs):
-    // split K over workgroups, slabs summed in a fixed order by the reduce kernel (which carries the epilogue).
     if (g.K >= 512 && tm * tn < 192 && g.ws) {
         split = 512 / (tm * tn);
         if (split > g.K / 128) split = g.K / 128;
         if (split < 1) split = 1;
         while (split > 1 && (size_t)split * g.M * g.N > g.ws_floats) --split;
     }
-    int k_chunk = ((g.K + split - 1) / split + 31) / 32 * 32;
-    if (split == 1) {
-        hipLaunchKernelGGL(gemm_kernel, dim3(tn, tm, 1), dim3(256), 0, st, g, k_chunk, (float*)nullptr);
+    const int k_chunk = ((g.K + split - 1) / split + 31) / 32 * 32;
+    if (split > 1) split = (g.K + k_chunk - 1) / k_chunk;
+    return GemmPlan{split, k_chunk};
+}
+
+// split-K slabs live in the caller's workspace (GemmArgs.ws, one per context: two contexts on two streams must not share it)
+void launch_gemm(const GemmArgs& g, hipStream_t st) {
+    if (g.M <= 0 || g.N <= 0) return;
+    const int tm = (g.M + 63) / 64, tn = (g.N + 63) / 64;
+    const GemmPlan p = gemm_plan(g);
+    if (p.split == 1) {
+        hipLaunchKernelGGL(gemm_kernel, dim3(tn, tm, 1), dim3(256), 0, st, g, p.k_chunk, (float*)nullptr);
     } else {
-        split = (g.K + k_chunk - 1) / k_chunk;
-        hipLaunchKernelGGL(gemm_kernel, dim3(tn, tm, split), dim3(256), 0, st, g, k_chunk, g.ws);
+        hipLaunchKernelGGL(gemm_kernel, dim3(tn, tm, p.split), dim3(256), 0, st, g, p.k_chunk, g.ws);
         const long long tot = (long long)g.M * g.N;
         hipLaunchKernelGGL(gemm_splitk_reduce, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st,
-                           (const float*)g.ws, split, g);
+                           (const float*)g.ws, p.split, g);
     }
 }

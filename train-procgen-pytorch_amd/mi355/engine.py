@@ -64,7 +64,7 @@ EXPORTS = ("mi_last_error mi_create mi_destroy mi_sync mi_host_alloc mi_host_fre
            "mi_get_params mi_copy_params mi_get_grads mi_set_adam_state mi_get_adam_state mi_put_obs mi_get_obs mi_put_step "
            "mi_put_policy_outputs mi_read_field mi_write_field mi_policy_step mi_rollout_step mi_rollout_groups mi_rollout_lane_info mi_rollout_submit mi_rollout_wait mi_predict_staged mi_value_saliency mi_commit_staged mi_set_gru mi_rec_state mi_get_hidden mi_rec_begin mi_get_hidden_ring mi_forward_rec mi_forward mi_compute_estimates "
            "mi_adv_stats mi_adv_apply mi_minibatch mi_minibatch_multi mi_minibatch_fused mi_optimizer_step mi_loss_log_read mi_device_ptr "
-           "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_op_fc_bf16 mi_op_reduce mi_op_adam mi_op_adv_merge mi_op_heads mi_op_sample mi_op_ppo_loss mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_gru_step mi_debug_step_latency mi_debug_lane_probe mi_debug_live_resources "
+           "mi_set_multirank mi_minibatch_finish mi_loss_log_finalize mi_profile_enable mi_profile_read mi_profile_class_name mi_op_conv3x3 mi_op_resblock mi_op_maxpool mi_op_gemm mi_op_fc_bf16 mi_op_linear mi_op_reduce mi_op_adam mi_op_adv_merge mi_op_heads mi_op_sample mi_op_ppo_loss mi_selftest_mfma mi_debug_read mi_debug_flags mi_comm_unique_id mi_comm_init mi_comm_destroy mi_allreduce_arm mi_allreduce_grads mi_allreduce_buffer mi_adv_normalize_global mi_minibatch_positions mi_debug_philox mi_debug_gru_step mi_debug_step_latency mi_debug_lane_probe mi_debug_live_resources "
            "mi_gru_train mi_minibatch_rec mi_get_gru mi_get_gru_grads mi_get_gru_adam_state mi_set_gru_adam_state mi_debug_gru_seq "
            "mi_sae_create mi_sae_destroy mi_sae_param_count mi_sae_set_params mi_sae_get_params mi_sae_get_grads mi_sae_set_adam_state mi_sae_get_adam_state mi_sae_put_ring "
            "mi_sae_get_hidden mi_sae_get_logits mi_sae_step mi_sae_minibatch mi_sae_probe_minibatch mi_sae_optimizer_step mi_sae_debug_forward "
@@ -919,6 +919,44 @@ class Engine:
         self._chk(self.lib.mi_op_fc_bf16(self._ctx, C.c_int32(mode), C.c_int32(n), C.c_int32(D), _fp(x), _fp(W), _fp(b), _fp(dy), _fp(out),
                                          _fp(out_b)))
         return (out, out_b) if mode == 3 else out
+
+    def op_linear(self, form, A, B, bias=None, mask=None, C0=None, gb0=None, relu_x=False, relu_out=False, x_bf16=False, dims=None,
+                  strides=None, use_ws=True, ws_floats=-1):
+        """The generic GEMM (csrc/gemm.hip) on caller data through the production launchers (mi_op_linear), any context
+        -> (out, (split, k_chunk)), the plan the call ran.
+        form 0: A = X (n, in), B = W (out, in), bias -> Y (n, out); form 1: A = dY (n, out), B = W, mask (n, in) -> dX (n, in);
+        form 2: A = dY, B = X (n, in), C0 = gW0 (out, in), gb0 -> out = (gW0 + dY^T relu?(X), gb0 + colsum(dY)).  x_bf16: the activation-typed
+        operands are bf16 on the device.
+        form 3: launch_gemm itself; A and B are flat buffers, dims = (M, N, K), strides = (sam, sak, sbk, sbn, ldc), mask and C0 (M, ldc);
+        C0 is given exactly when the call accumulates.  -> C (M, ldc) whole: the columns from N on hold the poison (all-ones words)."""
+        A, B = _f32(A), _f32(B)
+        bias, mask = (None if a is None else _f32(a) for a in (bias, mask))
+        flags = (1 if relu_x else 0) | (2 if relu_out else 0) | (4 if x_bf16 else 0)
+        out_b, st = None, None
+        if form == 3:
+            M, N, K = dims
+            st = np.asarray(strides, np.int64)
+            assert st.shape == (5,)
+            flags |= (8 if C0 is not None else 0) | (16 if use_ws else 0)
+            out = np.empty((max(M, 1), int(st[4])), np.float32) if C0 is None else np.array(C0, dtype=np.float32, order="C")
+            assert out.shape == (max(M, 1), int(st[4]))
+            d = (M, N, K)
+        else:
+            n = A.shape[0]
+            if form == 0:
+                d = (n, A.shape[1], B.shape[0])
+                out = np.empty((n, d[2]), np.float32)
+            elif form == 1:
+                d = (n, B.shape[1], B.shape[0])
+                out = np.empty((n, d[1]), np.float32)
+            else:
+                d = (n, B.shape[1], A.shape[1])
+                out, out_b = np.array(C0, dtype=np.float32, order="C"), np.array(gb0, dtype=np.float32, order="C")
+        plan = np.zeros(2, np.int32)
+        self._chk(self.lib.mi_op_linear(self._ctx, C.c_int32(form), C.c_int32(d[0]), C.c_int32(d[1]), C.c_int32(d[2]), _fp(st), C.c_int32(flags),
+                                        C.c_int64(ws_floats), _fp(A), _fp(B), _fp(bias), _fp(mask), _fp(out), _fp(out_b), _fp(plan)))
+        plan = (int(plan[0]), int(plan[1]))
+        return ((out, out_b) if form == 2 else out), plan
 
     def _op_reduce(self, mode, src, a, b, ld, desc, dst_w, dst_b):
         src, w = _f32(src).reshape(-1), np.array(dst_w, dtype=np.float32, order="C").reshape(-1)
