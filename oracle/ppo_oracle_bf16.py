@@ -10,7 +10,10 @@ the fp32 engine is held to ppo_oracle.py -- instead of "the same direction as th
 Parity status: PINNED through ppo_oracle.py: with the rounding switched off (`rounding=False`) every function here must
 reproduce ppo_oracle.py's autograd results (tests/test_oracle_golden.py::test_bf16_oracle_without_rounding_is_the_fp32_oracle),
 which in turn is pinned to the reference's golden vectors G3 / G4.  The rounding points themselves are the build's own
-design (the reference has no bf16 path); they are checked kernel by kernel in tests/test_gpu_bf16.py.
+design (the reference has no bf16 path); they are checked kernel by kernel in tests/test_gpu_bf16.py (to bf16's 1e-2) and ENFORCED
+exactly in tests/test_gpu_bf16_exact.py: on dyadic-grid inputs whose fp32 sums are exact in any order (tests/exact_inputs.py), every
+output of the conv, conv + pool, pool and residual-block kernels must equal the bf16 round-to-nearest-even of the float64 value at
+precisely the rounding points named below -- a second rounding, a truncation or a rounding moved past the bias fails there.
 
 Reference lines followed: common/model.py:134-209 (ImpalaModel / ImpalaBlock / ResidualBlock), common/policy.py:74-87,
 agents/ppo.py:119-170 (loss + backward)."""
